@@ -4,6 +4,11 @@
     python bench.py --gpus N --steps K --warmup W        (N > 1 without a launcher: bench.py starts the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
+    options: --full (everything below `grad_steps_per_sec`), --dump-outputs DIR (the last timed step's results as .npy,
+             from a bit-reproducible replay of the timed path)
+
+A plain run sets up, settles, warms up, times the K steps, writes --dump-outputs if asked and prints the headline fields
+(metric ... grad_steps_per_sec, config).  `--full` then goes on with everything else in the same line.
 
 HEADLINE (the one JSON line, rank 0): BASELINE.json configs[2] exactly -- one gradient step of the reference's stage-1
 loop shape (src/train_gaussians.py:96-181, no densification) on ONE 1920x1080 view of the 500k strand-aligned model per
@@ -15,6 +20,7 @@ scaling: one view per GPU per step at every N (a global step covers N views).
   value               = sum over the timed steps' views of P_vis / elapsed: Gaussians per second through the whole step,
                         P_vis = Gaussians of the model that pass the cull of the view (radii > 0), NOT the model size
   grad_steps_per_sec  = 1 / t_step
+--full only:
   roofline            : k_render_bwd_cells = K8 (the dominant kernel): SURVEY 8(d) algorithmic bytes / HIP-event duration on the
                         launch stream over solo passes cycling over the same cameras, against 8 TB/s HBM; `traffic` from the
                         committed rocprofv3 FETCH_SIZE / WRITE_SIZE passes (profiles/).
@@ -88,14 +94,23 @@ def main():
     ap.add_argument("--no-2m", action="store_true", help="skip the config5_2M block (BASELINE configs[4]'s model, N = 1)")
     ap.add_argument("--no-camera-block", action="store_true", help="skip the dropin_trainable_camera_step block (N = 1)")
     ap.add_argument("--no-strand-block", action="store_true", help="skip the strand_stage block (render_hair at the reference's size, N = 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else the line can carry: repeat, solo kernel times and "
+                         "roofline, replica check, the side blocks (each --no-* above skips one), op_only, cpu_baseline, "
+                         "host_gc; off: the line holds the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0), from a replay of the same "
+                         "steps with the gradient walk's additions in a fixed order: the same every run (see dump_outputs)")
     args = ap.parse_args()
 
-    # `--gpus N` without a launcher: become the launcher (one process per GPU, ranks over RCCL), never a silent 1-rank run
+    # `--gpus N` without a launcher: become the launcher (one process per GPU, ranks over RCCL), never a silent 1-rank run.
+    # The ranks run as child processes; this one only waits for them (it never touches the GPU).
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        import subprocess
         cmd = relaunch_command(args.gpus, sys.argv[1:])
         sys.stderr.write("bench.py: --gpus %d without torchrun; launching %s\n" % (args.gpus, " ".join(cmd[1:10]) + " ..."))
         sys.stderr.flush()
-        os.execv(sys.executable, cmd)
+        sys.exit(subprocess.call(cmd))
 
     from gaussianhaircut_amd import _lib
     from gaussianhaircut_amd import diff_gaussian_rasterization as dgr
@@ -190,7 +205,8 @@ def main():
             gc_log["gen2_collections"] += 1
             gc_log["gen2_ms"] += dt_
             gc_log["longest_ms"] = max(gc_log["longest_ms"], dt_)
-    _gc.callbacks.append(_gc_cb)
+    if args.full:
+        _gc.callbacks.append(_gc_cb)
 
     def timed_steps(model_, pool_, v, n_warm, n_steps, it0=0, gv=None, after_step=None):
         """n_warm untimed + n_steps timed gradient steps; step i renders cameras (i v + j) mod len(pool), j < v.
@@ -269,6 +285,65 @@ def main():
     timed_steps(model, pool, V, n_settle, 0)
     elapsed, used = timed_steps(model, pool, V, Wm, K, it0=n_settle)
     ms_per_step = 1e3 * elapsed / K
+    fused_steps = getattr(model.optimizer, "fused_steps", 0)
+    if args.dump_outputs:
+        # The timed steps add each gradient line's contributions in the GPU's scheduling order (as the reference's atomicAdd
+        # does), and Adam turns last-bit differences of near-cancelled gradients into whole steps: the parameters of two runs
+        # part within a few steps.  What is dumped is the same path replayed from the same seeded start -- a fresh scene, the
+        # same settle, warm-up and timed steps on the same cameras and iterations -- with those additions in a fixed order
+        # (ghr_set_deterministic: bit-reproducible), so that two runs, and two builds, can be compared output for output.
+        model_d, pool_d = build_scene(spec, NC)
+        prev_det = L.ghr_set_deterministic(1)
+        try:
+            for it0, n in ((0, n_settle), (n_settle, Wm + K)):  # (timed_steps: settle, then warm-up + timed steps)
+                for i in range(n):
+                    loss_d = training_step(model_d, [pool_d[(i * V + j) % len(pool_d)] for j in range(V)], bg, opt,
+                                           it0 + i + 1, global_views=V * world, streams=args.streams)
+            sync_all()
+        finally:
+            L.ghr_set_deterministic(prev_det)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, model_d, loss_d)
+        del model_d, pool_d, loss_d
+        torch.cuda.empty_cache()
+
+    P_model = spec.P
+    # Gaussians that pass the cull of a view (radii > 0): what the rasterizer actually carries through forward and
+    # backward.  Outside the timed region; summed over the views the timed steps rendered.
+    P_vis = visible(model, pool)
+    p_sum = torch.tensor([float(sum(P_vis[c] for vs in used for c in vs))], dtype=torch.float64, device=dev)
+    if world > 1:
+        dist.all_reduce(p_sum)
+    value = float(p_sum.item()) / elapsed
+
+    out = {
+        "metric": "gaussians_per_sec_grad_step_500k_strands_1080p", "value": round(value, 1), "unit": "Gaussians/s",
+        "n_gpus": world, "steps": K, "warmup": Wm, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "BASELINE configs[2]: %s, %d Gaussians (%s) in the model, %d view(s) per GPU per gradient step "
+                               "at %dx%d, drawn in turn from %d ring cameras per GPU (all ground truth resident): render + 4 "
+                               "stage-1 losses (L1, SSIM, mask, orientation 0.1) + backward%s + Adam" %
+                   (spec.name, P_model, spec.kind, V, spec.W, spec.H, len(pool),
+                    " + gradient sum over %d ranks (backend %s%s)" % (world, backend, " = RCCL" if backend == "nccl" else "")
+                    if world > 1 else ""),
+                   "views_per_gpu": V, "global_views": global_views, "parallelism": "view-dp%d" % world,
+                   "backend": backend, "cameras_per_gpu": len(pool), "settle_steps_before_warmup": n_settle,
+                   "optimizer": ("Adam applied by the step's last k_project_bwd (ghr_adam_fuse): %d of the %d timed + warm-up steps"
+                                 % (fused_steps - n_settle, K + Wm)) if fused_steps
+                   else "separate k_adam_v4 pass",
+                   "P_model": P_model, "P_visible_per_camera": P_vis,
+                   "value_is": "sum over the timed steps' views of the Gaussians that pass the cull / elapsed time"},
+        "grad_steps_per_sec": round(K / elapsed, 3),
+    }
+    if not args.full:  # the headline is all a plain run measures
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything below adds to the same line ------------------------------------------------------------------
     # (a diagnostic only, printed as `repeat_ms_per_step`: the same K steps once more, straight behind the timed ones.  `value`
     # and `ms_per_step` are the FIRST K steps whatever this says; two numbers far apart mean the box stalled the process in one
     # of the two 14-ms windows)
@@ -299,15 +374,6 @@ def main():
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         replicas_identical = bool(torch.equal(lo, hi))
-
-    P_model = spec.P
-    # Gaussians that pass the cull of a view (radii > 0): what the rasterizer actually carries through forward and
-    # backward.  Outside the timed region; summed over the views the timed steps rendered.
-    P_vis = visible(model, pool)
-    p_sum = torch.tensor([float(sum(P_vis[c] for vs in used for c in vs))], dtype=torch.float64, device=dev)
-    if world > 1:
-        dist.all_reduce(p_sum)
-    value = float(p_sum.item()) / elapsed
 
     traffic, traffic_src, traffic_stale = None, None, None
     pmc_file = os.path.join(ROOT, "profiles", "pmc_k_render_bwd.json")
@@ -347,31 +413,14 @@ def main():
                         "the passes); kernel duration from HIP events the library records around the kernel on its launch "
                         "stream, %d solo passes cycling over this rank's %d training cameras" % (n_ev, len(pool))}
 
-    out = {
-        "metric": "gaussians_per_sec_grad_step_500k_strands_1080p", "value": round(value, 1), "unit": "Gaussians/s",
-        "n_gpus": world, "steps": K, "warmup": Wm, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "BASELINE configs[2]: %s, %d Gaussians (%s) in the model, %d view(s) per GPU per gradient step "
-                               "at %dx%d, drawn in turn from %d ring cameras per GPU (all ground truth resident): render + 4 "
-                               "stage-1 losses (L1, SSIM, mask, orientation 0.1) + backward%s + Adam" %
-                   (spec.name, P_model, spec.kind, V, spec.W, spec.H, len(pool),
-                    " + gradient sum over %d ranks (backend %s%s)" % (world, backend, " = RCCL" if backend == "nccl" else "")
-                    if world > 1 else ""),
-                   "views_per_gpu": V, "global_views": global_views, "parallelism": "view-dp%d" % world,
-                   "backend": backend, "cameras_per_gpu": len(pool), "settle_steps_before_warmup": n_settle,
-                   "optimizer": ("Adam applied by the step's last k_project_bwd (ghr_adam_fuse): %d of the %d timed + warm-up steps"
-                                 % (model.optimizer.fused_steps - n_settle, K + Wm)) if getattr(model.optimizer, "fused_steps", 0)
-                   else "separate k_adam_v4 pass",
-                   "P_model": P_model, "P_visible_per_camera": P_vis,
-                   "num_rendered_per_camera": [per_cam[c][0][1] for c in sorted(per_cam)],
-                   "value_is": "sum over the timed steps' views of the Gaussians that pass the cull / elapsed time"},
-        "grad_steps_per_sec": round(K / elapsed, 3),
+    out["config"]["num_rendered_per_camera"] = [per_cam[c][0][1] for c in sorted(per_cam)]
+    out.update({
         "kernels_ms": {"k_render_fwd": round(fwd_avg, 4), "k_render_bwd": round(bwd_avg, 4),
                        "k_render_fwd_hbm_frac": round(bytes_fwd_kernel / (fwd_avg * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
                        if fwd_avg > 0 else None},
         "roofline": roofline,
         "repeat_ms_per_step": round(1e3 * elapsed_rep / K, 4),
-    }
+    })
     if replicas_identical is not None:
         out["replicas_identical"] = replicas_identical
 
@@ -662,6 +711,32 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_ROWS = 1 << 17  # Gaussians sampled by dump_outputs: 61 floats each, 32 MB in all
+DUMP_SEED = 20260
+
+
+def dump_outputs(dirname, model, loss):
+    """What a caller of the timed path holds after its last timed step, as DIR/<name>.npy (float32): ``loss`` (what
+    training_step returned) and the eight parameter tensors of the model after that step's Adam update (main() hands it
+    the model of its bit-reproducible replay of the timed steps).  The parameters
+    are sampled: the same DUMP_ROWS Gaussians of the model, chosen by a CPU generator seeded with DUMP_SEED, in
+    ascending index order (all of them when the model is smaller)."""
+    import numpy as np
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    os.makedirs(dirname, exist_ok=True)
+    params = {"xyz": model._xyz, "features_dc": model._features_dc, "features_rest": model._features_rest,
+              "opacity": model._opacity, "label": model._label, "scaling": model._scaling, "rotation": model._rotation,
+              "orient_conf": model._orient_conf}
+    P = int(model._xyz.shape[0])
+    g = torch.Generator(device="cpu").manual_seed(DUMP_SEED)
+    rows = torch.randperm(P, generator=g)[:DUMP_ROWS].sort().values if P > DUMP_ROWS else torch.arange(P)
+    for name, t in params.items():
+        a = t.detach().index_select(0, rows.to(t.device)).float().cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    np.save(os.path.join(dirname, "loss.npy"), np.asarray(loss.detach().float().cpu().numpy(), dtype=np.float32))
 
 
 def op_only_bench(dev, cfg="cfg2", iters=50, warm=10):  # SURVEY 8(d): 10 warm-up + 50 timed, median and p10 / p90
