@@ -652,9 +652,11 @@ class FusedAdam:
         slice -- 1 / G of the range -- and the updated parameters are ``all_gather_into_tensor``-ed back in place: the
         wire bytes of the all-reduce (a ring all-reduce IS a reduce-scatter followed by an all-gather), 1 / G of the
         optimizer pass per rank (134 -> 17 us at 500k Gaussians on 8 ranks).  Every rank ends the step with the same
-        parameters, bit for bit, as the replicated update gives (each element is updated once, by the same kernel, from
-        the same reduced gradient and the same moments).  The moments of the slices a rank does not own go STALE on
-        it: ``sync_moments()`` all-gathers them, and is called by everything that reads or re-lays them (state_dict,
+        parameters, bit for bit.  They are the replicated update's (each element is updated once, by the same kernel,
+        from the same moments) up to the rounding of the reduced gradient: the reduce-scatter and the all-reduce may add
+        the ranks' contributions to an element in different orders, which changes the last bits of the sum from three
+        ranks on (tests/test_gpu_dist_wide.py); with two ranks both give the same bits.  The moments of the slices a
+        rank does not own go STALE on it: ``sync_moments()`` all-gathers them, and is called by everything that reads or re-lays them (state_dict,
         optimizer surgery, a change of the plan, a replicated ``step()``).  The tail of a range that does not divide by
         G x 256 and the packed SH-band ranges take the all-reduce + replicated update as before (a few KB)."""
         self.resolve_deferred()

@@ -26,13 +26,19 @@ def test_relaunch_command_runs_one_process_per_gpu():
     assert os.path.basename(cmd[cmd.index("--master-port") + 2]) == "bench.py"
 
 
-def test_bench_without_a_launcher_starts_n_ranks():
+def test_bench_without_a_launcher_starts_n_ranks_and_each_reaches_the_device_check():
     import torch
     if torch.cuda.is_available():
         import pytest
         pytest.skip("CPU-side check (on a GPU box the ranks would run the whole benchmark)")
+    # Both ranks fail at the device check.  torch.distributed.run polls its workers every 0.1 s by default and stops the
+    # group (SIGTERM) at the first failure it sees: a rank that was a little slower than the other would be killed before
+    # it printed its line.  Its first poll is put off (PET_MONITOR_INTERVAL, read by the launcher that bench.py starts)
+    # until both have long exited.
+    env = _env()
+    env["PET_MONITOR_INTERVAL"] = "30"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
-                       env=_env(), capture_output=True, text=True, timeout=600, cwd=ROOT)
+                       env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode != 0
     assert "launching -m torch.distributed.run" in r.stderr
     # both ranks reached bench.py's own device check with the world size it asked for

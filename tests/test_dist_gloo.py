@@ -25,24 +25,24 @@ def _setup(views):
     gt = syn.make_model(SPEC)
     with torch.no_grad():
         gt._features_dc.add_(0.2)
-    cams = ring_cameras(VIEWS, SPEC.W, SPEC.H)
+    cams = ring_cameras(views, SPEC.W, SPEC.H)
     make_ground_truth(gt, cams, syn.background())
     model.training_setup(OptimizationParams())
     return model, cams
 
 
-def _worker(rank, world, port, q):
+def _worker(rank, world, port, q, views=VIEWS):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     torch.set_num_threads(1)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     with oracle_rasterizer():
-        model, cams = _setup(VIEWS)
+        model, cams = _setup(views)
         bucket = FlatGradBucket(model.leaf_parameters())
         mine = shard_views(cams, rank, world)
         grads = _capture(model, bucket)
         for it in range(2):
             training_step(model, mine, syn.background(), OptimizationParams(), it + 1, bucket=bucket,
-                          global_views=VIEWS)
+                          global_views=views)
         q.put((rank, param_checksum(model.leaf_parameters()), model._xyz.detach().numpy().copy(), grads[0]))
     dist.barrier()
     dist.destroy_process_group()
@@ -69,29 +69,42 @@ def _free_port():
 
 @pytest.mark.timeout(600)
 def test_two_rank_view_sharding_equals_sequential_accumulation():
+    _check_view_sharding_equals_sequential_accumulation(2, VIEWS)
+
+
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("world,views", [(3, 4), (4, 4), (4, 6)])
+def test_view_sharding_at_3_and_4_ranks_equals_sequential_accumulation(world, views):
+    """The 2-rank check at world 3 and 4, uneven splits included (4 views on 3 ranks: 2, 1, 1; 6 on 4: 2, 2, 1, 1)."""
+    _check_view_sharding_equals_sequential_accumulation(world, views)
+
+
+def _check_view_sharding_equals_sequential_accumulation(world, views):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, q, views)) for r in range(world)]
     for p in procs:
         p.start()
-    res = sorted([q.get(timeout=500) for _ in range(2)])
+    res = sorted([q.get(timeout=500) for _ in range(world)], key=lambda x: x[0])
     for p in procs:
         p.join(60)
         assert p.exitcode == 0
     # replicas bit-identical
-    assert res[0][1] == res[1][1]
-    np.testing.assert_array_equal(res[0][2], res[1][2])
-    # == one process accumulating all 4 views
+    for r in res[1:]:
+        assert res[0][1] == r[1]
+        np.testing.assert_array_equal(res[0][2], r[2])
+    # == one process accumulating all the views
     with oracle_rasterizer():
-        model, cams = _setup(VIEWS)
+        model, cams = _setup(views)
         bucket = FlatGradBucket(model.leaf_parameters())
         grads = _capture(model, bucket)
         for it in range(2):
-            training_step(model, cams, syn.background(), OptimizationParams(), it + 1, bucket=bucket, global_views=VIEWS)
+            training_step(model, cams, syn.background(), OptimizationParams(), it + 1, bucket=bucket, global_views=views)
     # SURVEY 8(e): G-GPU result == 1-GPU sequential accumulation of the same V views, <= 1e-5 on the GRADIENTS
-    # (fp32 reassociation of the 4-view sum: 2 + 2 vs sequential)
-    np.testing.assert_array_equal(res[0][3], res[1][3])
+    # (fp32 reassociation of the V-view sum: per-rank partial sums vs sequential)
+    for r in res[1:]:
+        np.testing.assert_array_equal(res[0][3], r[3])
     scale = np.abs(grads[0]).max()
     assert scale > 0 and np.abs(res[0][3] - grads[0]).max() <= 1e-5 * scale
     ref = model._xyz.detach().numpy()
@@ -213,3 +226,92 @@ def test_lone_state_dict_of_a_sharded_optimizer_raises_instead_of_hanging():
     for r in (0, 1):
         assert np.array_equal(res[r]["m"], want_m) and np.array_equal(res[r]["v"], want_m ** 2)
         assert res[r]["step"] == 3.0 and not res[r]["stale_after"]
+
+
+def _two_range_layout(world):
+    """Two "shard" ranges of different lengths (2 and 3 x G x 256 floats) with replicated stretches around them, as a shard
+    plan leaves them: (n, ((a0, b0), (a1, b1)))"""
+    a0 = 100
+    b0 = a0 + 2 * world * 256
+    a1 = b0 + 37  # (a tail that keeps the all-reduce)
+    b1 = a1 + 3 * world * 256
+    return b1 + 51, ((a0, b0), (a1, b1))
+
+
+def _moments_owned_by(world, rank, n, ranges):
+    """Moments as rank ``rank`` holds them after a sharded step: its own slice of every range current (value 1 + rank +
+    10 x range), the other ranks' slices stale (a value of this rank's own), the replicated stretches current everywhere."""
+    m = torch.full((n,), -3.0)
+    for i, (a, b) in enumerate(ranges):
+        L = (b - a) // world
+        m[a:b] = -100.0 - rank
+        m[a + rank * L: a + (rank + 1) * L] = 1.0 + rank + 10 * i
+    return m
+
+
+def _sync_worker(rank, world, port, q):
+    """The hand-built FusedAdam of _stale_worker at G ranks with two shard ranges of different lengths."""
+    from gaussianhaircut_amd import optim
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    n, ranges = _two_range_layout(world)
+    res = dict(rank=rank)
+    for how in ("sync_moments", "state_dict"):
+        o = object.__new__(optim.FusedAdam)
+        p = torch.nn.Parameter(torch.zeros(n))
+        o.param_groups = [dict(params=[p], lr=1e-3, name="xyz")]
+        o.betas, o.eps = (0.9, 0.999), 1e-15
+        o.flat_param = p.data
+        o.exp_avg = _moments_owned_by(world, rank, n, ranges)
+        o.exp_avg_sq = o.exp_avg * 2
+        o.state_dev = torch.zeros(18, dtype=torch.int32)
+        o.state_dev[0] = 3
+        o._moment_shards = (world, ranges)
+        stale = o.moments_stale()
+        try:
+            o.state_dict()
+            lone = "returned"
+        except optim.StaleMomentsError:
+            lone = "raised"
+        dist.barrier()
+        if how == "sync_moments":
+            o.sync_moments()
+            sd = o.state_dict()
+        else:
+            sd = o.state_dict(collective=True)
+        res[how] = dict(stale=stale, lone=lone, stale_after=o.moments_stale(), m=sd["state"][0]["exp_avg"].numpy().copy(),
+                        v=sd["state"][0]["exp_avg_sq"].numpy().copy(), step=float(sd["state"][0]["step"]))
+    q.put(res)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("world", [3, 4])
+def test_sync_moments_of_two_shard_ranges_at_3_and_4_ranks(world):
+    """sync_moments() and state_dict(collective=True) over G > 2 ranks: every rank ends with every owner's slice of every
+    sharded range (slices of (b - a) / G floats at a + r (b - a) / G), the replicated stretches left alone."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_sync_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = sorted([q.get(timeout=200) for _ in range(world)], key=lambda d: d["rank"])
+    for p in procs:
+        p.join(60)
+        assert p.exitcode == 0
+    n, ranges = _two_range_layout(world)
+    want = torch.full((n,), -3.0)
+    for i, (a, b) in enumerate(ranges):
+        L = (b - a) // world
+        for r in range(world):
+            want[a + r * L: a + (r + 1) * L] = 1.0 + r + 10 * i
+    want = want.numpy()
+    for r in res:
+        for how in ("sync_moments", "state_dict"):
+            d = r[how]
+            assert d["stale"] and d["lone"] == "raised" and not d["stale_after"], (r["rank"], how)
+            np.testing.assert_array_equal(d["m"], want, err_msg="rank %d, %s" % (r["rank"], how))
+            np.testing.assert_array_equal(d["v"], want * 2, err_msg="rank %d, %s" % (r["rank"], how))
+            assert d["step"] == 3.0

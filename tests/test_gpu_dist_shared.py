@@ -8,63 +8,24 @@ the driver's test boxes have one GPU; RCCL itself is exercised by the driver's m
   * a non-finite gradient on ONE rank skips the step on BOTH (parameters, moments and step counter untouched).
 """
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
 import torch.multiprocessing as mp
 
+from tests.dist_helpers import capture_reduced_gradient as _capture_reduced_gradient
+from tests.dist_helpers import collect as _collect
+from tests.dist_helpers import free_port as _free_port
+from tests.dist_helpers import scene
+
 pytestmark = pytest.mark.gpu
 
 VIEWS, STEPS = 8, 3
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _scene(dev, sh_degree):
-    from gaussianhaircut_amd.scene.cameras import ring_cameras
-    from gaussianhaircut_amd.scene.gaussian_model import OptimizationParams
-    from gaussianhaircut_amd.trainer import make_ground_truth
-    from gaussianhaircut_amd.utils import synthetic as syn
-    spec = syn.CONFIGS["tiny_strands"]
-    opt = OptimizationParams()
-    opt.lambda_dorient = 0.1
-    model, gt = syn.make_model(spec, dev), syn.make_model(spec, dev)
-    model.active_sh_degree = sh_degree
-    with torch.no_grad():
-        gt._features_dc.add_(0.25)
-        gt._xyz.add_(0.003 * torch.randn(gt._xyz.shape, generator=torch.Generator().manual_seed(5)).to(dev))
-    cams = ring_cameras(VIEWS, spec.W, spec.H, device=dev)
-    bg = syn.background(dev)
-    make_ground_truth(gt, cams, bg)
-    model.training_setup(opt)
-    return model, cams, bg, opt
-
-
-def _capture_reduced_gradient(model, store):
-    """step / step_chunked with the gradient zeroing taken out, so the (reduced) flat gradient can be copied first"""
-    o = model.optimizer
-    orig_c, orig_s = o.step_chunked, o.step
-
-    def chunked(chunks=4, zero_grad=True, reduce=False, shard=None):
-        # (replicated update: with the sharded one a rank only ever holds ITS slices of the reduced gradient)
-        orig_c(chunks=chunks, zero_grad=False, reduce=reduce, shard=False)
-        store.append(o.flat_grad.detach().clone())
-        o.flat_grad.zero_()
-
-    def step(zero_grad=True, nan_scan=True):
-        o.fold_own_views()  # (a multi-view step on one rank keeps its SH gradients as per-view tables until the update)
-        store.append(o.flat_grad.detach().clone())
-        orig_s(zero_grad=zero_grad, nan_scan=nan_scan)
-
-    o.step_chunked, o.step = chunked, step
+    return scene(dev, sh_degree, VIEWS)
 
 
 def _worker(rank, world, port, q, sh_degree, poison_rank, shard=None, factored=True):
@@ -145,24 +106,6 @@ def _run_two_ranks(sh_degree, poison_rank=None, shard=None, factored=True):
         p.join(120)
         assert p.exitcode == 0
     return res
-
-
-def _collect(q, procs, n, timeout=900):
-    """The workers' results; fails as soon as one of them has died (its peers would wait in a collective until the timeout)."""
-    import queue
-    import time
-    out, t0 = [], time.time()
-    while len(out) < n:
-        try:
-            out.append(q.get(timeout=2))
-        except queue.Empty:
-            dead = [p.exitcode for p in procs if p.exitcode not in (None, 0)]
-            if dead or time.time() - t0 > timeout:
-                for p in procs:
-                    if p.is_alive():
-                        p.terminate()
-                raise AssertionError("worker exit codes %s after %.0f s" % ([p.exitcode for p in procs], time.time() - t0))
-    return sorted(out, key=lambda d: d["rank"])
 
 
 @pytest.mark.timeout(1500)
