@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GHR_LIB_PATH") or os.path.join(CSRC, "libghr_hip.so")  # override: kernel experiments
 SOURCES = ["ghr_capi.hip"]
 HEADERS = ["ghr_device.h", "ghr_preprocess.h", "ghr_binning.h", "ghr_render_fwd.h", "ghr_render_bwd.h", "ghr_render_bwd2.h", "ghr_render_bwd3.h",
-           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h"]
+           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-fPIC",
                "-shared"]
 
@@ -141,7 +141,8 @@ EXPORTS = ["ghr_last_error", "ghr_abi_version", "ghr_forward_sizes", "ghr_binnin
            "ghr_forward_stage2", "ghr_backward", "ghr_backward_ex", "ghr_mark_visible", "ghr_ws_inspect", "ghr_set_profile_events", "ghr_set_deterministic", "ghr_selftest_wave", "ghr_selftest_math", "ghr_model_forward_stage1",
            "ghr_model_backward", "ghr_model_forward_segment", "ghr_model_forward_finish", "ghr_render_backward",
            "ghr_model_backward_segment", "ghr_camera_slots", "ghr_camera_grad_fold", "ghr_strand_build", "ghr_strand_build_backward", "ghr_strand_build_backward_ex", "ghr_sh_grad_from_views", "ghr_loss_sums_floats", "ghr_loss_forward", "ghr_loss_gt_stats", "ghr_loss_backward", "ghr_adam_step",
-           "ghr_adam_step_range", "ghr_adam_step_range_to", "ghr_adam_nan_scan", "ghr_adam_relay_rows", "ghr_adam_fused_finish"]
+           "ghr_adam_step_range", "ghr_adam_step_range_to", "ghr_adam_nan_scan", "ghr_adam_relay_rows", "ghr_adam_fused_finish",
+           "ghr_knn_workspace_size", "ghr_knn_keys", "ghr_knn_mean_dist2"]
 
 _lib = None
 
@@ -203,6 +204,9 @@ def lib() -> ctypes.CDLL:
     L.ghr_strand_build.argtypes = [vp, i32, i32, vp, vp, f32, vp, vp, vp]
     L.ghr_strand_build_backward.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
     L.ghr_strand_build_backward_ex.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.ghr_knn_workspace_size.argtypes = [ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]
+    L.ghr_knn_keys.argtypes = [vp, ctypes.c_int64, vp, vp, vp]
+    L.ghr_knn_mean_dist2.argtypes = [vp, ctypes.c_int64, vp, vp, vp, vp]
     L.ghr_ws_inspect.argtypes = [i32, i32, i32, i32, u32, vp, vp, vp, ctypes.POINTER(WsView)]
     for name in EXPORTS:
         fn = getattr(L, name)
@@ -224,6 +228,12 @@ def forward_sizes(P: int, W: int, H: int, mode_b: bool):
     g, i = ctypes.c_size_t(0), ctypes.c_size_t(0)
     check(lib().ghr_forward_sizes(P, W, H, int(mode_b), ctypes.byref(g), ctypes.byref(i)))
     return int(g.value), int(i.value)
+
+
+def knn_workspace_size(P: int) -> int:
+    b = ctypes.c_size_t(0)
+    check(lib().ghr_knn_workspace_size(P, ctypes.byref(b)))
+    return int(b.value)
 
 
 def binning_size(R: int, W: int, H: int) -> int:

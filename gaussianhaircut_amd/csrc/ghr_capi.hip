@@ -15,6 +15,7 @@
 #include "ghr_device.h"
 #include "ghr_adam.h"
 #include "ghr_geom_bwd.h"
+#include "ghr_knn.h"
 #include "ghr_loss.h"
 #include "ghr_preprocess.h"
 #include "ghr_project.h"
@@ -1044,6 +1045,43 @@ int ghr_mark_visible(void* stream, int32_t P, const float* means3D, const float*
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(ghr::k_mark_visible, dim3((P + GHR_BLOCK - 1) / GHR_BLOCK), dim3(GHR_BLOCK), 0, s, P, means3D,
                        viewmatrix, present);
+    return finish(s, 0);
+}
+
+int ghr_knn_workspace_size(int64_t P, size_t* bytes)
+{
+    if (!bytes || P < 0 || P >= ((int64_t)1 << 31)) return fail(GHR_E_INVALID, "ghr_knn_workspace_size: bad args");
+    const size_t nb = ((size_t)P + GHR_KNN_BLOCK - 1) / GHR_KNN_BLOCK, ns = (nb + GHR_KNN_SUPER - 1) / GHR_KNN_SUPER;
+    *bytes = up((size_t)P * sizeof(float4)) + up(nb * 2 * sizeof(float4)) + up(ns * 2 * sizeof(float4)) + ALIGN;
+    return GHR_OK;
+}
+
+int ghr_knn_keys(void* stream, int64_t P, const float* points, const float* bounds_dev, uint64_t* keys)
+{
+    if (P < 0 || P >= ((int64_t)1 << 31)) return fail(GHR_E_INVALID, "ghr_knn_keys: P must be in [0, 2^31)");
+    if (P == 0) return GHR_OK;
+    if (!points || !bounds_dev || !keys) return fail(GHR_E_INVALID, "ghr_knn_keys: NULL buffer");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ghr::k_knn_keys, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, (int)P, points, bounds_dev,
+                       (unsigned long long*)keys);
+    return finish(s, 0);
+}
+
+int ghr_knn_mean_dist2(void* stream, int64_t P, const float* points, const int64_t* order, void* ws, float* out)
+{
+    if (P < 0 || P >= ((int64_t)1 << 31)) return fail(GHR_E_INVALID, "ghr_knn_mean_dist2: P must be in [0, 2^31)");
+    if (P == 0) return GHR_OK;
+    if (!points || !order || !ws || !out) return fail(GHR_E_INVALID, "ghr_knn_mean_dist2: NULL buffer");
+    const size_t nb = ((size_t)P + GHR_KNN_BLOCK - 1) / GHR_KNN_BLOCK, ns = (nb + GHR_KNN_SUPER - 1) / GHR_KNN_SUPER;
+    char* base = align_base(ws);
+    float4* sorted = (float4*)base;
+    float4* bbox = (float4*)(base + up((size_t)P * sizeof(float4)));
+    float4* sbox = (float4*)((char*)bbox + up(nb * 2 * sizeof(float4)));
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ghr::k_knn_boxes, dim3((unsigned)ns), dim3(64 * GHR_KNN_WAVES), 0, s, (int)P, points,
+                       (const long long*)order, sorted, bbox, sbox);
+    hipLaunchKernelGGL(ghr::k_knn_search, dim3((unsigned)((nb + GHR_KNN_WAVES - 1) / GHR_KNN_WAVES)),
+                       dim3(64 * GHR_KNN_WAVES), 0, s, (int)P, sorted, bbox, sbox, out);
     return finish(s, 0);
 }
 

@@ -10,20 +10,22 @@ contract so ``render()`` and a reference-shaped training loop work unchanged):
 * ``get_mean_2d`` / ``get_depths`` / ``get_direction_2d``  :317-393
 * ``training_setup`` / ``update_learning_rate``           :426-456
 
+* ``create_from_pcd``                                        :399-424   (initial scales from ``simple_knn.distCUDA2``)
 * densify / clone / split / prune / reset_opacity           :560-741   (``scene/densification.py``)
 * ``save_ply`` / ``load_ply``                                :458-579   (``scene/ply_io.py``)
 
-Device-agnostic (the reference hard-codes ``device="cuda"``, :235,:384).  Out of scope: ``create_from_pcd`` (needs
-simple_knn).  ``capture``/``restore`` are symmetric (the reference's restore() unpacks 14 of capture()'s 15 fields,
-:65-100).
+Device-agnostic (the reference hard-codes ``device="cuda"``, :235,:384).  ``capture``/``restore`` are symmetric (the
+reference's restore() unpacks 14 of capture()'s 15 fields, :65-100).
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from ..utils.general_utils import build_rotation, get_expon_lr_func, inverse_sigmoid, strip_symmetric
+from ..utils.sh_utils import RGB2SH
 from .densification import DensificationMixin
 from .ply_io import PlyMixin
 
@@ -79,6 +81,33 @@ class GaussianModel(DensificationMixin, PlyMixin):
                                 else torch.zeros(P, 1, device=dev))
         self.max_radii2D = torch.zeros(P, device=dev)
         return self
+
+    def create_from_points(self, xyz, rgb, dist2, spatial_lr_scale: float):
+        """What the reference's ``create_from_pcd`` builds (gaussian_model.py:399-424) from tensors on any device: xyz [P, 3],
+        rgb [P, 3] in [0, 1], dist2 [P] (``distCUDA2(xyz)``).  SH DC = RGB2SH(rgb), the rest 0; log scales
+        log(sqrt(max(dist2, 1e-7))) on all three axes; identity rotations; opacity 0.1, label 0.5 (as logits); orientation
+        confidence log 0."""
+        P = xyz.shape[0]
+        dev = xyz.device
+        xyz = xyz.float()
+        features = torch.zeros((P, (self.max_sh_degree + 1) ** 2, 3), dtype=torch.float32, device=dev)
+        features[:, 0, :] = RGB2SH(rgb.float())
+        scales = torch.log(torch.sqrt(torch.clamp_min(dist2.float(), 0.0000001)))[..., None].repeat(1, 3)
+        rots = torch.zeros((P, 4), dtype=torch.float32, device=dev)
+        rots[:, 0] = 1
+        opacities = inverse_sigmoid(0.1 * torch.ones((P, 1), dtype=torch.float32, device=dev))
+        labels = inverse_sigmoid(0.5 * torch.ones((P, 1), dtype=torch.float32, device=dev))
+        return self.create_from_tensors(xyz, features, scales, rots, opacities, labels,
+                                        torch.zeros((P, 1), dtype=torch.float32, device=dev), spatial_lr_scale)
+
+    def create_from_pcd(self, pcd, spatial_lr_scale: float, device="cuda"):
+        """The reference's entry point (gaussian_model.py:399-424): a ``BasicPointCloud`` (``scene.ply_io.fetch_ply``) ->
+        the model on ``device``, with the exact 3-NN scales of ``simple_knn.distCUDA2`` (HIP; no CPU path)."""
+        from ..simple_knn import distCUDA2
+        xyz = torch.tensor(np.asarray(pcd.points)).float().to(device)
+        rgb = torch.tensor(np.asarray(pcd.colors)).float().to(device)
+        print("Number of points at initialisation : ", xyz.shape[0])
+        return self.create_from_points(xyz, rgb, distCUDA2(xyz), spatial_lr_scale)
 
     def capture(self, collective: bool = False):
         """The reference's checkpoint tuple (src/scene/gaussian_model.py:84-99).  Under data parallelism with the sharded

@@ -72,6 +72,17 @@ def read_ply_vertices(path: str):
     return [n for n, _ in props], data
 
 
+def fetch_ply(path: str):
+    """A COLMAP-style ``points3D.ply`` as a ``BasicPointCloud`` (reference ``fetchPly``, src/scene/dataset_readers.py:119-125):
+    positions and normals as stored (float32), colours the uchar ``red`` / ``green`` / ``blue`` over 255.0 (float64)."""
+    from ..utils.graphics_utils import BasicPointCloud
+    _, v = read_ply_vertices(path)
+    positions = np.vstack([v['x'], v['y'], v['z']]).T
+    colors = np.vstack([v['red'], v['green'], v['blue']]).T / 255.0
+    normals = np.vstack([v['nx'], v['ny'], v['nz']]).T
+    return BasicPointCloud(points=positions, colors=colors, normals=normals)
+
+
 class PlyMixin:
     def construct_list_of_attributes(self, remove_label=False):
         """gaussian_model.py:458-477."""

@@ -2,9 +2,18 @@
 from __future__ import annotations
 
 import math
+from typing import NamedTuple
 
 import numpy as np
 import torch
+
+
+class BasicPointCloud(NamedTuple):
+    """A point cloud as the reference's dataset readers return it (graphics_utils.py:17-20): points [N, 3] float32,
+    colors [N, 3] in [0, 1], normals [N, 3]."""
+    points: np.ndarray
+    colors: np.ndarray
+    normals: np.ndarray
 
 
 def getWorld2View2(R, t, translate=np.array([.0, .0, .0]), scale=1.0):

@@ -166,3 +166,29 @@ def grad_image(spec: WorkloadSpec, seed: int, device="cpu", C: int = 10) -> torc
     """dL/dout ~ N(0,1)/N (SURVEY.md 8(d) cfg 2)."""
     g = torch.Generator().manual_seed(seed)
     return (_randn(g, C, spec.H, spec.W) / (spec.H * spec.W)).to(device)
+
+
+def colmap_like_cloud(P: int, seed: int, outlier_frac: float = 0.01, n_duplicates: int = 0):
+    """A seeded stand-in for a COLMAP ``points3D`` cloud of a head: ``P`` points, most of them noisy samples of an ellipsoid
+    shell of about head size (semi-axes 0.09, 0.12, 0.11) with uneven density (a few dense patches over a sparse
+    background), ``outlier_frac`` of them far outliers spread over a box ~100x the head, and the last ``n_duplicates``
+    exact copies of earlier points (COLMAP writes duplicates).  Returns (xyz [P, 3] float32, rgb [P, 3] uint8)."""
+    g = torch.Generator().manual_seed(seed)
+    n_out = int(round(P * outlier_frac))
+    n_dup = min(n_duplicates, max(P - 1, 0))
+    n_shell = P - n_out - n_dup
+    # uneven density: half of the shell points gather around 8 patch centres, the rest cover the shell
+    d = F.normalize(_randn(g, n_shell, 3), dim=-1)
+    n_patch = n_shell // 2
+    centres = F.normalize(_randn(g, 8, 3), dim=-1)
+    pick = torch.randint(0, 8, (n_patch,), generator=g)
+    d[:n_patch] = F.normalize(centres[pick] + 0.15 * _randn(g, n_patch, 3), dim=-1)
+    axes = torch.tensor([0.09, 0.12, 0.11])
+    shell = d * axes * (1 + 0.01 * _randn(g, n_shell, 1)) + 0.002 * _randn(g, n_shell, 3)
+    outliers = (_rand(g, n_out, 3) * 2 - 1) * 12.0
+    xyz = torch.cat((shell, outliers))
+    if n_dup:
+        xyz = torch.cat((xyz, xyz[torch.randint(0, xyz.shape[0], (n_dup,), generator=g)]))
+    xyz = xyz[torch.randperm(P, generator=g)]  # COLMAP's order says nothing about position
+    rgb = (_rand(g, P, 3) * 255).round().to(torch.uint8)
+    return xyz.contiguous(), rgb

@@ -486,6 +486,22 @@ int ghr_selftest_wave(void* stream, const float* in, float* out);
  * error in ulp -- the margin of 2e-5 the parity tests give a discrete decision (tests/helpers.py) rests on those bounds. */
 int ghr_selftest_math(void* stream, int32_t n, const float* in, float* out);
 
+/* ---- exact 3-nearest-neighbour mean squared distance (simple_knn's distCUDA2; src/scene/gaussian_model.py:409) ------------
+ * Added without an ABI_VERSION bump: three new functions, no existing struct or signature changed.
+ * out[i] = ((b0 + b1) + b2) / 3 with b0 <= b1 <= b2 the three smallest d = (dx*dx + dy*dy) + dz*dz (fp32, no contraction;
+ * dx = p[j].x - p[i].x) over every j != i (by index), where a slot starts at FLT_MAX and takes d only when d is strictly
+ * smaller: +inf for P = 1, 2.  Bit-identical for any schedule and any input permutation.  Sequence: ghr_knn_keys; the caller
+ * sorts the keys (ascending, any stable or unstable sort) into `order`, the int64 permutation of 0 .. P-1 that sorts them;
+ * ghr_knn_mean_dist2.  P < 2^31; P == 0 does nothing.  Finite coordinates are the caller's check: other bits give
+ * unspecified values but no access outside the buffers (an `order` entry outside [0, P) is read as 0). */
+/* bytes of the workspace ghr_knn_mean_dist2 needs for P points (256-byte aligned base) */
+int ghr_knn_workspace_size(int64_t P, size_t* bytes);
+/* points [P,3] f32; bounds_dev [6] f32 = min x, y, z, max x, y, z of the points (device); keys [P] u64 (63-bit Morton codes,
+ * sortable as int64).  Keys only steer the search's speed, never its result. */
+int ghr_knn_keys(void* stream, int64_t P, const float* points, const float* bounds_dev, uint64_t* keys);
+/* order [P] int64 (device); ws: ghr_knn_workspace_size(P) bytes; out [P] f32 (device). */
+int ghr_knn_mean_dist2(void* stream, int64_t P, const float* points, const int64_t* order, void* ws, float* out);
+
 /* Introspection for tests (device pointers into the workspaces; layout is otherwise private). */
 typedef struct ghr_ws_view {
     const float* rec;          /* [P][16]: x, y, conic a, b, c, opacity, features[10] */
