@@ -19,6 +19,12 @@ from ..diff_gaussian_rasterization import _ImgLease, _on_device, LAST_STATS, NUM
 RECYCLE_IMG_WS = os.environ.get("GHR_RECYCLE_IMG_WS", "1") != "0"  # see _ImgLease
 
 
+def _grads_in_place(leaves) -> bool:
+    """These leaves are Parameters whose .grad aliases a contiguous fp32 buffer of the same shape (an optimizer's flat buffer)."""
+    return all(isinstance(t, torch.nn.Parameter) and t.requires_grad and t.grad is not None and t.grad.is_contiguous()
+               and t.grad.dtype == torch.float32 and t.grad.shape == t.shape for t in leaves)
+
+
 def _model_args(P, W, H, sh_degree, K, tensors, view, proj, campos, bg, scale_modifier, tanfovx, tanfovy, eps, debug,
                 fov_dev=None):
     m = _lib.ModelArgs()
@@ -112,9 +118,7 @@ class _RenderModelFused(torch.autograd.Function):
         dev, P = xyz.device, xyz.shape[0]
         f32 = dict(dtype=torch.float32, device=dev)
         sink = cfg.get("grad_sink")
-        direct = sink is not None and P > 0 and all(
-            isinstance(t, torch.nn.Parameter) and t.requires_grad and t.grad is not None and t.grad.is_contiguous()
-            and t.grad.dtype == torch.float32 and t.grad.shape == t.shape for t in ctx.leaves)
+        direct = sink is not None and P > 0 and _grads_in_place(ctx.leaves)
         with _on_device(dev):
             d_m2d = torch.empty((P, 3), **f32)
             if direct:
@@ -149,20 +153,19 @@ class _RenderModelFused(torch.autograd.Function):
                 # the stage-1 loop's per-iteration statistics (train_gaussians.py:161-165) ride along in k_project_bwd
                 m.dens_grad_accum, m.dens_denom, m.dens_max_radii2D = [_ptr(t) for t in dens]
                 m.dens_img_ws = _ptr(img)  # (a view whose capacity guess overflowed leaves the statistics alone: it is redone)
-            fuse = direct and P > 0 and getattr(sink, "_fuse_step", None) is not None
+            adam_fuse = sink.fused_step_args() if direct and P > 0 else None
+            fuse = adam_fuse is not None
             if fuse:
                 # a step whose LAST backward carries the optimizer update (optim.FusedAdam.begin_fused_step): every view checks
                 # its instance count on the device (an overflowed speculative pass must raise the step's flag) ...
                 m.dens_img_ws, m.overflow_raises_flag = _ptr(img), 1
                 if cfg.get("fuse_adam"):  # ... and this one IS the last
-                    m.adam_fuse = ctypes.addressof(sink._fuse_step["args"])
+                    m.adam_fuse = adam_fuse
             # the step's first gradients into a buffer that is known to hold zeros are assigned, not added (optim.py)
-            acc = 1
-            if P > 0 and direct and sink.take_known_zero():
-                acc = 0
+            acc = 0 if P > 0 and direct and sink.take_known_zero() else 1
             p_fdc, p_frest = _ptr(d_fdc), _ptr(d_frest)
             fold_first = False
-            if P > 0 and direct and getattr(sink, "_views", None) is not None:
+            if P > 0 and direct and sink.views_open:
                 if fuse and cfg.get("fuse_adam"):
                     # the view that carries the optimizer update needs the step's whole SH gradient in the flat buffer: the
                     # earlier views' tables are folded into it first (one launch), this view's terms are added by the kernel
@@ -244,7 +247,6 @@ def render_model_fused(cam, pc, bg_color, scaling_modifier, debug, defer_count=F
     num_rendered: int, or a PendingCount with ``defer_count``).  ``densify_stats``: the backward pass of this view also
     updates the model's ``xyz_gradient_accum`` / ``denom`` / ``max_radii2D`` (the reference's per-iteration bookkeeping,
     train_gaussians.py:161-165), inside k_project_bwd."""
-    import math
     xyz = pc.get_xyz
     P = xyz.shape[0]
     # "zero tensor used to make pytorch return gradients of the 2D (screen-space) means" of the original 3DGS;
@@ -432,17 +434,14 @@ class _RenderHairFused(torch.autograd.Function):
                 # (a buffer left undefined by step(zero_grad="defer") is only made whole by a backward that assigns EVERY
                 # group; this one assigns two of four: the others would be accumulated into garbage)
                 sink.resolve_deferred()
-            leaves_ok = (sink is not None and n_hair > 0 and all(
-                isinstance(t, torch.nn.Parameter) and t.requires_grad and t.grad is not None and t.grad.is_contiguous() and
-                t.grad.dtype == torch.float32 and t.grad.shape == t.shape for t in ctx.sh_leaves))
+            leaves_ok = sink is not None and n_hair > 0 and _grads_in_place(ctx.sh_leaves)
             # The optimizer update of the SH features inside this backward (round 6: trainer.strand_training_step opened a fused
             # step, FusedAdam.begin_fused_step): the kernel reads their moments and writes parameters + moments of the other
             # buffer set instead of 192 B of gradient per Gaussian for a separate Adam pass to read back; the caller finishes the
             # step once autograd has delivered the strand directions' gradients (finish_fused_step_with_late_groups)
-            fuse = bool(leaves_ok and cfg.get("fuse_adam") and getattr(sink, "_fuse_step", None) is not None)
-            direct = (not fuse and sink is not None and n_hair > 0 and all(
-                isinstance(t, torch.nn.Parameter) and t.requires_grad and t.grad is not None and t.grad.is_contiguous() and
-                t.grad.dtype == torch.float32 and t.grad.shape == t.shape for t in ctx.sh_leaves) and sink.take_known_zero())
+            adam_fuse = sink.fused_step_args() if leaves_ok and cfg.get("fuse_adam") else None
+            fuse = adam_fuse is not None
+            direct = not fuse and leaves_ok and sink.take_known_zero()
             if direct:
                 d_fdc, d_frest = ctx.sh_leaves[0].grad, ctx.sh_leaves[1].grad
             elif fuse:
@@ -463,7 +462,7 @@ class _RenderHairFused(torch.autograd.Function):
                 # buffer: the saved copies are the leaves' own storage -- .detach().float().contiguous() of a contiguous fp32
                 # parameter is a view)
                 m_hair.features_dc, m_hair.features_rest = _ptr(ctx.sh_leaves[0].data), _ptr(ctx.sh_leaves[1].data)
-                m_hair.adam_fuse = ctypes.addressof(sink._fuse_step["args"])
+                m_hair.adam_fuse = adam_fuse
             want_cam = any(ctx.needs_input_grad[8:13])
             cam_partial = None
             if want_cam and rows > 0:
@@ -488,12 +487,10 @@ class _RenderHairFused(torch.autograd.Function):
                                                         _ptr(d_dir), 0, sink.nan_flag_ptr() if (direct or fuse) else None,
                                                         scratch.shape[0], _ptr(binb), ctx.cap))
             d_cam = _camera_grads(cam_partial, ctx.cam_meta, ctx.needs_input_grad[8:13], dev, ctx.fov) if want_cam else (None,) * 5
-        if fuse:
+        if fuse or direct:
             sink.note_direct_backward()
-            sink.note_fused_update()
-            return (d_xyz, d_sc, d_rot, d_dir, d_conf, None, None, d_m2d) + d_cam + (None, None)
-        if direct:
-            sink.note_direct_backward()
+            if fuse:
+                sink.note_fused_update()
             return (d_xyz, d_sc, d_rot, d_dir, d_conf, None, None, d_m2d) + d_cam + (None, None)
         return (d_xyz, d_sc, d_rot, d_dir, d_conf, d_fdc, d_frest, d_m2d) + d_cam + (None, None)
 
@@ -517,7 +514,6 @@ def head_segment(pc):
 
 def render_hair_fused(cam, pc, pc_hair, bg_color, scaling_modifier, debug, fuse_adam=False):
     """Returns (renders[10,H,W], radii[n_head + n_hair], screenspace_points leaf)."""
-    import math
     head = head_segment(pc)
     xyz = pc_hair.get_xyz
     n = head["xyz"].shape[0] + xyz.shape[0]

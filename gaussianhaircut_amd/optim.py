@@ -51,7 +51,6 @@ def collectives_on() -> bool:
     """More than one rank -- or one rank with GHR_FORCE_COLLECTIVES=1, which sends every collective of the N > 1 path
     through the backend anyway (tests/test_gpu_dist_shared.py: ONE rank on backend "nccl" = RCCL runs the init, the
     async work handles and the stream ordering rules that gloo does not have, on a one-GPU box)."""
-    import os
     return dist.is_available() and dist.is_initialized() and (
         dist.get_world_size() > 1 or os.environ.get("GHR_FORCE_COLLECTIVES") == "1")
 
@@ -60,7 +59,42 @@ _TORCH_ADAM_DEFAULTS = dict(weight_decay=0, amsgrad=False, maximize=False, forea
                             differentiable=False, fused=None, decoupled_weight_decay=False)
 
 
+def _group_ranges(param_groups):
+    """(group index, group, offset, numel) of every group inside the flat buffers -- THE walk over the layout, taken from the
+    groups as they are when it is called (densification replaces their parameters; nothing here is cached)."""
+    off = 0
+    for gi, g in enumerate(param_groups):
+        k = sum(p.numel() for p in g["params"])
+        yield gi, g, off, k
+        off += k
+
+
 class FusedAdam:
+    # ---- every field of the optimizer's host state and its value outside a step; __init__ adds the buffers.  (Class-level, so
+    # that an object made by hand around a few attributes -- the plan tests -- reads the same defaults.)
+    concurrent = False         # set by the trainer while a step's views run on several streams
+    _direct_backwards = 0      # fused backwards that stored into flat_grad since the last update (note_direct_backward)
+    _acc_event = None          # the last accumulating kernel of a concurrent step (accumulate_begin / accumulate_end)
+    # groups whose parameters were replaced since the last step (densification / opacity reset): the reference's new
+    # nn.Parameters have grad None, so its optimizer.step() passes them by on that iteration -- no moment decay, no
+    # update, no step count (train_gaussians.py:158-181).  Bit g = group g; consumed by the next step.  Contract: the
+    # surgery sits between backward() and step() like the reference's densification block; a backward AFTER the
+    # surgery through the fused renderer clears the marks again (note_direct_backward), a caller that fills .grad any
+    # other way before stepping calls ``cancel_skip()``.
+    _skip_next = 0
+    _zero_version = None       # flat_grad's version counter when it was last known to hold zeros (_mark_zero)
+    _deferred = None           # the same counter while the contents are UNDEFINED: see step(zero_grad="defer")
+    # number of higher-order SH coefficients (rows of f_rest's middle axis) that can carry a gradient, i.e.
+    # (active_sh_degree + 1)^2 - 1; None = all.  Set by trainer.training_step; only shortens the all-reduce.
+    active_rest_coeffs = None
+    _views = None              # the view slots while they are open (begin_factored_views .. end_factored_views)
+    _views_buf = None          # their buffer, kept from step to step
+    _views_keep = None         # the gathered tables, until the stream has consumed them
+    _fuse = None               # {"p", "m", "v": the second set; "flags": two int32 words; "parity"; "clean"}
+    _fuse_step = None          # while a fused step is in progress: its ghr_adam_fuse + what keeps the pointers alive
+    fused_steps = 0            # updates that were carried by a step's last backward
+    _moment_shards = None      # (G, ((a, b), ...)): the "shard" ranges whose moments are current only on their owner's slice
+
     def __init__(self, param_groups: List[Dict], betas=(0.9, 0.999), eps: float = 1e-15, nan_guard: bool = True,
                  direct_grads: bool = True):
         self.param_groups = [dict(g) for g in param_groups]
@@ -68,9 +102,6 @@ class FusedAdam:
         # direct_grads: the fused renderer's backward adds its parameter gradients straight into ``flat_grad`` and keeps
         # the NaN flag up to date, instead of returning 8 tensors for autograd to accumulate (8 kernels, 3x the traffic)
         self.direct_grads = direct_grads
-        self._direct_backwards = 0
-        self.concurrent = False  # set by the trainer while a step's views run on several streams
-        self._acc_event = None
         params = [p for g in self.param_groups for p in g["params"]]
         assert params and all(p.is_cuda and p.dtype == torch.float32 for p in params), \
             "FusedAdam needs fp32 parameters on a ROCm device (use torch.optim.Adam elsewhere)"
@@ -82,29 +113,19 @@ class FusedAdam:
         self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
         # {step, nan flag, steps each group has sat out}
         self.state_dev = torch.zeros(_lib.ADAM_STATE, dtype=torch.int32, device=dev)
-        # groups whose parameters were replaced since the last step (densification / opacity reset): the reference's new
-        # nn.Parameters have grad None, so its optimizer.step() passes them by on that iteration -- no moment decay, no
-        # update, no step count (train_gaussians.py:158-181).  Bit g = group g; consumed by the next step.  Contract: the
-        # surgery sits between backward() and step() like the reference's densification block; a backward AFTER the
-        # surgery through the fused renderer clears the marks again (note_direct_backward), a caller that fills .grad any
-        # other way before stepping calls ``cancel_skip()``.
-        self._skip_next = 0
-        self._deferred = None  # see step(zero_grad="defer")
-        # number of higher-order SH coefficients (rows of f_rest's middle axis) that can carry a gradient, i.e.
-        # (active_sh_degree + 1)^2 - 1; None = all.  Set by trainer.training_step; only shortens the all-reduce.
-        self.active_rest_coeffs = None
-        off, ends = 0, []
-        for g in self.param_groups:
-            for p in g["params"]:
-                k = p.numel()
-                self.flat_param[off:off + k].copy_(p.data.reshape(-1))
-                p.data = self.flat_param[off:off + k].view(p.shape)
-                p.grad = self.flat_grad[off:off + k].view(p.shape)
-                off += k
-            ends.append(off)
-        self._ends = (ctypes.c_int64 * len(ends))(*ends)
-        self.params = params
+        for _, a, b, p in self._param_ranges():
+            self.flat_param[a:b].copy_(p.data.reshape(-1))
+            p.data = self.flat_param[a:b].view(p.shape)
+            p.grad = self.flat_grad[a:b].view(p.shape)
+        self._set_ends()
         self._mark_zero()
+
+    def _set_ends(self):  # the groups' end offsets as the kernels take them: a host array, remade whenever the layout changes
+        ends = [off + k for _, _, off, k in _group_ranges(self.param_groups)]
+        self._ends = (ctypes.c_int64 * len(ends))(*ends)
+
+    def _lr_array(self):
+        return (ctypes.c_float * len(self.param_groups))(*[float(g["lr"]) for g in self.param_groups])
 
     # ---- "the gradient buffer is all zero" as a checked fact.  The first direct backward of a step may then ASSIGN
     # instead of accumulate (k_project_bwd skips reading 244 B of zeros per Gaussian).  The library's own kernels are
@@ -114,14 +135,16 @@ class FusedAdam:
         self._zero_version = self.flat_grad._version
         self._deferred = None
 
+    def _holds_nothing(self) -> bool:
+        """The gradient buffer holds nothing yet: zeros nobody has touched, or undefined after a deferred step."""
+        return self._deferred is not None or (self._zero_version is not None and
+                                              self.flat_grad._version == self._zero_version and self._direct_backwards == 0)
+
     def take_known_zero(self) -> bool:
-        if getattr(self, "_deferred", None) is not None:  # see step(zero_grad="defer"): this backward defines them
+        ok = self._holds_nothing()
+        if self._deferred is not None:  # see step(zero_grad="defer"): this backward defines them
             self._check_untouched()
             self._deferred = None
-            self._zero_version = None
-            return True
-        ok = (self._zero_version is not None and self.flat_grad._version == self._zero_version and
-              self._direct_backwards == 0)
         self._zero_version = None
         return ok
 
@@ -140,10 +163,9 @@ class FusedAdam:
 
     def resolve_deferred(self):
         """Make the gradient buffer hold zeros if the last step left it undefined (no-op otherwise)."""
-        if getattr(self, "_deferred", None) is not None:
+        if self._deferred is not None:
             self._check_untouched()
-            self.flat_grad.zero_()
-            self._mark_zero()
+            self.zero_grad()
 
     # ---- gradient-bucket interface (same as parallel.FlatGradBucket)
     @property
@@ -155,10 +177,18 @@ class FusedAdam:
         return self.flat_grad
 
     def zero(self):
-        self.flat_grad.zero_()
-        self._mark_zero()
+        self.zero_grad()
         if self._views is not None:
             self._views["next"] = 0  # (a step that is recomputed: its views fill the slots again)
+
+    def abort_step(self, fused_update_undone: bool = False):
+        """Drop what the backwards of the current step left here (trainer.training_step redoes a step whose capacity guess
+        overflowed).  ``fused_update_undone``: end_fused_step counted an update that the raised flag then undid on the device."""
+        self._direct_backwards = 0
+        self.zero()
+        self.state_dev[1:2].zero_()  # (the garbage views raised the NaN flag)
+        self._acc_event = None
+        self.fused_steps -= int(fused_update_undone)
 
     def zero_grad(self, set_to_none: bool = False):
         self.flat_grad.zero_()  # grads alias the flat buffer: never dropped
@@ -188,33 +218,33 @@ class FusedAdam:
         return torch.isnan(self.flat_grad).any()
 
     # ---- optimizer-state surgery for densification (reference: gaussian_model.py:581-658 on torch.optim.Adam state)
-    def _rebuild(self, new_params: List[torch.Tensor], new_m: List[torch.Tensor], new_v: List[torch.Tensor]):
+    def relay_tensors(self, new_params: List[torch.Tensor], new_m: List[torch.Tensor], new_v: List[torch.Tensor]):
         """Re-lay the flat buffers for a new set of per-group tensors (one parameter per group, the reference's layout).
         Returns {group name: new nn.Parameter}.  The step counter is kept (Adam's ``step`` is per optimizer here, as it
         effectively is in the reference where every group is stepped every iteration)."""
         dev = self.flat_param.device
-        n = sum(t.numel() for t in new_params)
-        flat_p = torch.empty(n, dtype=torch.float32, device=dev)
-        flat_m = torch.empty(n, dtype=torch.float32, device=dev)
-        flat_v = torch.empty(n, dtype=torch.float32, device=dev)
-        self.flat_grad = torch.zeros(n, dtype=torch.float32, device=dev)
-        off, ends, out, params = 0, [], {}, []
-        for g, t, m, v in zip(self.param_groups, new_params, new_m, new_v):
-            k = t.numel()
-            flat_p[off:off + k].copy_(t.reshape(-1))
-            flat_m[off:off + k].copy_(m.reshape(-1))
-            flat_v[off:off + k].copy_(v.reshape(-1))
-            p = torch.nn.Parameter(flat_p[off:off + k].view(t.shape), requires_grad=True)
-            p.grad = self.flat_grad[off:off + k].view(t.shape)
+        sizes = [t.numel() for t in new_params]
+        flat_p, flat_m, flat_v = (torch.empty(sum(sizes), dtype=torch.float32, device=dev) for _ in range(3))
+        for dp, dm, dv, t, m, v in zip(flat_p.split(sizes), flat_m.split(sizes), flat_v.split(sizes), new_params, new_m, new_v):
+            dp.copy_(t.reshape(-1))
+            dm.copy_(m.reshape(-1))
+            dv.copy_(v.reshape(-1))
+        return self._adopt(flat_p, flat_m, flat_v, [t.shape for t in new_params])
+
+    def _adopt(self, flat_p, flat_m, flat_v, shapes):
+        """The end of every re-lay: the new flat buffers become the optimizer's, every group gets ONE new nn.Parameter of its
+        shape in ``shapes`` whose .grad lies in a new, zeroed gradient buffer.  Returns {group name: new nn.Parameter}."""
+        sizes = [torch.Size(shp).numel() for shp in shapes]
+        self.flat_param, self.exp_avg, self.exp_avg_sq = flat_p, flat_m, flat_v
+        self.flat_grad = torch.zeros(flat_p.numel(), dtype=torch.float32, device=flat_p.device)
+        out = {}
+        for g, shp, data, grad in zip(self.param_groups, shapes, flat_p.split(sizes), self.flat_grad.split(sizes)):
+            p = torch.nn.Parameter(data.view(shp), requires_grad=True)
+            p.grad = grad.view(shp)
             g["params"] = [p]
             out[g["name"]] = p
-            params.append(p)
-            off += k
-            ends.append(off)
-        self.flat_param, self.exp_avg, self.exp_avg_sq = flat_p, flat_m, flat_v
         self._fuse = None  # (the second buffer set of the fused update is re-made at the new size when next needed)
-        self._ends = (ctypes.c_int64 * len(ends))(*ends)
-        self.params = params
+        self._set_ends()
         self._mark_zero()
         self._direct_backwards = 0
         self._skip_next = (1 << len(self.param_groups)) - 1  # every parameter is new: the coming step is a no-op
@@ -224,7 +254,7 @@ class FusedAdam:
         """One re-lay of the flat buffers for a densification event (``ghr_adam_relay_rows``): new row r of every group is old
         row ``take[r]`` -- or row ``child[r]`` of ``overrides[group name]`` where ``child[r] >= 0`` -- with zeroed moments
         where ``fresh[r]``.  Every group must hold one parameter of shape [P, ...].  Returns {group name: new nn.Parameter}
-        like ``_rebuild`` (whose ~80 index_select / where / copy launches this replaces)."""
+        like ``relay_tensors`` (whose ~80 index_select / where / copy launches this replaces)."""
         self.sync_moments()
         dev = self.flat_param.device
         P_old = int(self.param_groups[0]["params"][0].shape[0])
@@ -236,9 +266,7 @@ class FusedAdam:
             widths.append(int(p.numel() // max(P_old, 1)) if P_old else int(torch.Size(p.shape[1:]).numel()))
             shapes.append(tuple(p.shape[1:]))
         n = sum(widths) * P_new
-        flat_p = torch.empty(n, dtype=torch.float32, device=dev)
-        flat_m = torch.empty(n, dtype=torch.float32, device=dev)
-        flat_v = torch.empty(n, dtype=torch.float32, device=dev)
+        flat_p, flat_m, flat_v = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
         take = take.to(torch.int64).contiguous()
         fresh = fresh.to(torch.uint8).contiguous()
         child = None if child is None else child.to(torch.int64).contiguous()
@@ -257,41 +285,20 @@ class FusedAdam:
                 _stream(), len(widths), w_arr, P_old, P_new, _ptr(take), _ptr(fresh), None if child is None else _ptr(child),
                 ctypes.cast(ovr, ctypes.c_void_p) if keep else None, _ptr(self.flat_param), _ptr(self.exp_avg),
                 _ptr(self.exp_avg_sq), _ptr(flat_p), _ptr(flat_m), _ptr(flat_v)))
-        self.flat_grad = torch.zeros(n, dtype=torch.float32, device=dev)
-        off, ends, out, params = 0, [], {}, []
-        for g, w, shp in zip(self.param_groups, widths, shapes):
-            k = w * P_new
-            p = torch.nn.Parameter(flat_p[off:off + k].view((P_new,) + shp), requires_grad=True)
-            p.grad = self.flat_grad[off:off + k].view((P_new,) + shp)
-            g["params"] = [p]
-            out[g["name"]] = p
-            params.append(p)
-            off += k
-            ends.append(off)
-        self.flat_param, self.exp_avg, self.exp_avg_sq = flat_p, flat_m, flat_v
-        self._fuse = None
-        self._ends = (ctypes.c_int64 * len(ends))(*ends)
-        self.params = params
-        self._mark_zero()
-        self._direct_backwards = 0
-        self._skip_next = (1 << len(self.param_groups)) - 1  # every parameter is new: the coming step is a no-op
-        return out
+        return self._adopt(flat_p, flat_m, flat_v, [(P_new,) + shp for shp in shapes])
 
     def _group_views(self):
         self.sync_moments()  # (sharded optimizer: the moments of the other ranks' slices are stale here)
-        off = 0
-        for g in self.param_groups:
+        for _, g, off, k in _group_ranges(self.param_groups):
             p = g["params"][0]
-            k = p.numel()
             yield g, p, self.exp_avg[off:off + k].view(p.shape), self.exp_avg_sq[off:off + k].view(p.shape)
-            off += k
 
     def prune(self, keep_mask: torch.Tensor):
         """``_prune_optimizer`` (gaussian_model.py:596-612): keep the rows where ``keep_mask`` is True, moments included."""
         ps, ms, vs = [], [], []
         for _, p, m, v in self._group_views():
             ps.append(p.data[keep_mask]); ms.append(m[keep_mask]); vs.append(v[keep_mask])
-        return self._rebuild(ps, ms, vs)
+        return self.relay_tensors(ps, ms, vs)
 
     def extend(self, tensors_dict: Dict[str, torch.Tensor]):
         """``cat_tensors_to_optimizer`` (gaussian_model.py:634-654): append rows with zero moments."""
@@ -301,7 +308,7 @@ class FusedAdam:
             ps.append(torch.cat((p.data, ext), dim=0))
             ms.append(torch.cat((m, torch.zeros_like(ext)), dim=0))
             vs.append(torch.cat((v, torch.zeros_like(ext)), dim=0))
-        return self._rebuild(ps, ms, vs)
+        return self.relay_tensors(ps, ms, vs)
 
     def replace(self, tensor: torch.Tensor, name: str):
         """``replace_tensor_to_optimizer`` (gaussian_model.py:581-594): new values, zeroed moments, for one group."""
@@ -323,38 +330,28 @@ class FusedAdam:
     # ---- direct-gradient sink used by gaussian_renderer.fused
     def nan_flag_ptr(self):
         if self._fuse_step is not None:  # a step whose last backward carries the update: its own flag word (see below)
-            return self.fused_flag_ptr()
+            return ctypes.c_void_p(int(self._fuse_step["args"].flag))
         return ctypes.c_void_p(self.state_dev.data_ptr() + 4)
 
     def scan_groups_for_nan(self, names):
         """Raise the device NaN flag if a gradient of the named groups holds a NaN (``ghr_adam_nan_scan``): the part of the
         scanning guard a step needs whose other groups' gradients were stored by the fused backward (which keeps the flag)."""
-        off = 0
         with _on_device(self.flat_param.device):
-            for g in self.param_groups:
-                k = sum(p.numel() for p in g["params"])
+            for _, g, off, k in _group_ranges(self.param_groups):
                 if g["name"] in names and k:
                     _lib.check(_lib.lib().ghr_adam_nan_scan(_stream(), ctypes.c_void_p(self.flat_grad.data_ptr() + 4 * off), k,
                                                             _ptr(self.state_dev)))
-                off += k
 
     # ---- SH gradients in factored form (data-parallel steps; include/ghr.h ABI 19, csrc/ghr_project.h k_sh_grad_from_views).
     # A view's gradient of the 48 SH floats of a Gaussian is basis(dir) (x) d_rgb: the fused backward of every view of the step
     # leaves its d_rgb table [P,3] (+ the camera centre) in a slot here instead of adding 192 B per Gaussian into the flat
     # gradient; step_chunked all-gathers the slots of all ranks and every rank rebuilds the f_dc / f_rest gradients from them.
-    _views = None
-
-    def _group_range(self, name):
-        off = 0
-        for g in self.param_groups:
-            k = sum(p.numel() for p in g["params"])
-            if g["name"] == name:
-                return off, off + k, g["params"][0]
-            off += k
-        return None
+    def _named_ranges(self):
+        """{group name: (start, end, first parameter)} of the groups inside the flat buffers."""
+        return {g["name"]: (off, off + k, g["params"][0]) for _, g, off, k in _group_ranges(self.param_groups)}
 
     def can_factor_views(self) -> bool:
-        dc, rest, xyz = self._group_range("f_dc"), self._group_range("f_rest"), self._group_range("xyz")
+        dc, rest, xyz = map(self._named_ranges().get, ("f_dc", "f_rest", "xyz"))
         return (dc is not None and rest is not None and xyz is not None and dc[1] == rest[0] and rest[2].dim() == 3 and
                 rest[2].shape[1] in (3, 8, 15) and xyz[2].dim() == 2 and xyz[2].shape[1] == 3 and
                 dc[2].shape[0] == xyz[2].shape[0] == rest[2].shape[0])
@@ -365,9 +362,9 @@ class FusedAdam:
         are gathered and the f_dc / f_rest ranges are NOT reduced.  ``gather=False`` (a rank's own business: the collectives do
         not change): only this rank's views are folded, before the usual sums -- what is saved is the read-modify-write of
         192 B per Gaussian in every view's backward (a rank with at least two views: 12 B per view + one 192-B store)."""
-        P = int(self._group_range("xyz")[2].shape[0])
+        P = int(self._named_ranges()["xyz"][2].shape[0])
         stride = -(-(3 * P + 4) // 4) * 4  # [d_rgb P x 3 | camera centre 3 | the rank's non-finite mark | pad]: 16-B multiples
-        v = getattr(self, "_views_buf", None)
+        v = self._views_buf
         if v is None or v["buf"].shape != (n_local, stride) or v["buf"].device != self.flat_param.device:
             v = dict(buf=torch.zeros((n_local, stride), dtype=torch.float32, device=self.flat_param.device), P=P,
                      stride=stride, gathered=None)
@@ -375,16 +372,17 @@ class FusedAdam:
         v["next"] = 0
         v["gather"] = bool(gather)
         v["deg"] = None if sh_degree is None else int(sh_degree)  # the active SH degree of the step's backwards
-        # whether the SH ranges of the gradient buffer hold nothing yet (zeros, or undefined after a deferred step): the fold then
-        # ASSIGNS; otherwise (somebody else's gradients are in there) it adds -- the question take_known_zero() answers for the
-        # step's first backward, asked here without consuming the answer
-        v["assign"] = bool(getattr(self, "_deferred", None) is not None or
-                           (self._zero_version is not None and self.flat_grad._version == self._zero_version and
-                            self._direct_backwards == 0))
+        # the fold ASSIGNS the SH ranges of a gradient buffer that holds nothing yet; otherwise (somebody else's gradients are in
+        # there) it adds -- what take_known_zero() answers for the step's first backward, asked here without consuming the answer
+        v["assign"] = self._holds_nothing()
         self._views = v
 
     def end_factored_views(self):
         self._views = None
+
+    @property
+    def views_open(self) -> bool:  # a direct backward is to leave its SH gradients in a view slot (next_view_slot)
+        return self._views is not None
 
     def next_view_slot(self, campos: torch.Tensor):
         """Device pointer of the next free d_rgb table of the step; the view's camera centre goes behind it."""
@@ -411,7 +409,7 @@ class FusedAdam:
         P, stride = v["P"], v["stride"]
         n_views = gathered.numel() // stride
         rows = gathered.view(n_views, stride)
-        (a_dc, _, _), (a_rest, _, p_rest), (a_xyz, _, _) = self._group_range("f_dc"), self._group_range("f_rest"), self._group_range("xyz")
+        (a_dc, _, _), (a_rest, _, p_rest), (a_xyz, _, _) = map(self._named_ranges().get, ("f_dc", "f_rest", "xyz"))
         K = int(p_rest.shape[1]) + 1
         act = K - 1 if self.active_rest_coeffs is None else int(self.active_rest_coeffs)
         deg = v["deg"] if v.get("deg") is not None else {0: 0, 3: 1, 8: 2, 15: 3}[act]
@@ -451,10 +449,6 @@ class FusedAdam:
     # kernel that follows undoes the update (copies the old values over the new) when the step's flag is up; a view whose
     # speculative forward pass overflowed its capacity raises the same flag, so the trainer's recovery finds the parameters
     # untouched.  The gradient buffer is left as it was (contents undefined, as with zero_grad="defer").
-    _fuse = None           # {"p", "m", "v": the second set; "flags": two int32 words; "parity"; "clean"}
-    _fuse_step = None      # while a fused step is in progress: its ghr_adam_fuse + what keeps the pointers alive
-    fused_steps = 0
-
     def can_fuse_step(self) -> bool:
         return (self.nan_guard and self.direct_grads and self._skip_next == 0 and self._moment_shards is None and
                 not collectives_on() and len(self.param_groups) <= 16 and
@@ -472,7 +466,7 @@ class FusedAdam:
         if not f["clean"]:
             f["flags"].zero_()  # (the previous step was not a fused one: its finish kernel did not clear this step's word)
             f["clean"] = True
-        lrs = (ctypes.c_float * len(self.param_groups))(*[float(g["lr"]) for g in self.param_groups])
+        lrs = self._lr_array()
         a = _lib.AdamFuse()
         a.n = n
         a.p_in, a.m_in, a.v_in = _ptr(self.flat_param), _ptr(self.exp_avg), _ptr(self.exp_avg_sq)
@@ -487,12 +481,21 @@ class FusedAdam:
         self._fuse_step = dict(args=a, lrs=lrs, done=False)
         return a
 
-    def fused_flag_ptr(self):
-        return ctypes.c_void_p(int(self._fuse_step["args"].flag))
+    def fused_step_args(self):
+        """Address of the ``ghr_adam_fuse`` of the fused step in progress; None outside begin_fused_step .. end_fused_step."""
+        return None if self._fuse_step is None else ctypes.addressof(self._fuse_step["args"])
 
     def note_fused_update(self):
         """The step's last backward has launched the update (gaussian_renderer.fused)."""
         self._fuse_step["done"] = True
+
+    @property
+    def fused_update_launched(self) -> bool:
+        return self._fuse_step is not None and self._fuse_step["done"]
+
+    @property
+    def direct_backwards(self) -> int:  # (read-only: note_direct_backward counts)
+        return self._direct_backwards
 
     def finish_fused_step_with_late_groups(self, late_groups):
         """A step whose update was carried by a STRAND segment's backward (``ghr_adam_fuse`` with mode 1: only the SH features are
@@ -503,13 +506,7 @@ class FusedAdam:
         a = st["args"]
         lib = _lib.lib()
         n = self.flat_param.numel()
-        ranges, off = [], 0
-        for g in self.param_groups:
-            k = sum(p.numel() for p in g["params"])
-            if g["name"] in late_groups and k:
-                ranges.append((off, k))
-            off += k
-        par = f["parity"]
+        ranges = [(off, k) for _, g, off, k in _group_ranges(self.param_groups) if g["name"] in late_groups and k]
         with _on_device(self.flat_param.device):
             # (ABI 20: one out-of-place pass per range -- in set -> out set, skipped under the step's own flag word, which the
             # pass raises itself for a NaN among the range's gradients: the `in` set is intact, the finish kernel undoes -- where
@@ -542,22 +539,15 @@ class FusedAdam:
         views = f.setdefault("views", {})
         mine = views.get(self.flat_param.data_ptr())
         if mine is None:
-            mine, off = [], 0
-            for g in self.param_groups:
-                p = g["params"][0]
-                k = p.numel()
-                mine.append(self.flat_param[off:off + k].view(p.shape))
-                off += k
-            views[self.flat_param.data_ptr()] = mine
+            mine = views[self.flat_param.data_ptr()] = [self.flat_param[off:off + k].view(g["params"][0].shape)
+                                                        for _, g, off, k in _group_ranges(self.param_groups)]
         for g, v in zip(self.param_groups, mine):
             g["params"][0].data = v
         self._direct_backwards = 0
         self._acc_event = None
         self._skip_next = 0
-        if grads_zero:
-            self._after_step(True, False)
-        else:
-            self._after_step(False, True)  # the gradient buffer was neither zeroed nor written: undefined until the next backward
+        # (not grads_zero: the gradient buffer was neither zeroed nor written -- undefined until the next backward)
+        self._after_step(grads_zero, not grads_zero)
         self.fused_steps += 1
         return True
 
@@ -571,21 +561,26 @@ class FusedAdam:
             raise RuntimeError("FusedAdam.step: view slots opened for a gathered exchange need step_chunked(reduce=True)")
         self.fold_own_views()  # (before resolve_deferred: the fold defines the SH ranges of a deferred buffer)
         self.resolve_deferred()  # (a step without a backward since a deferred one: its gradients are zeros)
-        zero_grad, defer = _zero_grad_mode(zero_grad)
-        self._sync_before_replicated_update()
+        zero_grad, defer, lrs, guard, skip = self._begin_update(zero_grad, nan_scan or self._direct_backwards == 0)
+        self.sync_moments()  # (a replicated update: no-op unless the last one was sharded)
         if self._fuse is not None:
             self._fuse["clean"] = False
-        lrs = (ctypes.c_float * len(self.param_groups))(*[float(g["lr"]) for g in self.param_groups])
-        guard = 0 if not self.nan_guard else (1 if nan_scan or self._direct_backwards == 0 else 2)
-        self._direct_backwards = 0
-        self._acc_event = None
-        skip, self._skip_next = self._skip_next, 0
         with _on_device(self.flat_param.device):
             _lib.check(_lib.lib().ghr_adam_step(_stream(), self.flat_param.numel(), _ptr(self.flat_param),
                                                 _ptr(self.flat_grad), _ptr(self.exp_avg), _ptr(self.exp_avg_sq),
                                                 _ptr(self.state_dev), len(self.param_groups), self._ends, lrs,
                                                 self.betas[0], self.betas[1], self.eps, guard, int(zero_grad), skip))
         self._after_step(zero_grad, defer)
+
+    def _begin_update(self, zero_grad, scan: bool):
+        """How step() and step_chunked() start: consumes the step's host-side marks; returns (zero, defer) of ``zero_grad``, the
+        learning rates, the kernels' guard mode (0 off, 1 scanning, 2 the direct backwards' flag) and the groups that sit out."""
+        zero, defer = _zero_grad_mode(zero_grad)
+        guard = 0 if not self.nan_guard else (1 if scan else 2)
+        self._direct_backwards = 0
+        self._acc_event = None
+        skip, self._skip_next = self._skip_next, 0
+        return zero, defer, self._lr_array(), guard, skip
 
     def _after_step(self, zero_grad, defer):
         if defer:
@@ -613,17 +608,18 @@ class FusedAdam:
         n = self.flat_param.numel()
         per = -(-n // max(int(chunks), 1))
         per = -(-per // 1024) * 1024  # whole 4-KiB pieces
-        plan, run_a, off = [], 0, 0
+        plan, run_a = [], 0
         act = self.active_rest_coeffs
+        # (getattr: the plan is also built for stand-ins that only carry flat_param / param_groups / active_rest_coeffs)
+        gather = (getattr(self, "_views", None) or {}).get("gather")
 
         def flush(b):
             for a in range(run_a, b, per):
                 plan.append((a, min(a + per, b), "sum"))
 
-        for g in self.param_groups:
+        for _, g, off, k in _group_ranges(self.param_groups):
             p = g["params"][0]
-            k = p.numel()
-            if (getattr(self, "_views", None) or {}).get("gather") and g.get("name") in ("f_dc", "f_rest"):
+            if gather and g.get("name") in ("f_dc", "f_rest"):
                 # not reduced: rebuilt on every rank from the gathered per-view factors (begin_factored_views)
                 flush(off)
                 plan.append((off, off + k, "views"))
@@ -632,7 +628,6 @@ class FusedAdam:
                 flush(off)
                 plan.append((off, off + k, "none" if act <= 0 else ("rest", p.shape[0], p.shape[1], int(act))))
                 run_a = off + k
-            off += k
         flush(n)
         return [x for x in plan if x[1] > x[0]]
 
@@ -660,12 +655,7 @@ class FusedAdam:
         optimizer surgery, a change of the plan, a replicated ``step()``).  The tail of a range that does not divide by
         G x 256 and the packed SH-band ranges take the all-reduce + replicated update as before (a few KB)."""
         self.resolve_deferred()
-        zero_grad, defer = _zero_grad_mode(zero_grad)
-        lrs = (ctypes.c_float * len(self.param_groups))(*[float(g["lr"]) for g in self.param_groups])
-        guard = 2 if self.nan_guard else 0
-        self._direct_backwards = 0
-        self._acc_event = None
-        skip, self._skip_next = self._skip_next, 0
+        zero_grad, defer, lrs, guard, skip = self._begin_update(zero_grad, False)
         comm = reduce and collectives_on()
         if shard and not (zero_grad or defer):
             # the in-place reduce-scatter leaves a rank's OWN slice holding the global sum and the other slices local
@@ -687,7 +677,7 @@ class FusedAdam:
                 self.sync_moments()  # the slices change owners (SH degree went up): bring every rank up to date first
             self._moment_shards = key
         else:
-            self._sync_before_replicated_update()
+            self.sync_moments()
         works = [None] * len(plan)
         views_work, gathered = None, None
         if self._views is not None:
@@ -764,8 +754,6 @@ class FusedAdam:
         self._after_step(zero_grad, defer)  # (every range of the plan has been through the kernel)
 
     # ---- ZeRO-1 helpers (step_chunked(shard=True))
-    _moment_shards = None  # (G, ((a, b), ...)): the "shard" ranges whose moments are current only on their owner's slice
-
     @staticmethod
     def _shard_plan(plan, G):
         """Splits every "sum" range of a reduce plan into a part whose length divides by G x 256 (how = "shard": slice r of
@@ -807,16 +795,11 @@ class FusedAdam:
             for buf in (self.exp_avg, self.exp_avg_sq):
                 dist.all_gather_into_tensor(buf[a:b], buf[a + r * L: a + (r + 1) * L])
 
-    def _sync_before_replicated_update(self):
-        if self._moment_shards is not None:
-            self.sync_moments()
-
     def _param_ranges(self):
-        off = 0
-        for gi, g in enumerate(self.param_groups):
+        for gi, g, a, _ in _group_ranges(self.param_groups):
             for p in g["params"]:
-                yield gi, off, off + p.numel(), p
-                off += p.numel()
+                yield gi, a, a + p.numel(), p
+                a += p.numel()
 
     def state_dict(self, collective: bool = False):
         """``torch.optim.Adam.state_dict()`` layout (what the reference's ``GaussianModel.capture`` stores,

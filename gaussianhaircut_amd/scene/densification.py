@@ -230,7 +230,7 @@ class DensificationMixin:
             mn = torch.where(fresh.view(bshape), zero, m.index_select(0, take))
             vn = torch.where(fresh.view(bshape), zero, v.index_select(0, take))
             ps.append(pn); ms.append(mn); vs.append(vn)
-        t = o._rebuild(ps, ms, vs)
+        t = o.relay_tensors(ps, ms, vs)
         self._assign(t)
         self._orient_conf = t["orient_conf"] if "orient_conf" in t else torch.zeros_like(self._label)
         P = self.get_xyz.shape[0]

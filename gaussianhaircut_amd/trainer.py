@@ -2,14 +2,16 @@
 densification / logging / GUI -- lr schedule, render, losses, backward, [grad all-reduce], NaN guard, Adam."""
 from __future__ import annotations
 
-import functools
+import contextlib
 import os
 from types import SimpleNamespace
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 
-from .gaussian_renderer import render
+from . import optim as _optim
+from .gaussian_renderer import _use_fused, _use_fused_hair, render, render_hair
+from .optim import FusedAdam, collectives_on
 from .parallel import FlatGradBucket
 from .utils.loss_utils import l1_loss, or_loss, ssim
 
@@ -91,6 +93,7 @@ def view_loss(render_pkg, cam, opt, fused=None, scale: float = 1.0):
 
 
 _SIDE_STREAMS = {}
+_NO_STREAM = contextlib.nullcontext()  # (a view on the current stream)
 
 
 def _side_streams(device, n):
@@ -107,36 +110,30 @@ def _views_forward_backward(gaussians, cams, background, opt, V, pipe, n_streams
     pipes = [pipe] * len(cams)
     if last_pipe is not None and cams:
         pipes[-1] = last_pipe
+    main, side = None, ()
     if n_streams > 1:
         main = torch.cuda.current_stream(background.device)
         side = _side_streams(background.device, n_streams)
         for s in side:
             s.wait_stream(main)  # parameters as the previous optimizer step left them
         sink.concurrent = True
-        try:
-            for i, cam in enumerate(cams):
-                with torch.cuda.stream(side[i % n_streams]):
-                    pipe = pipes[i]
-                    pkg = render(cam, gaussians, pipe, background)
-                    loss = view_loss(pkg, cam, opt, scale=1.0 / V)
-                    loss.backward(gradient=_one_like(loss))
-                    _generic_densify_stats(gaussians, pkg, pipe)
-                    ld = loss.detach()
+    try:
+        for i, (cam, pipe) in enumerate(zip(cams, pipes)):
+            with torch.cuda.stream(side[i % n_streams]) if side else _NO_STREAM:
+                pkg = render(cam, gaussians, pipe, background)
+                loss = view_loss(pkg, cam, opt, scale=1.0 / V)
+                loss.backward(gradient=_one_like(loss))
+                _generic_densify_stats(gaussians, pkg, pipe)
+                ld = loss.detach()
+                if side:
                     ld.record_stream(main)
-                    losses.append(ld)
-                    counts.append(getattr(pkg, "count", None))
-        finally:
+                losses.append(ld)
+                counts.append(getattr(pkg, "count", None))
+    finally:
+        if side:
             sink.concurrent = False
             for s in side:
                 main.wait_stream(s)
-    else:
-        for cam, pipe in zip(cams, pipes):
-            pkg = render(cam, gaussians, pipe, background)
-            loss = view_loss(pkg, cam, opt, scale=1.0 / V)
-            loss.backward(gradient=_one_like(loss))
-            _generic_densify_stats(gaussians, pkg, pipe)
-            losses.append(loss.detach())
-            counts.append(getattr(pkg, "count", None))
     return losses, counts
 
 
@@ -150,7 +147,172 @@ def _generic_densify_stats(gaussians, pkg, pipe):
         gaussians.add_densification_stats(pkg["viewspace_points"], vis)
 
 
-def _training_step(gaussians, cams: List, background, opt, iteration: int, bucket: Optional[FlatGradBucket] = None,
+class _StepPlan(NamedTuple):
+    """What one training_step is going to do (_plan_step): decided once, before anything is opened on the optimizer."""
+    V: int                       # every view's loss is scaled 1 / V
+    sink: Optional[FusedAdam]    # the optimizer, where the fused backward may store its gradients itself
+    fused_sink: bool             # ... and this step's configuration lets it
+    all_direct: bool             # every view of this rank goes through that direct backward
+    n_streams: int               # HIP streams the views alternate on (0: the current one)
+    defer: bool                  # no view waits for its instance count
+    fuse: bool                   # the last backward is to carry the update -- if the optimizer agrees (_open_step)
+    factored: Optional[str]      # SH gradients as per-view tables: None, "gathered" over the ranks, or this rank's "own" fold
+    slots: int                   # view slots per rank of the gathered form
+    run_pipe: SimpleNamespace    # the pipe of the views; last_pipe: of the view that carries the update
+    last_pipe: Optional[SimpleNamespace]
+
+
+def _fused_adam(gaussians) -> Optional[FusedAdam]:
+    o = getattr(gaussians, "optimizer", None)
+    return o if isinstance(o, FusedAdam) else None
+
+
+def _plan_step(gaussians, cams, background, bucket, global_views, pipe, streams, defer_counts, densify_stats, fuse_adam,
+               views_per_rank) -> _StepPlan:
+    """The decisions of a step and nothing else: no call that changes the optimizer."""
+    # the loss of a view is scaled 1 / V: with more than one rank V defaults to the GLOBAL number of views (the
+    # all-reduce sums the ranks' gradients), assuming every rank holds len(cams) of them
+    V = global_views or len(cams) * _world_size()
+    sink = _fused_adam(gaussians)
+    if sink is not None and sink.direct_grads:
+        # the direct backward needs every leaf of the fused renderer inside the optimizer (e.g. train_orient_conf = False
+        # leaves _orient_conf out): otherwise autograd accumulates and the scanning guard applies -- a property of the
+        # configuration, identical on every rank
+        leaves = (gaussians._xyz, gaussians._scaling, gaussians._rotation, gaussians._opacity, gaussians._label,
+                  gaussians._orient_conf, gaussians._features_dc, gaussians._features_rest)
+        if not all(isinstance(p, torch.nn.Parameter) and p.grad is not None for p in leaves):
+            sink = None
+    fused_sink = (sink is not None and sink.direct_grads and background.is_cuda and not getattr(pipe, "debug", False))
+    n_streams = (2 if streams is None else int(streams)) if fused_sink and len(cams) > 1 else 0
+    # every view of this step goes through the fused renderer's direct backward (render() decides per camera: a camera
+    # whose tensors require grad takes the generic path, whose gradients arrive through autograd)
+    all_direct = bool(fused_sink and cams and all(_use_fused(gaussians, pipe, c) for c in cams))
+    defer = fused_sink and (True if defer_counts is None else bool(defer_counts))
+    run_pipe = pipe
+    if defer or densify_stats:
+        run_pipe = SimpleNamespace(**{**vars(pipe), "defer_count": bool(defer), "densify_stats": bool(densify_stats)})
+    # (the fused update leaves the gradient buffer undefined, like zero_grad="defer": not for callers who switched that off)
+    fuse = (FUSE_ADAM_INTO_BACKWARD and DEFER_GRAD_ZEROING if fuse_adam is None else bool(fuse_adam)) and all_direct and \
+        bool(cams) and not collectives_on() and bucket is None
+    # Data-parallel steps of few views send the SH gradients -- 48 of the 61 floats per Gaussian -- in factored form: every view's
+    # backward leaves its dL/d(rgb) table (12 B per Gaussian) in a slot of the optimizer, the ranks all-gather the slots and each
+    # rebuilds the f_dc / f_rest gradients (optim.FusedAdam.begin_factored_views).  The choice decides the sequence of
+    # collectives: it depends on the configuration and on the GLOBAL number of views only, never on this rank's cameras.
+    slots = int(views_per_rank) if views_per_rank else -(-V // max(_world_size(), 1))
+    factored = None
+    if (collectives_on() and fused_sink and OVERLAP_ALL_REDUCE_WITH_ADAM and bucket is None and _optim.FACTORED_SH_REDUCE and
+            0 < slots * _world_size() <= _optim.FACTORED_SH_MAX_VIEWS and sink.can_factor_views()):
+        factored = "gathered"
+    elif (all_direct and bucket is None and _optim.FACTORED_SH_REDUCE and sink.can_factor_views() and
+          len(cams) >= (3 if fuse else 2) and (not collectives_on() or OVERLAP_ALL_REDUCE_WITH_ADAM)):
+        # one rank, or too many views in all for the gathered form: the rank folds ITS views' tables into the flat gradient
+        # once (before the sums / the update; before the last view's backward when that one carries the update) and every other
+        # view's backward skips the read-modify-write of 192 B of SH gradients per Gaussian (4 views per rank through the
+        # collective branch: 2.74 -> 2.45 ms, profiles/r06k).  A rank's own choice: the sequence of collectives is the plain one.
+        factored = "own"
+    last_pipe = SimpleNamespace(**{**vars(run_pipe), "fuse_adam": True}) if fuse else None
+    return _StepPlan(V, sink, fused_sink, all_direct, n_streams, defer, fuse, factored, slots, run_pipe, last_pipe)
+
+
+def _open_step(plan: _StepPlan, gaussians, cams) -> bool:
+    """Opens the planned step on the optimizer, in this order.  Returns whether the last backward carries the update."""
+    sink, o = plan.sink, _fused_adam(gaussians)
+    if o is not None and not plan.all_direct:
+        # the previous step may have left the gradient buffer undefined (zero_grad="defer" below): only a fused backward
+        # redefines it -- a rank without views, or the generic / autograd path, needs the zeros the eager step leaves
+        o.resolve_deferred()
+    if sink is not None:
+        sink.end_factored_views()  # (a step that died between its backwards and its update)
+    if plan.factored == "gathered":
+        if len(cams) > plan.slots:
+            raise RuntimeError("training_step: %d views on this rank, %d view slots per rank (%d global views on %d ranks): "
+                               "pass views_per_rank = the largest number of views any rank holds, on every rank" %
+                               (len(cams), plan.slots, plan.V, _world_size()))
+        sink.begin_factored_views(plan.slots, sh_degree=int(gaussians.active_sh_degree))
+    elif plan.factored == "own":
+        sink.begin_factored_views(len(cams), gather=False, sh_degree=int(gaussians.active_sh_degree))
+    fuse = plan.fuse
+    if fuse:
+        sink.cancel_skip()  # (as in _update: every backward of this step runs after any earlier surgery)
+        fuse = sink.can_fuse_step()
+    if fuse:
+        sink.begin_fused_step()
+    return fuse
+
+
+def _redo_overflowed_step(plan: _StepPlan, gaussians, cams, background, opt, pipe, densify_stats, overflow, fused_done):
+    """A guessed capacity was too small: that view's image, loss and gradients are garbage (memory-safe garbage).
+    Drops everything this step accumulated and redoes it with blocking, exactly sized forwards."""
+    plan.sink.abort_step(fused_update_undone=fused_done)  # (the overflowed views raised the step's flag)
+    # (densify_stats: an overflowed view's backward pass left the statistics alone -- k_project_bwd checks the count on the
+    # device -- but the step's OTHER views have been counted, and ALL views are recomputed below: theirs would be counted twice)
+    if densify_stats and len(cams) > 1 and not all(overflow):
+        raise RuntimeError("training_step(densify_stats=True): a capacity guess overflowed in a multi-view step; the "
+                           "statistics of its other views cannot be rolled back -- use defer_counts=False for the first "
+                           "step after the scene has grown")
+    redo_pipe = SimpleNamespace(**{**vars(pipe), "densify_stats": True}) if densify_stats else pipe
+    return _views_forward_backward(gaussians, cams, background, opt, plan.V, redo_pipe, 0, plan.sink)[0]
+
+
+def _update(plan: _StepPlan, gaussians, cams, bucket):
+    """The step's end when no backward carried the update: [gradient collectives], NaN guard, Adam."""
+    o = _fused_adam(gaussians)
+    if o is not None:
+        # Every backward of this step ran AFTER any earlier optimizer surgery (densification / opacity reset between two
+        # calls), so all groups hold fresh gradients: the "parameters replaced since the last backward" marks never apply
+        # here, whichever path produced the gradients (generic pipe, autograd accumulation, a rank without views).  They
+        # only matter for a hand-written loop that runs backward -> surgery -> step (the reference's order), which calls
+        # optimizer.step() itself.  Unconditional, hence identical on every rank.
+        o.cancel_skip()
+        # SH bands above the active degree carry exactly-zero gradients on every rank: not part of the all-reduce
+        o.active_rest_coeffs = (int(gaussians.active_sh_degree) + 1) ** 2 - 1
+        # grads already live in the optimizer's flat buffer; NaN guard + Adam + grad zeroing are one HIP pass
+        # every view's gradients went through the fused renderer's direct backward (which keeps the NaN flag) and no
+        # other rank contributes: the guard needs no scan over the gradients
+        direct_local = o.direct_backwards == len(cams)
+        # On the fused path the next training_step's first backward ASSIGNS the whole gradient buffer, so the Adam pass
+        # need not zero it (an eighth of its traffic): FusedAdam.step(zero_grad="defer").  Anything else that touches the
+        # buffer first either gets the zeros (resolve_deferred) or fails loudly (optim.py).
+        zg = "defer" if (plan.all_direct and direct_local and DEFER_GRAD_ZEROING) else True
+        # The choice below must be the same on every rank (it decides the sequence of collectives): it only depends on
+        # the configuration (`fused_sink`), and a rank whose gradients did not all come through the direct backward
+        # fails loudly instead of silently taking the other branch.
+        if collectives_on() and plan.fused_sink and OVERLAP_ALL_REDUCE_WITH_ADAM:
+            if not direct_local:
+                raise RuntimeError("training_step: %d of %d views went through the fused backward on this rank" %
+                                   (o.direct_backwards, len(cams)))
+            # all-reduce in chunks, each chunk's Adam update as soon as its sum is there (FusedAdam.step_chunked)
+            o.step_chunked(chunks=4, zero_grad=zg, reduce=True)
+        else:
+            o.all_reduce()
+            o.step(zero_grad=zg, nan_scan=not (direct_local and not collectives_on()))
+        return
+    if bucket is not None:
+        bucket.all_reduce()
+        bad = bucket.has_nan()
+    else:
+        bad = torch.stack([p.grad.isnan().any() for p in gaussians.leaf_parameters() if p.grad is not None]).any()
+    # train_gaussians.py:174-181: a NaN anywhere skips the update -- the reference drops the gradients
+    # (zero_grad(set_to_none=True)), so optimizer.step() touches nothing: no moment decay, no step count.
+    # One host decision per step, like the reference's `if torch.isnan(...)` (the torch.optim.Adam path is not the measured
+    # one; round 2's clone-everything-and-restore variant tripled the optimizer traffic and still synchronised on Adam's
+    # CPU-resident step counters).
+    if bool(bad):
+        print('NaN during backprop was found, skipping iteration...')
+        if bucket is not None:
+            # the gradients alias the bucket and cannot be dropped to None: a step over zeroed gradients would still decay
+            # the moments and move the parameters by lr m / sqrt(v) -- skip the whole step, as the reference's does in effect
+            bucket.zero()
+            return
+        gaussians.optimizer.zero_grad(set_to_none=True)
+    gaussians.optimizer.step()
+    if bucket is not None:
+        bucket.zero()
+    else:
+        gaussians.optimizer.zero_grad(set_to_none=True)
+
+
+def training_step(gaussians, cams: List, background, opt, iteration: int, bucket: Optional[FlatGradBucket] = None,
                   global_views: Optional[int] = None, pipe=PIPE, streams: Optional[int] = None,
                   defer_counts: Optional[bool] = None, densify_stats: bool = False, fuse_adam: Optional[bool] = None,
                   views_per_rank: Optional[int] = None):
@@ -183,169 +345,31 @@ def _training_step(gaussians, cams: List, background, opt, iteration: int, bucke
     ``optim.FACTORED_SH_MAX_VIEWS`` view slots in all send the SH gradients as per-view dL/d(rgb) tables (12 B per Gaussian and
     view, all-gathered; ``FusedAdam.begin_factored_views``) instead of summing 192 B per Gaussian: every rank opens that many
     slots, and a rank with more views than slots fails loudly before any collective."""
-    from .optim import FusedAdam
-    gaussians.update_learning_rate(iteration)
-    # the loss of a view is scaled 1 / V: with more than one rank V defaults to the GLOBAL number of views (the
-    # all-reduce sums the ranks' gradients), assuming every rank holds len(cams) of them
-    V = global_views or len(cams) * _world_size()
-    sink = gaussians.optimizer if isinstance(getattr(gaussians, "optimizer", None), FusedAdam) else None
-    if sink is not None and sink.direct_grads:
-        # the direct backward needs every leaf of the fused renderer inside the optimizer (e.g. train_orient_conf = False
-        # leaves _orient_conf out): otherwise autograd accumulates and the scanning guard applies -- a property of the
-        # configuration, identical on every rank
-        leaves = (gaussians._xyz, gaussians._scaling, gaussians._rotation, gaussians._opacity, gaussians._label,
-                  gaussians._orient_conf, gaussians._features_dc, gaussians._features_rest)
-        if not all(isinstance(p, torch.nn.Parameter) and p.grad is not None for p in leaves):
-            sink = None
-    can_overlap = (sink is not None and sink.direct_grads and len(cams) > 1 and background.is_cuda and
-                   not getattr(pipe, "debug", False))
-    n_streams = (2 if streams is None else int(streams)) if can_overlap else 0
-    fused_sink = (sink is not None and sink.direct_grads and background.is_cuda and not getattr(pipe, "debug", False))
-    # every view of this step goes through the fused renderer's direct backward (render() decides per camera: a camera
-    # whose tensors require grad takes the generic path, whose gradients arrive through autograd)
-    from .gaussian_renderer import _use_fused
-    all_direct = bool(fused_sink and cams and all(_use_fused(gaussians, pipe, c) for c in cams))
-    if isinstance(getattr(gaussians, "optimizer", None), FusedAdam) and not all_direct:
-        # the previous step may have left the gradient buffer undefined (zero_grad="defer" below): only a fused backward
-        # redefines it -- a rank without views, or the generic / autograd path, needs the zeros the eager step leaves
-        gaussians.optimizer.resolve_deferred()
-    defer = fused_sink and (True if defer_counts is None else bool(defer_counts))
-    run_pipe = pipe
-    if defer or densify_stats:
-        run_pipe = SimpleNamespace(**{**vars(pipe), "defer_count": bool(defer), "densify_stats": bool(densify_stats)})
-    from .optim import collectives_on
-    # (the fused update leaves the gradient buffer undefined, like zero_grad="defer": not for callers who switched that off)
-    fuse = (FUSE_ADAM_INTO_BACKWARD and DEFER_GRAD_ZEROING if fuse_adam is None else bool(fuse_adam)) and all_direct and \
-        bool(cams) and not collectives_on() and bucket is None
-    # Data-parallel steps of few views send the SH gradients -- 48 of the 61 floats per Gaussian -- in factored form: every view's
-    # backward leaves its dL/d(rgb) table (12 B per Gaussian) in a slot of the optimizer, the ranks all-gather the slots and each
-    # rebuilds the f_dc / f_rest gradients (optim.FusedAdam.begin_factored_views).  The choice decides the sequence of
-    # collectives: it depends on the configuration and on the GLOBAL number of views only, never on this rank's cameras.
-    from . import optim as _optim
-    if sink is not None:
-        sink.end_factored_views()  # (a step that died between its backwards and its update)
-    slots = int(views_per_rank) if views_per_rank else -(-V // max(_world_size(), 1))
-    factored = bool(collectives_on() and fused_sink and OVERLAP_ALL_REDUCE_WITH_ADAM and bucket is None and
-                    _optim.FACTORED_SH_REDUCE and 0 < slots * _world_size() <= _optim.FACTORED_SH_MAX_VIEWS and
-                    sink.can_factor_views())
-    if factored:
-        if len(cams) > slots:
-            raise RuntimeError("training_step: %d views on this rank, %d view slots per rank (%d global views on %d ranks): "
-                               "pass views_per_rank = the largest number of views any rank holds, on every rank" %
-                               (len(cams), slots, V, _world_size()))
-        sink.begin_factored_views(slots, sh_degree=int(gaussians.active_sh_degree))
-    elif (all_direct and bucket is None and _optim.FACTORED_SH_REDUCE and sink.can_factor_views() and
-          len(cams) >= (3 if fuse else 2) and (not collectives_on() or OVERLAP_ALL_REDUCE_WITH_ADAM)):
-        # one rank, or too many views in all for the gathered form: the rank folds ITS views' tables into the flat gradient
-        # once (before the sums / the update; before the last view's backward when that one carries the update) and every other
-        # view's backward skips the read-modify-write of 192 B of SH gradients per Gaussian (4 views per rank through the
-        # collective branch: 2.74 -> 2.45 ms, profiles/r06k).  A rank's own choice: the sequence of collectives is the plain one.
-        sink.begin_factored_views(len(cams), gather=False, sh_degree=int(gaussians.active_sh_degree))
-    last_pipe = None
-    if fuse:
-        sink.cancel_skip()  # (as below: every backward of this step runs after any earlier surgery)
-        fuse = sink.can_fuse_step()
-    if fuse:
-        sink.begin_fused_step()
-        last_pipe = SimpleNamespace(**{**vars(run_pipe), "fuse_adam": True})
     try:
-        losses, counts = _views_forward_backward(gaussians, cams, background, opt, V, run_pipe, n_streams, sink, last_pipe)
-    finally:
-        fused_done = sink.end_fused_step() if fuse else False
-    overflow = [c.resolve()[1] for c in counts if hasattr(c, "resolve")]  # resolve every one: they feed the next guess
-    if any(overflow):
-        # a guessed capacity was too small: that view's image, loss and gradients are garbage (memory-safe garbage).
-        # Drop everything this step accumulated and redo it with blocking, exactly sized forwards.
-        sink._direct_backwards = 0
-        sink.zero()
-        sink.state_dev[1:2].zero_()
-        sink._acc_event = None
-        # (densify_stats: an overflowed view's backward pass left the statistics alone -- k_project_bwd checks the count on the
-        # device -- but the step's OTHER views have been counted, and ALL views are recomputed below: theirs would be counted twice)
-        if densify_stats and len(cams) > 1 and not all(overflow):
-            raise RuntimeError("training_step(densify_stats=True): a capacity guess overflowed in a multi-view step; the "
-                               "statistics of its other views cannot be rolled back -- use defer_counts=False for the first "
-                               "step after the scene has grown")
-        redo_pipe = SimpleNamespace(**{**vars(pipe), "densify_stats": True}) if densify_stats else pipe
-        losses, counts = _views_forward_backward(gaussians, cams, background, opt, V, redo_pipe, 0, sink)
-        if fused_done:  # (the overflowed views raised the step's flag: the fused update was undone on the device)
-            sink.fused_steps -= 1
+        gaussians.update_learning_rate(iteration)
+        plan = _plan_step(gaussians, cams, background, bucket, global_views, pipe, streams, defer_counts, densify_stats,
+                          fuse_adam, views_per_rank)
+        fuse = _open_step(plan, gaussians, cams)
+        try:
+            losses, counts = _views_forward_backward(gaussians, cams, background, opt, plan.V, plan.run_pipe, plan.n_streams,
+                                                     plan.sink, plan.last_pipe if fuse else None)
+        finally:
+            fused_done = plan.sink.end_fused_step() if fuse else False
+        overflow = [c.resolve()[1] for c in counts if hasattr(c, "resolve")]  # resolve every one: they feed the next guess
+        if any(overflow):
+            losses = _redo_overflowed_step(plan, gaussians, cams, background, opt, pipe, densify_stats, overflow, fused_done)
             fused_done = False
-    if not losses:  # a rank without views in this step still takes part in the collectives and the update
-        total = torch.zeros((), device=background.device)
-    else:
-        total = losses[0] if len(losses) == 1 else torch.stack(losses).sum()
-    if fused_done:
-        return total  # the last view's backward carried the update (k_adam_v4 did not run)
-    if isinstance(gaussians.optimizer, FusedAdam):
-        # Every backward of this step ran AFTER any earlier optimizer surgery (densification / opacity reset between two
-        # calls), so all groups hold fresh gradients: the "parameters replaced since the last backward" marks never apply
-        # here, whichever path produced the gradients (generic pipe, autograd accumulation, a rank without views).  They
-        # only matter for a hand-written loop that runs backward -> surgery -> step (the reference's order), which calls
-        # optimizer.step() itself.  Unconditional, hence identical on every rank.
-        gaussians.optimizer.cancel_skip()
-        # SH bands above the active degree carry exactly-zero gradients on every rank: not part of the all-reduce
-        gaussians.optimizer.active_rest_coeffs = (int(gaussians.active_sh_degree) + 1) ** 2 - 1
-        # grads already live in the optimizer's flat buffer; NaN guard + Adam + grad zeroing are one HIP pass
-        # every view's gradients went through the fused renderer's direct backward (which keeps the NaN flag) and no
-        # other rank contributes: the guard needs no scan over the gradients
-        direct_local = gaussians.optimizer._direct_backwards == len(cams)
-        # On the fused path the next training_step's first backward ASSIGNS the whole gradient buffer, so the Adam pass
-        # need not zero it (an eighth of its traffic): FusedAdam.step(zero_grad="defer").  Anything else that touches the
-        # buffer first either gets the zeros (resolve_deferred) or fails loudly (optim.py).
-        zg = "defer" if (all_direct and direct_local and DEFER_GRAD_ZEROING) else True
-        # The choice below must be the same on every rank (it decides the sequence of collectives): it only depends on
-        # the configuration (`fused_sink`), and a rank whose gradients did not all come through the direct backward
-        # fails loudly instead of silently taking the other branch.
-        from .optim import collectives_on
-        if collectives_on() and fused_sink and OVERLAP_ALL_REDUCE_WITH_ADAM:
-            if not direct_local:
-                raise RuntimeError("training_step: %d of %d views went through the fused backward on this rank" %
-                                   (gaussians.optimizer._direct_backwards, len(cams)))
-            # all-reduce in chunks, each chunk's Adam update as soon as its sum is there (FusedAdam.step_chunked)
-            gaussians.optimizer.step_chunked(chunks=4, zero_grad=zg, reduce=True)
-            return total
-        gaussians.optimizer.all_reduce()
-        gaussians.optimizer.step(zero_grad=zg, nan_scan=not (direct_local and not collectives_on()))
+        if not losses:  # a rank without views in this step still takes part in the collectives and the update
+            total = torch.zeros((), device=background.device)
+        else:
+            total = losses[0] if len(losses) == 1 else torch.stack(losses).sum()
+        if not fused_done:  # (otherwise the last view's backward carried the update: k_adam_v4 does not run)
+            _update(plan, gaussians, cams, bucket)
         return total
-    if bucket is not None:
-        bucket.all_reduce()
-        bad = bucket.has_nan()
-    else:
-        bad = torch.stack([p.grad.isnan().any() for p in gaussians.leaf_parameters() if p.grad is not None]).any()
-    # train_gaussians.py:174-181: a NaN anywhere skips the update -- the reference drops the gradients
-    # (zero_grad(set_to_none=True)), so optimizer.step() touches nothing: no moment decay, no step count.
-    # One host decision per step, like the reference's `if torch.isnan(...)` (the torch.optim.Adam path is not the measured
-    # one; round 2's clone-everything-and-restore variant tripled the optimizer traffic and still synchronised on Adam's
-    # CPU-resident step counters).
-    if bool(bad):
-        print('NaN during backprop was found, skipping iteration...')
-        if bucket is not None:
-            # the gradients alias the bucket and cannot be dropped to None: a step over zeroed gradients would still decay
-            # the moments and move the parameters by lr m / sqrt(v) -- skip the whole step, as the reference's does in effect
-            bucket.zero()
-            return total
-        gaussians.optimizer.zero_grad(set_to_none=True)
-    gaussians.optimizer.step()
-    if bucket is not None:
-        bucket.zero()
-    else:
-        gaussians.optimizer.zero_grad(set_to_none=True)
-    return total
-
-
-@functools.wraps(_training_step)
-def training_step(gaussians, cams: List, background, opt, iteration: int, *args, **kwargs):
-    # (this wrapper only makes sure the optimizer's view slots never outlive the step)
-    try:
-        return _training_step(gaussians, cams, background, opt, iteration, *args, **kwargs)
-    finally:
+    finally:  # (the optimizer's view slots never outlive the step)
         o = getattr(gaussians, "optimizer", None)
         if hasattr(o, "end_factored_views"):
             o.end_factored_views()
-
-
-training_step.__name__ = training_step.__qualname__ = "training_step"
 
 
 @torch.no_grad()
@@ -408,8 +432,6 @@ def strand_view_loss(render_pkg, cam, opt, fused=None, scale: float = 1.0):
 def strand_training_step(gaussians, gaussians_hair, cams: List, background, opt, iteration: int, pipe=PIPE):
     """One iteration of the strand stage (src/train_strands.py:98-160): rebuild the strand Gaussians from the strand
     parameters, render head + hair, loss, backward, NaN guard on the strand parameters, Adam."""
-    from .gaussian_renderer import _use_fused_hair, render_hair
-    from .optim import FusedAdam
     gaussians_hair.initialize_gaussians_hair()
     gaussians_hair.update_learning_rate(iteration)
     V = len(cams)
@@ -419,7 +441,7 @@ def strand_training_step(gaussians, gaussians_hair, cams: List, background, opt,
     # for an Adam pass to read back.  The strand directions' and the confidence's gradients arrive through autograd after
     # that kernel; they are stepped -- and their NaN mark is added to the step's flag -- before the step is finished on the
     # device (FusedAdam.finish_fused_step_with_late_groups), which undoes everything when the flag is up.
-    o = gaussians_hair.optimizer if isinstance(getattr(gaussians_hair, "optimizer", None), FusedAdam) else None
+    o = _fused_adam(gaussians_hair)
     fuse = bool(FUSE_STRAND_ADAM and o is not None and V == 1 and o.direct_grads and o.can_fuse_step() and
                 not getattr(pipe, "debug", False) and _use_fused_hair(gaussians, gaussians_hair, pipe, cams[0]) and
                 all(g["name"] in ("xyz", "f_dc", "f_rest", "orient_conf") for g in o.param_groups))
@@ -437,16 +459,15 @@ def strand_training_step(gaussians, gaussians_hair, cams: List, background, opt,
             losses.append(loss.detach())
             if cam is not cams[-1]:
                 gaussians_hair.initialize_gaussians_hair()  # a fresh graph for the next view
-        if fuse and o._fuse_step["done"]:
+        if fuse and o.fused_update_launched:
             o.finish_fused_step_with_late_groups([g["name"] for g in o.param_groups if g["name"] not in ("f_dc", "f_rest")])
     finally:
         if fuse:
             fused_done = o.end_fused_step(grads_zero=True)
     if fused_done:
         return losses[0]
-    if isinstance(gaussians_hair.optimizer, FusedAdam):
-        o = gaussians_hair.optimizer
-        if o._direct_backwards == V and V > 0:
+    if o is not None:
+        if o.direct_backwards == V and V > 0:
             # every view's SH-feature gradients (48 of the 52 floats per Gaussian) were assigned by the fused backward, which
             # raised the optimizer's flag for any non-finite value it stored; what reached the remaining parameters through
             # autograd (strand directions, confidence: 4 of the 52 floats per Gaussian) is scanned here -- not everything
