@@ -14,6 +14,7 @@
 #include "ghr_binning.h"
 #include "ghr_device.h"
 #include "ghr_adam.h"
+#include "ghr_camera.h"
 #include "ghr_geom_bwd.h"
 #include "ghr_knn.h"
 #include "ghr_loss.h"
@@ -1083,6 +1084,70 @@ int ghr_knn_mean_dist2(void* stream, int64_t P, const float* points, const int64
     hipLaunchKernelGGL(ghr::k_knn_search, dim3((unsigned)((nb + GHR_KNN_WAVES - 1) / GHR_KNN_WAVES)),
                        dim3(64 * GHR_KNN_WAVES), 0, s, (int)P, sorted, bbox, sbox, out);
     return finish(s, 0);
+}
+
+static int check_camera_rows(const char* who, int32_t parametrisation, int32_t rows, int32_t first, int32_t n, const void* consts,
+                             int32_t const_stride, const void* params, int32_t param_stride)
+{
+    if (parametrisation != GHR_CAM_ORTHO6D && parametrisation != GHR_CAM_SE3)
+        return fail(GHR_E_INVALID, "%s: unknown parametrisation (GHR_CAMERA_ORTHO6D or GHR_CAMERA_SE3)", who);
+    if (first < 0 || n < 0 || rows < 0) return fail(GHR_E_INVALID, "%s: rows / first / n < 0", who);
+    if ((int64_t)first + n > rows) return fail(GHR_E_INVALID, "%s: rows [first, first + n) reach past the bank's rows", who);
+    if (!consts || !params) return fail(GHR_E_INVALID, "%s: NULL base pointer", who);
+    if (const_stride < GHR_CAM_CONST || param_stride < ghr::cam_row(parametrisation))
+        return fail(GHR_E_INVALID, "%s: a row stride is smaller than the row", who);
+    return GHR_OK;
+}
+
+int ghr_camera_compose(void* stream, int32_t parametrisation, int32_t rows, int32_t first, int32_t n, const float* consts,
+                       int32_t const_stride, const float* params, int32_t param_stride, float* out, int32_t out_stride)
+{
+    if (int rc = check_camera_rows("ghr_camera_compose", parametrisation, rows, first, n, consts, const_stride, params, param_stride))
+        return rc;
+    if (!out) return fail(GHR_E_INVALID, "ghr_camera_compose: NULL base pointer");
+    if (out_stride < GHR_CAM_OUT) return fail(GHR_E_INVALID, "ghr_camera_compose: a row stride is smaller than the row");
+    if (n == 0) return GHR_OK;
+    const ghr::CamArgs a{parametrisation, first, n, consts, const_stride, params, param_stride};
+    hipLaunchKernelGGL(ghr::k_cam_compose, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, a, out, out_stride);
+    return finish((hipStream_t)stream, 0);
+}
+
+int ghr_camera_compose_backward(void* stream, int32_t parametrisation, int32_t rows, int32_t first, int32_t n, const float* consts,
+                                int32_t const_stride, const float* params, int32_t param_stride, const float* d_view,
+                                const float* d_full, const float* d_proj, const float* d_center, const float* d_fovx,
+                                const float* d_fovy, float* grads, int32_t grad_stride, int32_t* touched, int32_t train_mask)
+{
+    if (int rc = check_camera_rows("ghr_camera_compose_backward", parametrisation, rows, first, n, consts, const_stride, params,
+                                   param_stride))
+        return rc;
+    if (!grads || !touched) return fail(GHR_E_INVALID, "ghr_camera_compose_backward: NULL base pointer");
+    if (grad_stride < ghr::cam_row(parametrisation))
+        return fail(GHR_E_INVALID, "ghr_camera_compose_backward: a row stride is smaller than the row");
+    if (train_mask & ~(GHR_CAM_TRAIN_POSE | GHR_CAM_TRAIN_FOV)) return fail(GHR_E_INVALID, "ghr_camera_compose_backward: bad train_mask");
+    if (n == 0 || train_mask == 0) return GHR_OK;
+    const ghr::CamArgs a{parametrisation, first, n, consts, const_stride, params, param_stride};
+    const ghr::CamCotangents d{d_view, d_full, d_proj, d_center, d_fovx, d_fovy};
+    hipLaunchKernelGGL(ghr::k_cam_compose_bwd, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, a, d, grads, grad_stride,
+                       touched, train_mask);
+    return finish((hipStream_t)stream, 0);
+}
+
+int ghr_camera_adam_step(void* stream, int32_t parametrisation, int32_t n, float* params, float* grads, float* exp_avg,
+                         float* exp_avg_sq, int32_t stride, int32_t* steps, int32_t* touched, float lr_rotation,
+                         float lr_translation, float lr_fov, double beta1, double beta2, float eps, int32_t train_mask)
+{
+    if (parametrisation != GHR_CAM_ORTHO6D && parametrisation != GHR_CAM_SE3)
+        return fail(GHR_E_INVALID, "ghr_camera_adam_step: unknown parametrisation (GHR_CAMERA_ORTHO6D or GHR_CAMERA_SE3)");
+    if (n < 0) return fail(GHR_E_INVALID, "ghr_camera_adam_step: n < 0");
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !steps || !touched)
+        return fail(GHR_E_INVALID, "ghr_camera_adam_step: NULL base pointer");
+    if (stride < ghr::cam_row(parametrisation)) return fail(GHR_E_INVALID, "ghr_camera_adam_step: the row stride is smaller than the row");
+    if (train_mask & ~(GHR_CAM_TRAIN_POSE | GHR_CAM_TRAIN_FOV)) return fail(GHR_E_INVALID, "ghr_camera_adam_step: bad train_mask");
+    if (n == 0) return GHR_OK;
+    hipLaunchKernelGGL(ghr::k_cam_adam, dim3(1), dim3(GHR_CAM_ADAM_THREADS), 0, (hipStream_t)stream, parametrisation, n, params,
+                       grads, exp_avg, exp_avg_sq, stride, steps, touched, lr_rotation, lr_translation, lr_fov, beta1, beta2, eps,
+                       train_mask);
+    return finish((hipStream_t)stream, 0);
 }
 
 int ghr_selftest_wave(void* stream, const float* in, float* out)

@@ -3,6 +3,8 @@
 ``full_proj_transform`` (= view @ proj, row-vector convention) and ``camera_center``; plus optional ground truth."""
 from __future__ import annotations
 
+import contextlib
+import ctypes
 import math
 from typing import Optional
 
@@ -58,7 +60,8 @@ class TrainableCamera(Camera):
     rebuilds every matrix on every property access (and inverts a 4x4 for the camera centre); here ``tensors()`` builds all
     five once per call under autograd -- ``render()`` asks for them once per view (``fused.camera_inputs``) -- and the
     properties are thin views of the same computation for code that reads them one by one.  BARF's se(3) parametrisation
-    (utils/camera_opt_utils.py) is out of scope: any camera class whose five tensors carry a graph works the same way."""
+    (utils/camera_opt_utils.py), the reference's default, is what ``CameraBank`` below composes -- one launch per view, with the
+    cameras' own Adam; this class stays the PyTorch-composed ortho-6D form (``bench.py`` times it)."""
 
     def __init__(self, R, T, FoVx, FoVy, width, height, znear=0.01, zfar=100.0, device="cpu", image_name="synthetic",
                  trainable_cameras=True, trainable_intrinsics=True):
@@ -104,6 +107,387 @@ class TrainableCamera(Camera):
     FoVx = property(lambda self: self.tensors()[3])
     FoVy = property(lambda self: self.tensors()[4])
     projection_matrix = property(lambda self: self.tensors()[5])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The camera bank: all trainable cameras of a scene as rows of flat buffers, composed / back-propagated / stepped by the three
+# kernels of csrc/ghr_camera.h (include/ghr.h: ghr_camera_compose, ghr_camera_compose_backward, ghr_camera_adam_step).
+def _sinc_family(s, offset):
+    """sum_k (-1)^k s^k / (2 k + offset)!, k = 0 .. 10, by Horner's rule in s = theta^2: offset 1 is sin(t) / t, 2 is
+    (1 - cos t) / t^2, 3 is (t - sin t) / t^3 -- the eleven-term polynomials the reference's se(3) exponential uses
+    (utils/camera_opt_utils.py, nth = 10).  No square root and no division by theta: value and gradient are finite at w = 0."""
+    coeff = [(-1.0) ** k / math.factorial(2 * k + offset) for k in range(11)]
+    acc = torch.full_like(s, coeff[-1])
+    for c in reversed(coeff[:-1]):
+        acc = acc * s + c
+    return acc
+
+
+_SO3_GENERATORS = torch.tensor([[[0.0, 0.0, 0.0], [0.0, 0.0, -1.0], [0.0, 1.0, 0.0]],
+                                [[0.0, 0.0, 1.0], [0.0, 0.0, 0.0], [-1.0, 0.0, 0.0]],
+                                [[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 0.0]]])
+
+
+def _cross_matrix(w):
+    """[w]x = sum_k w_k G_k with the three generators of so(3)"""
+    return torch.einsum("k,kij->ij", w, _SO3_GENERATORS.to(device=w.device, dtype=w.dtype))
+
+
+def compose_camera_torch(use_barf, consts, rotation_res, translation_res, fov_res):
+    """One camera of a ``CameraBank`` in PyTorch ops (the A/B comparator of the kernels, and the form CPU tensors take): the six
+    tensors of ``tensors()`` from a constants row (include/ghr.h) and the three residuals.  Semantics of src/scene/cameras.py:
+    94-154 for both parametrisations; the camera centre in the closed form -t R^T of the rigid transform."""
+    W2C = consts[:16].view(4, 4)
+    if use_barf:
+        wx, s = _cross_matrix(rotation_res), (rotation_res * rotation_res).sum()
+        A, B, C = _sinc_family(s, 1), _sinc_family(s, 2), _sinc_family(s, 3)
+        eye, wx2 = torch.eye(3, dtype=consts.dtype, device=consts.device), wx @ wx
+        R, V = eye + A * wx + B * wx2, eye + B * wx + C * wx2
+        top = torch.cat([R, V @ translation_res[:, None]], dim=1)
+    else:
+        top = torch.cat([ortho2rotation(rotation_res), translation_res[:, None]], dim=1)
+    bottom = torch.zeros(1, 4, dtype=consts.dtype, device=consts.device)
+    bottom[0, 3] = 1.0
+    view = (W2C @ torch.cat([top, bottom], dim=0)).transpose(0, 1)
+    fov = consts[16:18] + fov_res
+    znear = consts[18]
+    right = torch.tan(fov / 2) * znear
+    inv_tan = 2.0 * znear / (right - (-right))   # graphics_utils.py:55-65
+    e = torch.zeros(5, 4, 4, dtype=consts.dtype, device=consts.device)
+    e[0, 0, 0] = e[1, 1, 1] = e[2, 2, 2] = e[3, 3, 2] = e[4, 2, 3] = 1.0
+    proj = e[0] * inv_tan[0] + e[1] * inv_tan[1] + e[2] * consts[19] + e[3] * consts[20] + e[4]
+    full = view @ proj
+    center = -(view[3, :3] @ view[:3, :3].transpose(0, 1))
+    return view, full, center, fov[0], fov[1], proj
+
+
+class _BankCompose(torch.autograd.Function):
+    """``BankCamera.tensors()`` on a ROCm device: forward = one ghr_camera_compose of the camera's row, backward = one
+    ghr_camera_compose_backward that writes into the bank's gradient row.  The only autograd input is the bank's anchor (a
+    scalar leaf that makes autograd record the node); it gets no gradient -- nothing dense for autograd to accumulate."""
+
+    @staticmethod
+    def forward(ctx, anchor, bank, index):
+        out = bank._compose_rows(index, 1)[0]
+        ctx.bank, ctx.index = bank, index
+        ctx.set_materialize_grads(False)
+        return CameraBank._split(out)
+
+    @staticmethod
+    def backward(ctx, d_view, d_full, d_center, d_fovx, d_fovy, d_proj):
+        ctx.bank._backward_rows(ctx.index, 1, d_view, d_full, d_proj, d_center, d_fovx, d_fovy)
+        return None, None, None
+
+
+class BankCamera:
+    """Camera ``index`` of a ``CameraBank``: quacks like the reference's ``Camera`` (image size, znear / zfar, image_name, the
+    ``original_*`` ground-truth slots, ``_rotation_res`` / ``_translation_res`` / ``_fov_res`` -- views of the bank's parameter
+    row) with all six tensors from ONE evaluation (``tensors()``; ``fused.camera_inputs`` asks for it once per view)."""
+
+    def __init__(self, bank, index, width, height, image_name, R=None, T=None, znear=0.01, zfar=100.0):
+        self.bank, self.index = bank, int(index)
+        self.image_width, self.image_height = int(width), int(height)
+        self.image_name, self.znear, self.zfar = image_name, znear, zfar
+        self.R, self.T = R, T
+        self.trainable_cameras, self.trainable_intrinsics, self.use_barf = bank.trainable_cameras, bank.trainable_intrinsics, bank.use_barf
+        self.original_image: Optional[torch.Tensor] = None
+        self.original_mask: Optional[torch.Tensor] = None
+        self.original_orient_angle: Optional[torch.Tensor] = None
+        self.original_orient_conf: Optional[torch.Tensor] = None
+        self._frozen = None   # (key, tensors) of the last evaluation without a graph
+
+    _rotation_res = property(lambda self: self.bank.params[self.index, :self.bank.rot_dim])
+    _translation_res = property(lambda self: self.bank.params[self.index, self.bank.rot_dim:self.bank.rot_dim + 3])
+    _fov_res = property(lambda self: self.bank.params[self.index, self.bank.rot_dim + 3:])
+
+    def tensors(self):
+        """(world_view_transform, full_proj_transform, camera_center, FoVx, FoVy, projection_matrix).  While the bank trains
+        (``CameraBank.live``) and autograd records, they carry the graph to the bank's gradient row; otherwise they are constants,
+        re-used until the bank's parameters change (a constant FoV is read by the host once, not once per view)."""
+        bank = self.bank
+        if bank.live and bank.train_mask and torch.is_grad_enabled():
+            if bank.fused:
+                return _BankCompose.apply(bank._anchor, bank, self.index)
+            return bank._compose_torch_row(self.index)
+        key = (bank._version, bank.params._version)
+        if self._frozen is None or self._frozen[0] != key:
+            with torch.no_grad():
+                out = bank._compose_rows(self.index, 1)[0] if bank.fused else None
+                t = CameraBank._split(out) if bank.fused else bank._compose_torch_row(self.index, graph=False)
+            self._frozen = (key, t)
+        return self._frozen[1]
+
+    world_view_transform = property(lambda self: self.tensors()[0])
+    full_proj_transform = property(lambda self: self.tensors()[1])
+    camera_center = property(lambda self: self.tensors()[2])
+    FoVx = property(lambda self: self.tensors()[3])
+    FoVy = property(lambda self: self.tensors()[4])
+    projection_matrix = property(lambda self: self.tensors()[5])
+
+
+class CameraBank:
+    """The residuals of all N cameras of a scene in one flat device buffer, their Adam moments and per-camera step counts beside
+    it (the reference keeps three nn.Parameters per camera and a torch.optim.Adam over 3 N tensors: src/scene/cameras.py:83-92,
+    src/train_gaussians.py:45-66).  ``use_barf``: BARF's se(3) residual (the reference's default) or the ortho-6D rotation.
+    ``trainable_cameras`` / ``trainable_intrinsics`` off leave the pose / the FoV group frozen: it composes (at its initial
+    value, or whatever was loaded), gets no gradient and no update.
+
+    ``cameras``: ``Camera`` objects (their R, T, FoV, size, name and ground-truth slots are taken over) or
+    ``(R, T, FoVx, FoVy, width, height, image_name)`` records.  ``bank[i]`` is a ``BankCamera``.
+
+    On a ROCm device (``fused``, the default there) ``bank[i].tensors()`` is one launch, its backward one launch that writes
+    dL/d(residuals) into row i of ``bank.grads`` and raises the row's ``touched`` mark, and ``step()`` one launch over all rows;
+    the host reads nothing back.  On CPU tensors, or with ``fused=False``, the same semantics in PyTorch ops."""
+
+    BETAS, EPS = (0.9, 0.999), 1e-15
+
+    def __init__(self, cameras, use_barf=True, trainable_cameras=True, trainable_intrinsics=True, device="cpu", fused=None,
+                 trans=np.array([0.0, 0.0, 0.0]), scale=1.0):
+        from .. import _lib
+        dev = torch.device(device)
+        self.device, self.use_barf = dev, bool(use_barf)
+        self.trainable_cameras, self.trainable_intrinsics = bool(trainable_cameras), bool(trainable_intrinsics)
+        self.fused = (dev.type == "cuda") if fused is None else bool(fused)
+        if self.fused and dev.type != "cuda":
+            raise ValueError("CameraBank(fused=True) needs a ROCm device: the kernels have no CPU form (use fused=False)")
+        self.parametrisation = _lib.CAMERA_SE3 if self.use_barf else _lib.CAMERA_ORTHO6D
+        self.rot_dim = 3 if self.use_barf else 6
+        self.width = self.rot_dim + 5
+        self.train_mask = (_lib.CAMERA_TRAIN_POSE if self.trainable_cameras else 0) | \
+                          (_lib.CAMERA_TRAIN_FOV if self.trainable_intrinsics else 0)
+        rows, self._cams = [], []
+        for i, c in enumerate(cameras):
+            if isinstance(c, (tuple, list)):
+                R, T, fx, fy, w, h, name = c
+                gt = {}
+            else:
+                R, T, fx, fy, w, h, name = c.R, c.T, float(c.FoVx), float(c.FoVy), c.image_width, c.image_height, c.image_name
+                gt = {k: getattr(c, k, None) for k in ("original_image", "original_mask", "original_orient_angle", "original_orient_conf")}
+            znear, zfar = 0.01, 100.0
+            w2c = getWorld2View2(np.asarray(R), np.asarray(T), trans, scale)   # cameras.py:72
+            # P[2][2], P[2][3] of getProjectionMatrix: Python doubles stored into an fp32 tensor (graphics_utils.py:69-70)
+            rows.append(list(w2c.reshape(-1)) + [float(fx), float(fy), znear, zfar / (zfar - znear), -(zfar * znear) / (zfar - znear)])
+            cam = BankCamera(self, i, w, h, name, np.asarray(R, dtype=np.float64), np.asarray(T, dtype=np.float64), znear, zfar)
+            for k, v in gt.items():
+                setattr(cam, k, v.to(dev) if isinstance(v, torch.Tensor) else v)
+            self._cams.append(cam)
+        N = len(rows)
+        self.consts = torch.tensor(np.asarray(rows, dtype=np.float64).reshape(N, _lib.CAMERA_CONST), dtype=torch.float32, device=dev)
+        init = torch.zeros(self.width)
+        if not self.use_barf:
+            init[:6] = torch.eye(3, 3)[:2].reshape(-1)
+        self.params = init.repeat(N, 1).contiguous().to(dev)
+        self.grads, self.exp_avg, self.exp_avg_sq = (torch.zeros(N, self.width, device=dev) for _ in range(3))
+        self.steps = torch.zeros(N, dtype=torch.int32, device=dev)     # Adam step count of each camera
+        self.touched = torch.zeros(N, dtype=torch.int32, device=dev)   # its gradient row holds this step's gradient
+        self._anchor = torch.zeros((), device=dev, requires_grad=True)
+        cols = torch.tensor([self.trainable_cameras] * (self.rot_dim + 3) + [self.trainable_intrinsics] * 2, device=dev)
+        self._train_cols = cols
+        self._version, self.live = 0, True
+        self.opt = None
+        self._lr = (0.0, 0.0, 0.0)
+
+    def __len__(self):
+        return len(self._cams)
+
+    def __getitem__(self, i) -> BankCamera:
+        return self._cams[i]
+
+    def __iter__(self):
+        return iter(self._cams)
+
+    # ---- compose ------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _split(out):
+        """one output row (include/ghr.h) -> the six tensors of ``tensors()``"""
+        return (out[0:16].view(4, 4), out[16:32].view(4, 4), out[48:51], out[51], out[52], out[32:48].view(4, 4))
+
+    def _check_rows(self, first, n):
+        if first < 0 or n < 0 or first + n > len(self):
+            raise IndexError("CameraBank: rows [%d, %d) of %d cameras" % (first, first + n, len(self)))
+
+    def _compose_rows(self, first, n):
+        from .. import _lib
+        from ..diff_gaussian_rasterization import _ptr, _stream
+        self._check_rows(first, n)
+        out = torch.empty(n, _lib.CAMERA_OUT, device=self.device)
+        _lib.check(_lib.lib().ghr_camera_compose(_stream(), self.parametrisation, len(self), int(first), int(n), _ptr(self.consts),
+                                                 _lib.CAMERA_CONST, _ptr(self.params), self.width, _ptr(out), _lib.CAMERA_OUT))
+        return out
+
+    def _backward_rows(self, first, n, d_view, d_full, d_proj, d_center, d_fovx, d_fovy):
+        from .. import _lib
+        from ..diff_gaussian_rasterization import _stream
+        self._check_rows(first, n)
+        keep = [None if d is None else d.contiguous() for d in (d_view, d_full, d_proj, d_center, d_fovx, d_fovy)]
+        for d, k in zip(keep, (16, 16, 16, 3, 1, 1)):
+            if d is not None and (d.dtype != torch.float32 or d.numel() != n * k or d.device != self.device):
+                raise ValueError("CameraBank: a cotangent is not %d fp32 values per camera on the bank's device" % k)
+        ptrs = [None if d is None else ctypes.c_void_p(d.data_ptr()) for d in keep]
+        _lib.check(_lib.lib().ghr_camera_compose_backward(
+            _stream(), self.parametrisation, len(self), int(first), int(n), ctypes.c_void_p(self.consts.data_ptr()), _lib.CAMERA_CONST,
+            ctypes.c_void_p(self.params.data_ptr()), self.width, *ptrs, ctypes.c_void_p(self.grads.data_ptr()), self.width,
+            ctypes.c_void_p(self.touched.data_ptr()), self.train_mask))
+
+    def _compose_torch_row(self, i, graph=True):
+        rd = self.rot_dim
+        p = self.params[i].detach().clone()
+        if graph:
+            p.requires_grad_(True)
+            p.register_hook(lambda g, i=i: self._accumulate(i, g))
+        return compose_camera_torch(self.use_barf, self.consts[i], p[:rd], p[rd:rd + 3], p[rd + 3:])
+
+    @torch.no_grad()
+    def _accumulate(self, i, g):
+        """the PyTorch form of the backward kernel's last lines: assign to an untouched row, add to a touched one; frozen groups 0"""
+        g = torch.where(self._train_cols, g, torch.zeros_like(g))
+        self.grads[i] = torch.where(self.touched[i] != 0, self.grads[i] + g, g)
+        self.touched[i] = 1
+
+    @torch.no_grad()
+    def compose_all(self):
+        """All N cameras' tensors from one launch, without a graph: (world_view_transform [N,4,4], full_proj_transform [N,4,4],
+        camera_center [N,3], FoVx [N], FoVy [N], projection_matrix [N,4,4]) -- for export and evaluation."""
+        N = len(self)
+        if self.fused:
+            out = self._compose_rows(0, N)
+            return (out[:, 0:16].view(N, 4, 4), out[:, 16:32].view(N, 4, 4), out[:, 48:51], out[:, 51], out[:, 52],
+                    out[:, 32:48].view(N, 4, 4))
+        rows = [self._compose_torch_row(i, graph=False) for i in range(N)]
+        return tuple(torch.stack([r[k] for r in rows]) if N else torch.zeros(0, device=self.device) for k in range(6))
+
+    # ---- the cameras' optimizer (src/train_gaussians.py:57-66,183-196) ------------------------------------------------------
+    def training_setup(self, opt, spatial_lr_scale: float = 1.0):
+        from ..utils.general_utils import get_expon_lr_func
+        self.opt = opt
+        self.iterations_cam = int(opt.iterations_cam)
+        self._lr_rotation, self._lr_fov = float(opt.cam_rotation_lr), float(opt.cam_fov_lr)
+        self._lr_translation = get_expon_lr_func(lr_init=opt.cam_translation_lr_init * spatial_lr_scale,
+                                                 lr_final=opt.cam_translation_lr_final * spatial_lr_scale,
+                                                 max_steps=opt.cam_lr_max_steps)
+        return self
+
+    def learning_rates(self, iteration):
+        """(rotation, translation, fov) learning rates of ``iteration``: host floats, the translation's on its schedule"""
+        return self._lr_rotation, float(self._lr_translation(iteration)), self._lr_fov
+
+    @contextlib.contextmanager
+    def step_scope(self, iteration=None):
+        """The views of one training iteration (``trainer.training_step`` wraps them; a hand-written loop may):
+        ``with bank.step_scope(iteration): render ...; loss.backward()``.  Inside, from ``opt.iterations_cam`` on, the cameras are
+        constants (no graph: the views take the constant-camera path, no camera-gradient work for a ``step`` that no longer moves
+        them); ``live`` is restored on the way out, so ``tensors()`` outside a scope always carries the graph.  If the body raises,
+        what its backwards left in the gradient rows is dropped (``discard_gradients``).  ``iteration=None`` only does the latter."""
+        if iteration is not None and self.opt is None:
+            raise RuntimeError("CameraBank.training_setup(opt, spatial_lr_scale) has not been called")
+        before = self.live
+        if iteration is not None:
+            self.live = iteration < self.iterations_cam
+        try:
+            yield self
+        except BaseException:
+            self.discard_gradients()
+            raise
+        finally:
+            self.live = before
+
+    @torch.no_grad()
+    def discard_gradients(self):
+        """Lowers every touched mark: the next backward into a row assigns it, ``step`` passes it by."""
+        self.touched.zero_()
+
+    def step(self, iteration, lrs=None):
+        """One Adam step of every camera viewed since the last one, at ``iteration``'s learning rates (``lrs`` overrides them);
+        nothing at ``iteration >= opt.iterations_cam``.  A NaN in a viewed camera's gradient skips the whole step; the viewed
+        cameras' gradients and marks are cleared either way."""
+        if self.opt is None:
+            raise RuntimeError("CameraBank.training_setup(opt, spatial_lr_scale) has not been called")
+        if iteration >= self.iterations_cam or not self.train_mask or not len(self):
+            return
+        lr = tuple(float(x) for x in (lrs if lrs is not None else self.learning_rates(iteration)))
+        self._lr = lr
+        if self.fused:
+            from .. import _lib
+            from ..diff_gaussian_rasterization import _stream
+            vp = lambda t: ctypes.c_void_p(t.data_ptr())
+            _lib.check(_lib.lib().ghr_camera_adam_step(_stream(), self.parametrisation, len(self), vp(self.params), vp(self.grads),
+                                                       vp(self.exp_avg), vp(self.exp_avg_sq), self.width, vp(self.steps),
+                                                       vp(self.touched), lr[0], lr[1], lr[2], self.BETAS[0], self.BETAS[1],
+                                                       self.EPS, self.train_mask))
+        else:
+            self._step_torch(lr)
+        self._version += 1
+
+    @torch.no_grad()
+    def _step_torch(self, lr):
+        """k_cam_adam in PyTorch ops (no host decision either)"""
+        rd, (b1, b2) = self.rot_dim, self.BETAS
+        t, col = self.touched != 0, self._train_cols
+        bad = (torch.isnan(self.grads) & t[:, None] & col[None]).any()
+        upd = t & ~bad
+        steps = self.steps + upd.to(torch.int32)
+        sf = steps.clamp(min=1).double()
+        bias1, b2s = 1.0 - b1 ** sf, torch.sqrt(1.0 - b2 ** sf).float()
+        lrs = torch.tensor([lr[0]] * rd + [lr[1]] * 3 + [lr[2]] * 2, dtype=torch.float64, device=self.device)
+        ss = (lrs[None] / bias1[:, None]).float()
+        g = self.grads
+        m = self.exp_avg + (g - self.exp_avg) * float(np.float32(1.0 - b1))
+        v = self.exp_avg_sq * float(np.float32(b2)) + float(np.float32(1.0 - b2)) * g * g
+        p = self.params - ss * (m / (torch.sqrt(v) / b2s[:, None] + self.EPS))
+        sel = upd[:, None] & col[None]
+        self.params.copy_(torch.where(sel, p, self.params))
+        self.exp_avg.copy_(torch.where(sel, m, self.exp_avg))
+        self.exp_avg_sq.copy_(torch.where(sel, v, self.exp_avg_sq))
+        self.steps.copy_(steps)
+        self.grads.copy_(torch.where(t[:, None], torch.zeros_like(g), g))
+        self.touched.zero_()
+
+    # ---- persistence --------------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        return {"use_barf": self.use_barf, "image_names": [c.image_name for c in self._cams],
+                "params": self.params.detach().clone(), "exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(),
+                "steps": self.steps.clone()}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        if bool(sd["use_barf"]) != self.use_barf or tuple(sd["params"].shape) != tuple(self.params.shape):
+            raise ValueError("CameraBank.load_state_dict: another parametrisation or number of cameras")
+        if list(sd["image_names"]) != [c.image_name for c in self._cams]:
+            raise ValueError("CameraBank.load_state_dict: the cameras' image names differ")
+        for k in ("params", "exp_avg", "exp_avg_sq", "steps"):
+            getattr(self, k).copy_(sd[k].to(self.device))
+        self.grads.zero_()
+        self.touched.zero_()
+        self._version += 1
+
+    @torch.no_grad()
+    def reference_pickles(self):
+        """What the reference's loop dumps at a checkpoint (src/train_gaussians.py:203-208): ``((params_cam_rotation,
+        params_cam_translation, params_cam_fov), projection_all)`` -- dicts image_name -> tensor (CPU copies; the residual dicts of
+        a frozen group are empty, as there), the matrices from one ``compose_all()``."""
+        rd, P = self.rot_dim, self.params.detach().cpu()
+        names = [c.image_name for c in self._cams]
+        rot = {n: P[i, :rd].clone() for i, n in enumerate(names)} if self.trainable_cameras else {}
+        tra = {n: P[i, rd:rd + 3].clone() for i, n in enumerate(names)} if self.trainable_cameras else {}
+        fov = {n: P[i, rd + 3:].clone() for i, n in enumerate(names)} if self.trainable_intrinsics else {}
+        full = self.compose_all()[1].cpu()
+        return (rot, tra, fov), {n: full[i].clone() for i, n in enumerate(names)}
+
+    @torch.no_grad()
+    def load_reference_pickles(self, dicts):
+        """Takes the three dicts of a reference ``cameras/<iteration>.pkl`` (every camera of the bank must be in each non-empty
+        one; the moments and step counts are left alone, as the reference's restart leaves them at zero)."""
+        rd = self.rot_dim
+        for d, lo, hi in zip(dicts, (0, rd, rd + 3), (rd, rd + 3, rd + 5)):
+            if not d:
+                continue
+            for i, c in enumerate(self._cams):
+                v = torch.as_tensor(d[c.image_name]).detach().reshape(-1).to(device=self.device, dtype=torch.float32)
+                if v.numel() != hi - lo:
+                    raise ValueError("CameraBank.load_reference_pickles: %s has %d values, the bank's parametrisation %d" %
+                                     (c.image_name, v.numel(), hi - lo))
+                self.params[i, lo:hi] = v
+        self._version += 1
 
 
 def make_camera(width, height, fovy_deg=40.0, distance=4.0, device="cpu") -> Camera:

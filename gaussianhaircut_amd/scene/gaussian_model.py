@@ -364,3 +364,10 @@ class OptimizationParams:
     gaussian_pruning_threshold = 0.5
     train_orient_conf = True
     use_gt_orient_conf = True
+    # the cameras' own Adam (src/arguments/__init__.py:88-103; scene.cameras.CameraBank.training_setup)
+    iterations_cam = 15_000
+    cam_lr_max_steps = 15_000
+    cam_rotation_lr = 0.001
+    cam_translation_lr_init = 0.0016
+    cam_translation_lr_final = 0.000016
+    cam_fov_lr = 0.001

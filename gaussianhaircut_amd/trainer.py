@@ -315,7 +315,7 @@ def _update(plan: _StepPlan, gaussians, cams, bucket):
 def training_step(gaussians, cams: List, background, opt, iteration: int, bucket: Optional[FlatGradBucket] = None,
                   global_views: Optional[int] = None, pipe=PIPE, streams: Optional[int] = None,
                   defer_counts: Optional[bool] = None, densify_stats: bool = False, fuse_adam: Optional[bool] = None,
-                  views_per_rank: Optional[int] = None):
+                  views_per_rank: Optional[int] = None, camera_bank=None):
     """One global gradient step over this rank's views.  Returns the (detached) summed local loss.
 
     ``streams`` (default 2 with the fused path and more than one view): the views of the step are independent given
@@ -344,32 +344,77 @@ def training_step(gaussians, cams: List, background, opt, iteration: int, bucket
     rank; default ceil(global views / ranks), which is what ``parallel.shard_views`` deals.  Steps of up to
     ``optim.FACTORED_SH_MAX_VIEWS`` view slots in all send the SH gradients as per-view dL/d(rgb) tables (12 B per Gaussian and
     view, all-gathered; ``FusedAdam.begin_factored_views``) instead of summing 192 B per Gaussian: every rank opens that many
-    slots, and a rank with more views than slots fails loudly before any collective."""
+    slots, and a rank with more views than slots fails loudly before any collective.
+
+    ``camera_bank`` (a ``scene.cameras.CameraBank`` after ``training_setup``; one rank): the step's views are cameras of the bank
+    and the cameras are trained with the Gaussians, in the reference's order (src/train_gaussians.py:183-196): every view's
+    backward leaves dL/d(residuals) in its camera's gradient row, and after the Gaussians' update -- every stream of the step
+    joined -- ``camera_bank.step(iteration)`` steps the viewed cameras in one launch.  The views must be DISTINCT cameras (their
+    rows are then disjoint across the view streams): that is checked for the cameras of ANY bank among the views, with or without
+    this argument.  From ``opt.iterations_cam`` on the bank composes constants for the duration of the step and the views take the
+    constant-camera path.  A step that raises drops what its views left in their banks' gradient rows."""
+    banks = _check_bank_views(camera_bank, cams)
     try:
-        gaussians.update_learning_rate(iteration)
-        plan = _plan_step(gaussians, cams, background, bucket, global_views, pipe, streams, defer_counts, densify_stats,
-                          fuse_adam, views_per_rank)
-        fuse = _open_step(plan, gaussians, cams)
-        try:
-            losses, counts = _views_forward_backward(gaussians, cams, background, opt, plan.V, plan.run_pipe, plan.n_streams,
-                                                     plan.sink, plan.last_pipe if fuse else None)
-        finally:
-            fused_done = plan.sink.end_fused_step() if fuse else False
-        overflow = [c.resolve()[1] for c in counts if hasattr(c, "resolve")]  # resolve every one: they feed the next guess
-        if any(overflow):
-            losses = _redo_overflowed_step(plan, gaussians, cams, background, opt, pipe, densify_stats, overflow, fused_done)
-            fused_done = False
-        if not losses:  # a rank without views in this step still takes part in the collectives and the update
-            total = torch.zeros((), device=background.device)
-        else:
-            total = losses[0] if len(losses) == 1 else torch.stack(losses).sum()
-        if not fused_done:  # (otherwise the last view's backward carried the update: k_adam_v4 does not run)
-            _update(plan, gaussians, cams, bucket)
-        return total
+        with contextlib.ExitStack() as scopes:
+            for b in banks:  # (a bank that is only viewed, not stepped here, keeps its own notion of whether it trains)
+                scopes.enter_context(b.step_scope(iteration if b is camera_bank else None))
+            return _training_step(gaussians, cams, background, opt, iteration, bucket, global_views, pipe, streams, defer_counts,
+                                  densify_stats, fuse_adam, views_per_rank, camera_bank, banks)
     finally:  # (the optimizer's view slots never outlive the step)
         o = getattr(gaussians, "optimizer", None)
         if hasattr(o, "end_factored_views"):
             o.end_factored_views()
+
+
+def _training_step(gaussians, cams, background, opt, iteration, bucket, global_views, pipe, streams, defer_counts, densify_stats,
+                   fuse_adam, views_per_rank, camera_bank, banks):
+    gaussians.update_learning_rate(iteration)
+    plan = _plan_step(gaussians, cams, background, bucket, global_views, pipe, streams, defer_counts, densify_stats,
+                      fuse_adam, views_per_rank)
+    fuse = _open_step(plan, gaussians, cams)
+    try:
+        losses, counts = _views_forward_backward(gaussians, cams, background, opt, plan.V, plan.run_pipe, plan.n_streams,
+                                                 plan.sink, plan.last_pipe if fuse else None)
+    finally:
+        fused_done = plan.sink.end_fused_step() if fuse else False
+    overflow = [c.resolve()[1] for c in counts if hasattr(c, "resolve")]  # resolve every one: they feed the next guess
+    if any(overflow):
+        for b in banks:  # (the views run again: their camera gradients must not be added a second time)
+            b.discard_gradients()
+        losses = _redo_overflowed_step(plan, gaussians, cams, background, opt, pipe, densify_stats, overflow, fused_done)
+        fused_done = False
+    if not losses:  # a rank without views in this step still takes part in the collectives and the update
+        total = torch.zeros((), device=background.device)
+    else:
+        total = losses[0] if len(losses) == 1 else torch.stack(losses).sum()
+    if not fused_done:  # (otherwise the last view's backward carried the update: k_adam_v4 does not run)
+        _update(plan, gaussians, cams, bucket)
+    if camera_bank is not None:
+        camera_bank.step(iteration)
+    return total
+
+
+def _check_bank_views(bank, cams):
+    """The banks among a step's views (``bank``, the one to be stepped, first).  Views that are cameras of a bank must be DISTINCT
+    cameras of it, whether the step also steps that bank or not: two views of one camera would read-modify-write the same gradient
+    row and touched mark from two streams.  With ``bank``: one rank, and every view is a camera of it."""
+    if bank is not None and _world_size() > 1:
+        raise NotImplementedError("training_step(camera_bank=...) on more than one rank: replicating the camera updates across "
+                                  "ranks is not implemented")
+    banks, seen = ([] if bank is None else [bank]), set()
+    for c in cams:
+        b = getattr(c, "bank", None)
+        if bank is not None and b is not bank:
+            raise ValueError("training_step(camera_bank=...): every view must be a camera of that bank (bank[i])")
+        if b is None:
+            continue
+        if (id(b), c.index) in seen:
+            raise ValueError("training_step: the views of one step must be distinct cameras of their bank (row %d twice): two "
+                             "views of one camera would write the same gradient row from two streams" % c.index)
+        seen.add((id(b), c.index))
+        if not any(b is x for x in banks):
+            banks.append(b)
+    return banks
 
 
 @torch.no_grad()

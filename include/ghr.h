@@ -502,6 +502,44 @@ int ghr_knn_keys(void* stream, int64_t P, const float* points, const float* boun
 /* order [P] int64 (device); ws: ghr_knn_workspace_size(P) bytes; out [P] f32 (device). */
 int ghr_knn_mean_dist2(void* stream, int64_t P, const float* points, const int64_t* order, void* ws, float* out);
 
+/* ---- the camera bank: trainable camera residuals of a whole scene in flat device buffers (src/scene/cameras.py:83-154,
+ * src/utils/camera_opt_utils.py:84-141, src/train_gaussians.py:45-66,183-196) -------------------------------------------------
+ * Added without an ABI_VERSION bump: three new functions, no existing struct or signature changed.
+ * One row per camera in every buffer, rows `stride` floats apart (all fp32):
+ *   consts  GHR_CAMERA_CONST floats: W2C[16] (row-major getWorld2View2) | FoVx0 | FoVy0 | znear | P[2][2] | P[2][3] of
+ *           getProjectionMatrix (zfar / (zfar - znear), -(zfar znear) / (zfar - znear))
+ *   params / grads / moments  rotation_res[6 (ortho-6D) | 3 (se(3))] | translation_res[3] | fov_res[2]
+ *   out     GHR_CAMERA_OUT floats: world_view_transform[16] | full_proj_transform[16] | projection_matrix[16] | camera_center[3] |
+ *           FoVx | FoVy, the matrices transposed as the reference keeps them
+ * `rows`: the number of cameras the bank's buffers hold; `first`, `n`: the calls handle rows [first, first + n) of consts / params /
+ * grads / touched and fail when that range reaches past `rows` (nothing is launched); `out` and the cotangents hold the
+ * RANGE's rows from 0 (out + r * out_stride; cotangents dense: [n][16], [n][16], [n][16], [n][3], [n], [n]).
+ * train_mask: GHR_CAMERA_TRAIN_POSE (rotation + translation) | GHR_CAMERA_TRAIN_FOV; a group outside it composes, gets no
+ * gradient and no update. */
+#define GHR_CAMERA_ORTHO6D 0
+#define GHR_CAMERA_SE3 1
+#define GHR_CAMERA_CONST 21
+#define GHR_CAMERA_OUT 53
+#define GHR_CAMERA_TRAIN_POSE 1
+#define GHR_CAMERA_TRAIN_FOV 2
+int ghr_camera_compose(void* stream, int32_t parametrisation, int32_t rows, int32_t first, int32_t n, const float* consts,
+                       int32_t const_stride, const float* params, int32_t param_stride, float* out, int32_t out_stride);
+/* The hand-derived VJP of ghr_camera_compose.  Each cotangent pointer may be NULL (that output took no part in the loss); dFoV
+ * receives its direct cotangent and the part through projection_matrix / full_proj_transform.  A row whose touched mark is 0 has
+ * its gradient ASSIGNED (whatever it held is gone), a row with the mark up has it ADDED; the mark is set.  One thread owns a row:
+ * calls that may run concurrently (two streams) must cover disjoint rows. */
+int ghr_camera_compose_backward(void* stream, int32_t parametrisation, int32_t rows, int32_t first, int32_t n, const float* consts,
+                                int32_t const_stride, const float* params, int32_t param_stride, const float* d_view,
+                                const float* d_full, const float* d_proj, const float* d_center, const float* d_fovx,
+                                const float* d_fovy, float* grads, int32_t grad_stride, int32_t* touched, int32_t train_mask);
+/* torch.optim.Adam over the rows of all n cameras whose touched mark is up, each with ITS OWN step count (torch counts per parameter
+ * and passes a parameter without .grad by), three learning rates as host floats.  If any gradient of a touched row is NaN nothing
+ * moves and no count advances (train_gaussians.py:190-196).  Either way the touched rows' gradients and marks are cleared.  One
+ * launch, one workgroup; nothing is read back. */
+int ghr_camera_adam_step(void* stream, int32_t parametrisation, int32_t n, float* params, float* grads, float* exp_avg,
+                         float* exp_avg_sq, int32_t stride, int32_t* steps, int32_t* touched, float lr_rotation,
+                         float lr_translation, float lr_fov, double beta1, double beta2, float eps, int32_t train_mask);
+
 /* Introspection for tests (device pointers into the workspaces; layout is otherwise private). */
 typedef struct ghr_ws_view {
     const float* rec;          /* [P][16]: x, y, conic a, b, c, opacity, features[10] */

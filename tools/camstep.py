@@ -1,7 +1,10 @@
 """One mode of the configs[2] step, alone, for rocprofv3 --kernel-trace --stats (round 6):
-    python tools/camstep.py plain|leaf|residual|fixed [steps]
+    python tools/camstep.py plain|leaf|residual|fixed|bank [steps]
 plain = bench.py's headline (16 cycling cameras), fixed = camera 0 only, leaf = the five camera tensors are leaves that
-require grad, residual = scene.cameras.TrainableCamera + torch.optim.Adam over the camera parameters."""
+require grad, residual = scene.cameras.TrainableCamera + torch.optim.Adam over the camera parameters, bank = the same 16 ring
+cameras as one scene.cameras.CameraBank(use_barf=True) and training_step(camera_bank=bank).
+    python tools/camstep.py compare [steps]
+runs leaf, residual, bank, bank alternately in ONE process, twice: the first pass of each is warm-up, the second is printed."""
 import copy
 import os
 import sys
@@ -10,7 +13,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from gaussianhaircut_amd.scene.cameras import TrainableCamera, ring_cameras  # noqa: E402
+from gaussianhaircut_amd.scene.cameras import CameraBank, TrainableCamera, ring_cameras  # noqa: E402
 from gaussianhaircut_amd.scene.gaussian_model import OptimizationParams  # noqa: E402
 from gaussianhaircut_amd.trainer import make_ground_truth, training_step  # noqa: E402
 from gaussianhaircut_amd.utils import synthetic as syn  # noqa: E402
@@ -21,6 +24,15 @@ LEAVES = ("world_view_transform", "full_proj_transform", "camera_center", "FoVx"
 def main():
     mode = sys.argv[1] if len(sys.argv) > 1 else "plain"
     K = int(sys.argv[2]) if len(sys.argv) > 2 else 30
+    if mode == "compare":
+        for rep in range(2):
+            for m in ("leaf", "residual", "bank", "bank"):
+                run(m, K, report=rep == 1)
+        return
+    run(mode, K)
+
+
+def run(mode, K, report=True):
     dev = torch.device("cuda:0")
     spec = syn.CONFIGS[os.environ.get("CAMSTEP_CFG", "cfg3")]
     opt = OptimizationParams()
@@ -35,7 +47,10 @@ def main():
         make_ground_truth(gt, pool, bg)
         del gt
     model.training_setup(opt)
-    after = None
+    after, kw = None, {}
+    if mode == "bank":
+        bank = CameraBank(pool, use_barf=True, device=dev).training_setup(opt)
+        pool, kw = list(bank), dict(camera_bank=bank)
     if mode == "fixed":
         pool = pool[:1]
     if mode == "leaf":
@@ -59,7 +74,7 @@ def main():
             cam_opt.step()
             cam_opt.zero_grad(set_to_none=True)
     for i in range(5):
-        training_step(model, [pool[i % len(pool)]], bg, opt, i + 1)
+        training_step(model, [pool[i % len(pool)]], bg, opt, i + 1, **kw)
         if after:
             after(pool[i % len(pool)])
     torch.cuda.synchronize()
@@ -67,14 +82,15 @@ def main():
     host = 0.0
     for i in range(K):
         h0 = time.perf_counter()
-        training_step(model, [pool[(5 + i) % len(pool)]], bg, opt, 6 + i)
+        training_step(model, [pool[(5 + i) % len(pool)]], bg, opt, 6 + i, **kw)
         if after:
             after(pool[(5 + i) % len(pool)])
         host += time.perf_counter() - h0
     t_issue = time.perf_counter() - t0
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    print("CAMSTEP %s: %.4f ms per step over %d steps (host issue time %.4f ms per step)" % (mode, 1e3 * dt / K, K, 1e3 * t_issue / K))
+    if report:
+        print("CAMSTEP %s: %.4f ms per step over %d steps (host issue time %.4f ms per step)" % (mode, 1e3 * dt / K, K, 1e3 * t_issue / K))
 
 
 if __name__ == "__main__":
