@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GHR_LIB_PATH") or os.path.join(CSRC, "libghr_hip.so")  # override: kernel experiments
 SOURCES = ["ghr_capi.hip"]
 HEADERS = ["ghr_device.h", "ghr_preprocess.h", "ghr_binning.h", "ghr_render_fwd.h", "ghr_render_bwd.h", "ghr_render_bwd2.h", "ghr_render_bwd3.h",
-           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h"]
+           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-fPIC",
                "-shared"]
 
@@ -29,6 +29,7 @@ ADAM_STATE = 18  # GHR_ADAM_STATE
 CAMERA_ORTHO6D, CAMERA_SE3 = 0, 1  # GHR_CAMERA_*: parametrisation of a camera bank's rotation residual
 CAMERA_CONST, CAMERA_OUT = 21, 53  # GHR_CAMERA_CONST / GHR_CAMERA_OUT: floats per constants / output row
 CAMERA_TRAIN_POSE, CAMERA_TRAIN_FOV = 1, 2  # GHR_CAMERA_TRAIN_*
+EVAL_TERMS = 8  # GHR_EVAL_TERMS: doubles per view of the evaluation table {l1, ce, or_num, or_den, mse[3], ssim}
 ABI_VERSION = 20  # GHR_ABI_VERSION of include/ghr.h this binding was written for
 
 GHR_OK, GHR_E_INVALID, GHR_E_NOCOLORS, GHR_E_HIP = 0, -1, -2, -3
@@ -125,7 +126,11 @@ class LossArgs(ctypes.Structure):
                [(n, ctypes.c_float) for n in ("w_l1", "w_ssim", "w_mask", "w_orient")] + \
                [("unmasked_colours", ctypes.c_int32), ("gt_stats", ctypes.c_void_p)]
 
-
+class EvalArgs(ctypes.Structure):
+    """``ghr_eval_args`` (include/ghr.h)."""
+    _fields_ = [("W", ctypes.c_int32), ("H", ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ("renders", "gt_image", "gt_mask", "gt_orient_angle", "gt_orient_conf")] + \
+               [("with_ssim", ctypes.c_int32)]
 
 
 def loss_sums_floats(W: int, H: int) -> int:
@@ -146,7 +151,8 @@ EXPORTS = ["ghr_last_error", "ghr_abi_version", "ghr_forward_sizes", "ghr_binnin
            "ghr_model_backward_segment", "ghr_camera_slots", "ghr_camera_grad_fold", "ghr_strand_build", "ghr_strand_build_backward", "ghr_strand_build_backward_ex", "ghr_sh_grad_from_views", "ghr_loss_sums_floats", "ghr_loss_forward", "ghr_loss_gt_stats", "ghr_loss_backward", "ghr_adam_step",
            "ghr_adam_step_range", "ghr_adam_step_range_to", "ghr_adam_nan_scan", "ghr_adam_relay_rows", "ghr_adam_fused_finish",
            "ghr_knn_workspace_size", "ghr_knn_keys", "ghr_knn_mean_dist2",
-           "ghr_camera_compose", "ghr_camera_compose_backward", "ghr_camera_adam_step"]
+           "ghr_camera_compose", "ghr_camera_compose_backward", "ghr_camera_adam_step",
+           "ghr_eval_scratch_floats", "ghr_eval_metrics", "ghr_eval_products"]
 
 _lib = None
 
@@ -215,11 +221,15 @@ def lib() -> ctypes.CDLL:
     L.ghr_camera_compose_backward.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, i32] + [vp] * 6 + [vp, i32, vp, i32]
     L.ghr_camera_adam_step.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, f32, f32, f32, ctypes.c_double, ctypes.c_double,
                                        f32, i32]
+    L.ghr_eval_scratch_floats.argtypes = [i32, i32]
+    L.ghr_eval_metrics.argtypes = [vp, ctypes.POINTER(EvalArgs), vp, vp]
+    L.ghr_eval_products.argtypes = [vp, i32, i32, vp, vp, vp]
     L.ghr_ws_inspect.argtypes = [i32, i32, i32, i32, u32, vp, vp, vp, ctypes.POINTER(WsView)]
     for name in EXPORTS:
         fn = getattr(L, name)
-        if name not in ("ghr_last_error",):
+        if name not in ("ghr_last_error", "ghr_eval_scratch_floats"):
             fn.restype = ctypes.c_int
+    L.ghr_eval_scratch_floats.restype = ctypes.c_size_t
     _lib = L
     return L
 

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <vector>
 
 #include "ghr_binning.h"
@@ -18,6 +19,7 @@
 #include "ghr_geom_bwd.h"
 #include "ghr_knn.h"
 #include "ghr_loss.h"
+#include "ghr_eval.h"
 #include "ghr_preprocess.h"
 #include "ghr_project.h"
 #include "ghr_render_bwd.h"
@@ -914,6 +916,74 @@ int ghr_loss_backward(void* stream, const ghr_loss_args* l, const float* maps, c
     const dim3 grid((l->W + GHR_L_TW - 1) / GHR_L_TW, (l->H + GHR_L_TH - 1) / GHR_L_TH, 3);
     if (loss_vec_ok(l, maps)) hipLaunchKernelGGL(ghr::k_loss_bwd_v, loss_march_grid(l, a.seg), dim3(64), 0, s, a);
     else hipLaunchKernelGGL(ghr::k_loss_bwd, grid, dim3(256), 0, s, a);
+    return finish(s, 0);
+}
+
+// ---- evaluation pass (ghr_eval.h) ------------------------------------------------------------------------------------
+static bool eval_aligned16(std::initializer_list<const void*> ps)
+{
+    for (const void* p : ps)
+        if (((uintptr_t)p & 15u) != 0) return false;
+    return true;
+}
+// the knob of the loss kernels' tests selects the scalar / tile forms here too
+static bool eval_vec_off() { return std::getenv("GHR_LOSS_SCALAR") != nullptr; }
+
+size_t ghr_eval_scratch_floats(int32_t W, int32_t H)
+{
+    if (W <= 0 || H <= 0) return 0;
+    const size_t n_ssim = std::max(ghr::loss_slots_tile(W, H), ghr::loss_slots_march(W, H, GHR_LM_ROWS));
+    return (size_t)GHR_EVAL_POINT_TERMS * ghr::eval_point_groups(W, H) + n_ssim;
+}
+
+int ghr_eval_metrics(void* stream, const ghr_eval_args* e, float* scratch, double* row)
+{
+    if (!e || e->W <= 0 || e->H <= 0 || !e->renders || !e->gt_image || !e->gt_mask || !scratch || !row)
+        return fail(GHR_E_INVALID, "ghr_eval_metrics: bad args");
+    if ((e->gt_orient_angle == nullptr) != (e->gt_orient_conf == nullptr))
+        return fail(GHR_E_INVALID, "ghr_eval_metrics: gt_orient_angle and gt_orient_conf come together (both NULL: no orientation terms)");
+    if (((uintptr_t)row & 7u) != 0) return fail(GHR_E_INVALID, "ghr_eval_metrics: row must be 8-B aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t N = (size_t)e->W * (size_t)e->H;
+    const uint32_t n_point = ghr::eval_point_groups(e->W, e->H);
+    ghr::EvalArgs a{e->W, e->H, e->renders, e->gt_image, e->gt_mask, e->gt_orient_angle, e->gt_orient_conf, scratch, n_point};
+    const bool vec = !eval_vec_off() && (N & 3) == 0 &&
+                     eval_aligned16({e->renders, e->gt_image, e->gt_mask, e->gt_orient_angle, e->gt_orient_conf});
+    if (vec) hipLaunchKernelGGL(ghr::k_eval_points_v, dim3(n_point), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(ghr::k_eval_points, dim3(n_point), dim3(256), 0, s, a);
+    float* ssim_slots = scratch + (size_t)GHR_EVAL_POINT_TERMS * n_point;
+    uint32_t n_ssim = 0;
+    if (e->with_ssim) {
+        ghr_loss_args l{};
+        l.W = e->W; l.H = e->H; l.image = e->renders; l.gt_image = e->gt_image; l.gt_mask = e->gt_mask;
+        const int seg = loss_march_seg(&l, false);
+        ghr::LossArgs la{e->W, e->H, e->renders, nullptr, nullptr, nullptr, e->gt_image, e->gt_mask, nullptr, nullptr,
+                         0, nullptr, ssim_slots, nullptr, nullptr, seg, 0u};
+        if (loss_vec_ok(&l)) {
+            n_ssim = (uint32_t)ghr::loss_slots_march(e->W, e->H, seg);
+            la.n_slots = n_ssim;
+            hipLaunchKernelGGL(ghr::k_eval_ssim_v, loss_march_grid(&l, seg), dim3(64), 0, s, la);
+        } else {
+            n_ssim = (uint32_t)ghr::loss_slots_tile(e->W, e->H);
+            la.n_slots = n_ssim;
+            hipLaunchKernelGGL(ghr::k_eval_ssim, dim3((e->W + GHR_L_TW - 1) / GHR_L_TW, (e->H + GHR_L_TH - 1) / GHR_L_TH, 3),
+                               dim3(256), 0, s, la);
+        }
+    }
+    hipLaunchKernelGGL(ghr::k_eval_finalize, dim3(1), dim3(256), 0, s, scratch, n_point, ssim_slots, n_ssim, (double)N, row);
+    return finish(s, 0);
+}
+
+int ghr_eval_products(void* stream, int32_t W, int32_t H, const float* renders, uint8_t* bytes, float* conf)
+{
+    if (W <= 0 || H <= 0 || !renders || !bytes || !conf) return fail(GHR_E_INVALID, "ghr_eval_products: bad args");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t N = (size_t)W * (size_t)H, quads = (N + 3) / 4;
+    ghr::ProductArgs a{W, H, renders, bytes, conf};
+    const dim3 grid((unsigned)((quads + 255) / 256));
+    const bool vec = !eval_vec_off() && (N & 3) == 0 && eval_aligned16({renders, conf}) && ((uintptr_t)bytes & 3u) == 0;
+    if (vec) hipLaunchKernelGGL(ghr::k_eval_products, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(ghr::k_eval_products_s, grid, dim3(256), 0, s, a);
     return finish(s, 0);
 }
 

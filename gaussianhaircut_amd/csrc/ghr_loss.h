@@ -153,7 +153,9 @@ __device__ __forceinline__ void block_sum_n(float* v, float (*s_red)[8])
 //      LDS -- 40 % of the window arithmetic
 //   2  computes only those two moments into a.stats_out (no loss terms)
 // The arithmetic of each moment is identical in all variants, so MODE 1 + MODE 2 reproduce MODE 0 bit for bit.
-template <int MODE>
+// EVAL (with MODE 0; ghr_eval.h): the SSIM of clamp(render, 0, 1) against clamp(ground truth, 0, 1) alone -- no mask, the
+// clamp applied where the window is staged, no maps, and one partial sum per slot (a.sums[slot]) instead of five.
+template <int MODE, bool EVAL = false>
 __device__ __forceinline__ void loss_fwd_body(const LossArgs& a)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -185,9 +187,10 @@ __device__ __forceinline__ void loss_fwd_body(const LossArgs& a)
             const int gx = bx + lx - GHR_SSIM_R, gy = by + ly - GHR_SSIM_R;
             const bool in = i < GHR_L_EH * GHR_L_XS && lx < GHR_L_EW && gx >= 0 && gx < W && gy >= 0 && gy < H;
             const size_t p = in ? (size_t)gy * W + gx : 0;
-            vm[it] = in ? (a.mask_colours ? m[p] : 1.0f) : 0.f;
+            vm[it] = in ? ((!EVAL && a.mask_colours) ? m[p] : 1.0f) : 0.f;
             vi[it] = (HAVE_X && in) ? img[p] : 0.f;
             vg[it] = in ? gt[p] : 0.f;
+            if (EVAL) { vi[it] = fminf(fmaxf(vi[it], 0.f), 1.f); vg[it] = fminf(fmaxf(vg[it], 0.f), 1.f); }
         }
 #pragma unroll
         for (int it = 0; it < NIT; it++) {
@@ -275,6 +278,18 @@ __device__ __forceinline__ void loss_fwd_body(const LossArgs& a)
                 a.stats_out[(1 * 3 + ch) * N + p] = acc[o][PYY];
             }
         }
+        return;
+    }
+    if (EVAL) {
+        float sv[1] = {0.f};
+#pragma unroll
+        for (int o = 0; o < 2; o++) {
+            const int gy = by + 2 * tr + o;
+            float d0, d1, d2;
+            if (gx < W && gy < H) sv[0] += ssim_point(acc[o][PX], acc[o][PY], acc[o][PXX], acc[o][PYY], acc[o][PXY], d0, d1, d2);
+        }
+        block_sum_n<1>(sv, s_red);
+        if (tid == 0) a.sums[(size_t)blockIdx.x + (size_t)gridDim.x * (blockIdx.y + (size_t)gridDim.y * blockIdx.z)] = sv[0];
         return;
     }
     const bool orient = ch == 2 && a.dir2d != nullptr;
@@ -593,7 +608,8 @@ __device__ __forceinline__ void keep_last_rows(float (*s_h)[GHR_LM_HR][GHR_LM_HS
 // rather than on one of the first two (which carry the mask term): a template parameter, not a branch, so that the memory
 // operations of a pass are the same sequence on every path -- the waits the compiler derives for the prefetched batch are
 // then exact counts instead of drains.
-template <int MODE, bool CH2>
+// EVAL: as in loss_fwd_body (instantiated with MODE 0, CH2 false for all three channels: no channel carries another term).
+template <int MODE, bool CH2, bool EVAL = false>
 __device__ __forceinline__ void loss_fwd_march(const LossArgs& a, float (*s_x)[GHR_LM_WS], float (*s_y)[GHR_LM_WS],
                                                float (*s_h)[GHR_LM_HR][GHR_LM_HS])
 {
@@ -615,7 +631,7 @@ __device__ __forceinline__ void loss_fwd_march(const LossArgs& a, float (*s_x)[G
     const float* img = a.image + (size_t)ch * N;
     const float* gt = a.gt_image + (size_t)ch * N;
     const float* m = a.gt_mask + N;  // gt_mask[1]
-    const bool masked = a.mask_colours != 0;  // uniform
+    const bool masked = !EVAL && a.mask_colours != 0;  // uniform
 
     float sums[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  // |image-gt|*m, ssim, |mask-gt_mask|, orientation num, den
     // input rows r0 .. r0 + nvec / 12 - 1 -> rows 0.. of s_x (render x mask) and s_y (ground truth x mask), in two halves:
@@ -640,7 +656,10 @@ __device__ __forceinline__ void loss_fwd_march(const LossArgs& a, float (*s_x)[G
         for (int it = 0; it < 2; it++) {
             const f4 mm = sel4(wp[it].in, vm[it]);
             f4 x = {0.f, 0.f, 0.f, 0.f};
-            if (HAVE_X) {
+            if (HAVE_X && EVAL) {
+                x = sel4(wp[it].in, vi[it]);
+                x = f4{fminf(fmaxf(x.x, 0.f), 1.f), fminf(fmaxf(x.y, 0.f), 1.f), fminf(fmaxf(x.z, 0.f), 1.f), fminf(fmaxf(x.w, 0.f), 1.f)};
+            } else if (HAVE_X) {
                 x = sel4(wp[it].in, vi[it]);
                 const int gy = r0 + wp[it].row;
                 const bool own = wp[it].in && wp[it].q >= 2 && wp[it].q < 2 + GHR_LM_TW / 4 && gy >= y0 && gy < y1;
@@ -650,7 +669,8 @@ __device__ __forceinline__ void loss_fwd_march(const LossArgs& a, float (*s_x)[G
                 x = f4{x.x * mm.x, x.y * mm.y, x.z * mm.z, x.w * mm.w};
             }
             f4 g = sel4(wp[it].in, vg[it]);
-            g = f4{g.x * mm.x, g.y * mm.y, g.z * mm.z, g.w * mm.w};
+            if (EVAL) g = f4{fminf(fmaxf(g.x, 0.f), 1.f), fminf(fmaxf(g.y, 0.f), 1.f), fminf(fmaxf(g.z, 0.f), 1.f), fminf(fmaxf(g.w, 0.f), 1.f)};
+            else g = f4{g.x * mm.x, g.y * mm.y, g.z * mm.z, g.w * mm.w};
             if (HAVE_X) touch4(x);
             touch4(g);
             if (lane + 64 * it < nvec) {
@@ -700,7 +720,7 @@ __device__ __forceinline__ void loss_fwd_march(const LossArgs& a, float (*s_x)[G
 
     const int tx = lane & 31, rg = lane >> 5;
     const int gx = bx + tx;
-    const bool orient = MODE != 2 && CH2 && a.dir2d != nullptr;  // uniform
+    const bool orient = MODE != 2 && CH2 && !EVAL && a.dir2d != nullptr;  // uniform
     // The loop is rotated so that a batch is committed at the END of the pass before it, in straight-line code behind the
     // pass's stores: the wait for its loads then is an exact count (vmcnt = the stores issued since) instead of a drain of
     // every outstanding store at the top of each pass (which is what the counter arithmetic at a loop header amounts to).
@@ -739,7 +759,7 @@ __device__ __forceinline__ void loss_fwd_march(const LossArgs& a, float (*s_x)[G
                     l_mu2[o] = ldb<float>(a.gt_stats + (size_t)(0 * 3 + ch) * N, p4[o]);
                     l_e22[o] = ldb<float>(a.gt_stats + (size_t)(1 * 3 + ch) * N, p4[o]);
                 }
-                if (!CH2) {
+                if (!CH2 && !EVAL) {
                     l_mk[o] = ldb<float>(a.mask + (size_t)ch * N, p4[o]);
                     l_gmk[o] = ldb<float>(a.gt_mask + (size_t)ch * N, p4[o]);
                 }
@@ -765,7 +785,7 @@ __device__ __forceinline__ void loss_fwd_march(const LossArgs& a, float (*s_x)[G
                 const float e22 = MODE == 1 ? l_e22[o] : acc[o][PYY];
                 const float sv = ssim_point(acc[o][PX], mu2, acc[o][PXX], e22, acc[o][PXY], d0[o], d1[o], d2[o]);
                 sums[1] += ok[o] ? sv : 0.f;
-                if (!CH2) sums[2] += ok[o] ? fabsf(l_mk[o] - l_gmk[o]) : 0.f;
+                if (!CH2 && !EVAL) sums[2] += ok[o] ? fabsf(l_mk[o] - l_gmk[o]) : 0.f;
             }
             if (CH2 && orient) {  // the waves of the third colour channel also carry the orientation term (before the stores:
                                   // waiting for its loads then does not wait for them)
@@ -786,7 +806,7 @@ __device__ __forceinline__ void loss_fwd_march(const LossArgs& a, float (*s_x)[G
             for (int k = 0; k < 5; k++) touch(sums[k]);
 #pragma unroll
             for (int o = 0; o < 4; o++) {
-                if (ok[o]) {
+                if (!EVAL && ok[o]) {
                     stb<float>(a.maps + (size_t)(0 * 3 + ch) * N, p4[o], d0[o]);
                     stb<float>(a.maps + (size_t)(1 * 3 + ch) * N, p4[o], d1[o]);
                     stb<float>(a.maps + (size_t)(2 * 3 + ch) * N, p4[o], d2[o]);
@@ -798,6 +818,11 @@ __device__ __forceinline__ void loss_fwd_march(const LossArgs& a, float (*s_x)[G
         commit(more ? GHR_LM_ROWS * GHR_LM_WQ : 0, yb + GHR_LM_ROWS + GHR_SSIM_R);
     }
     if (MODE == 2) return;
+    if (EVAL) {
+        const float sv = wave_sum(sums[1]);
+        if (lane == 0) a.sums[(size_t)sx + (size_t)nst * (blockIdx.y + (size_t)gridDim.y * (unsigned)ch)] = sv;
+        return;
+    }
 #pragma unroll
     for (int k = 0; k < 5; k++) sums[k] = wave_sum(sums[k]);
     if (lane == 0) {  // this wave's slot: strip sx (< nst: the grid's padding strips have returned), segment, channel
@@ -809,14 +834,15 @@ __device__ __forceinline__ void loss_fwd_march(const LossArgs& a, float (*s_x)[G
 }
 
 // grid (8 ceil(ceil(W/32) / 8), ceil(H/seg), 3 colour channels), block 64: one wave per strip segment
-template <int MODE>
+template <int MODE, bool EVAL = false>
 __device__ __forceinline__ void loss_fwd_march_any(const LossArgs& a)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int NM = MODE == 0 ? 5 : (MODE == 1 ? 3 : 2);
     __shared__ __attribute__((aligned(16))) float s_x[GHR_LM_SR][GHR_LM_WS], s_y[GHR_LM_SR][GHR_LM_WS];
     __shared__ __attribute__((aligned(16))) float s_h[NM][GHR_LM_HR][GHR_LM_HS];
-    if (blockIdx.z == 2) loss_fwd_march<MODE, true>(a, s_x, s_y, s_h);
+    if (EVAL) loss_fwd_march<MODE, false, true>(a, s_x, s_y, s_h);
+    else if (blockIdx.z == 2) loss_fwd_march<MODE, true>(a, s_x, s_y, s_h);
     else loss_fwd_march<MODE, false>(a, s_x, s_y, s_h);
 #endif
 }

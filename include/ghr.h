@@ -404,6 +404,34 @@ int ghr_loss_backward(void* stream, const ghr_loss_args* a, const float* maps, c
                       const float* grad_loss, float* d_image, float* d_mask, float* d_dir2d, float* d_orient_conf,
                       float* zero_plane_a, float* zero_plane_b);
 
+/* ---- evaluation pass (src/train_gaussians.py:232-293 training_report; src/metrics.py:71-78; src/render_gaussians.py:31-68) ----
+ * Metrics of one view on the packed [10,H,W] rasterizer output `renders` (channels: rgb 0-2, mask 3-4, dir2d 5-6, orientation
+ * confidence 8) against gt_image [3,H,W], gt_mask [2,H,W], gt_orient_angle [1,H,W], gt_orient_conf [1,H,W]; all terms on
+ * clamp(x, 0, 1) of render, mask, orientation angle and their ground truths, as training_report forms them.  gt_orient_angle
+ * and gt_orient_conf both NULL: no orientation terms (their two sums are 0). */
+typedef struct ghr_eval_args {
+    int32_t W, H;
+    const float* renders;
+    const float* gt_image;
+    const float* gt_mask;
+    const float* gt_orient_angle;
+    const float* gt_orient_conf;
+    int32_t with_ssim;            /* 0: the SSIM kernel is not launched and the row's ssim is 0 */
+} ghr_eval_args;
+#define GHR_EVAL_TERMS 8
+/* Floats of device scratch for one view's partial sums (one slot per workgroup, plain stores: nothing to initialise). */
+size_t ghr_eval_scratch_floats(int32_t W, int32_t H);
+/* row: GHR_EVAL_TERMS device doubles of a caller-owned table, written by the last of the (at most three) launches:
+ *   {l1 = mean |dimage|, ce = mean |dmask|, or_num = sum min(|d|, |d-1|, |d+1|) pi gt_mask[0] w, or_den = sum w (w = gt_orient_conf,
+ *    unclamped), mse[3] = mean dimage^2 per channel, ssim = mean of the 11x11 Gaussian-window SSIM map}.
+ * The slots are folded in a fixed order in double: the same bits run after run.  Nothing is read back. */
+int ghr_eval_metrics(void* stream, const ghr_eval_args* a, float* scratch, double* row);
+/* The seven products of render_set in one launch.  bytes: 12*H*W device bytes
+ *   [render HWC3 | hair mask HW | head mask HW | orient_angle * hair HW | vis_orient(angle, hair) HWC3 |
+ *    vis_orient(angle, 1 - 1 / (orient_conf * hair + 1)) HWC3], quantised as torchvision's save_image does
+ *   (floor(clamp(255 v + 0.5, 0, 255))); conf: H*W device floats = orient_conf * hair (the reference's .pth product). */
+int ghr_eval_products(void* stream, int32_t W, int32_t H, const float* renders, uint8_t* bytes, float* conf);
+
 /* ---- fused Adam (src/scene/gaussian_model.py:431-444; src/train_gaussians.py:174-181) ---------------------------
  * One pass over flat buffers p/g/m/v of n floats split into n_groups contiguous groups (group_end[i] = exclusive end
  * offset, lr[i] = its learning rate; host arrays).  state: GHR_ADAM_STATE (18) device ints {step, nan_flag, steps each
