@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GHR_LIB_PATH") or os.path.join(CSRC, "libghr_hip.so")  # override: kernel experiments
 SOURCES = ["ghr_capi.hip"]
 HEADERS = ["ghr_device.h", "ghr_preprocess.h", "ghr_binning.h", "ghr_render_fwd.h", "ghr_render_bwd.h", "ghr_render_bwd2.h", "ghr_render_bwd3.h",
-           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h"]
+           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_orient.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-fPIC",
                "-shared"]
 
@@ -152,7 +152,8 @@ EXPORTS = ["ghr_last_error", "ghr_abi_version", "ghr_forward_sizes", "ghr_binnin
            "ghr_adam_step_range", "ghr_adam_step_range_to", "ghr_adam_nan_scan", "ghr_adam_relay_rows", "ghr_adam_fused_finish",
            "ghr_knn_workspace_size", "ghr_knn_keys", "ghr_knn_mean_dist2",
            "ghr_camera_compose", "ghr_camera_compose_backward", "ghr_camera_adam_step",
-           "ghr_eval_scratch_floats", "ghr_eval_metrics", "ghr_eval_products"]
+           "ghr_eval_scratch_floats", "ghr_eval_metrics", "ghr_eval_products",
+           "ghr_orient_dog_scratch_bytes", "ghr_orient_dog", "ghr_orient_bank_floats", "ghr_orient_gabor"]
 
 _lib = None
 
@@ -224,12 +225,17 @@ def lib() -> ctypes.CDLL:
     L.ghr_eval_scratch_floats.argtypes = [i32, i32]
     L.ghr_eval_metrics.argtypes = [vp, ctypes.POINTER(EvalArgs), vp, vp]
     L.ghr_eval_products.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.ghr_orient_dog_scratch_bytes.argtypes = [i32, i32]
+    L.ghr_orient_dog.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp]
+    L.ghr_orient_bank_floats.argtypes = [i32, i32]
+    L.ghr_orient_gabor.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32]
     L.ghr_ws_inspect.argtypes = [i32, i32, i32, i32, u32, vp, vp, vp, ctypes.POINTER(WsView)]
     for name in EXPORTS:
         fn = getattr(L, name)
-        if name not in ("ghr_last_error", "ghr_eval_scratch_floats"):
+        if name not in ("ghr_last_error", "ghr_eval_scratch_floats", "ghr_orient_dog_scratch_bytes", "ghr_orient_bank_floats"):
             fn.restype = ctypes.c_int
-    L.ghr_eval_scratch_floats.restype = ctypes.c_size_t
+    for name in ("ghr_eval_scratch_floats", "ghr_orient_dog_scratch_bytes", "ghr_orient_bank_floats"):
+        getattr(L, name).restype = ctypes.c_size_t
     _lib = L
     return L
 

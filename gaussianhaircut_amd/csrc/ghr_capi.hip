@@ -20,6 +20,7 @@
 #include "ghr_knn.h"
 #include "ghr_loss.h"
 #include "ghr_eval.h"
+#include "ghr_orient.h"
 #include "ghr_preprocess.h"
 #include "ghr_project.h"
 #include "ghr_render_bwd.h"
@@ -984,6 +985,57 @@ int ghr_eval_products(void* stream, int32_t W, int32_t H, const float* renders, 
     const bool vec = !eval_vec_off() && (N & 3) == 0 && eval_aligned16({renders, conf}) && ((uintptr_t)bytes & 3u) == 0;
     if (vec) hipLaunchKernelGGL(ghr::k_eval_products, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(ghr::k_eval_products_s, grid, dim3(256), 0, s, a);
+    return finish(s, 0);
+}
+
+// ---- orientation maps (ghr_orient.h) ---------------------------------------------------------------------------------
+size_t ghr_orient_dog_scratch_bytes(int32_t W, int32_t H)
+{
+    if (W <= 0 || H <= 0) return 0;
+    return 2 * sizeof(double) * (size_t)W * (size_t)H;
+}
+
+int ghr_orient_dog(void* stream, int32_t W, int32_t H, int32_t channels, int32_t is_u8, const void* image, int32_t r_low,
+                   const double* w_low, int32_t r_high, const double* w_high, void* scratch, float* filtered)
+{
+    if (W < 1 || H < 1) return fail(GHR_E_INVALID, "ghr_orient_dog: W and H must be >= 1");
+    if (channels != 1 && channels != 3) return fail(GHR_E_INVALID, "ghr_orient_dog: channels must be 1 or 3");
+    if (r_low < 0 || r_high < 0) return fail(GHR_E_INVALID, "ghr_orient_dog: negative radius");
+    if (!image || !w_low || !w_high || !scratch || !filtered) return fail(GHR_E_INVALID, "ghr_orient_dog: NULL buffer");
+    if (((uintptr_t)scratch & 7u) != 0) return fail(GHR_E_INVALID, "ghr_orient_dog: scratch must be 8-B aligned");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::OrientDogArgs a{W, H, channels, is_u8 != 0, image, r_low, r_high, w_low, w_high, (double*)scratch, filtered};
+    const dim3 grid((W + 63) / 64, (H + 3) / 4);
+    hipLaunchKernelGGL(ghr::k_orient_dog<0>, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_orient_dog<1>, grid, dim3(256), 0, s, a);
+    return finish(s, 0);
+}
+
+static int orient_tiles_per_wave(int32_t n_filters) { return ((n_filters + 15) / 16 + GHR_ORIENT_WAVES - 1) / GHR_ORIENT_WAVES; }
+
+size_t ghr_orient_bank_floats(int32_t n_filters, int32_t ksize)
+{
+    if (n_filters < 1 || n_filters > GHR_ORIENT_MAX_FILTERS || ksize < 1 || ksize > GHR_ORIENT_MAX_KSIZE || !(ksize & 1)) return 0;
+    return (size_t)GHR_ORIENT_WAVES * orient_tiles_per_wave(n_filters) * ((ksize * ksize + 3) / 4) * 64;
+}
+
+int ghr_orient_gabor(void* stream, int32_t W, int32_t H, const float* filtered, int32_t n_filters, int32_t ksize,
+                     const float* weights, const float* thetas, uint8_t* deg, float* var, float* angle, float* conf,
+                     int32_t via_half)
+{
+    if (W < 1 || H < 1) return fail(GHR_E_INVALID, "ghr_orient_gabor: W and H must be >= 1");
+    if (n_filters < 1 || n_filters > GHR_ORIENT_MAX_FILTERS) return fail(GHR_E_INVALID, "ghr_orient_gabor: n_filters must be 1 ... 256");
+    if (ksize < 1 || ksize > GHR_ORIENT_MAX_KSIZE || !(ksize & 1)) return fail(GHR_E_INVALID, "ghr_orient_gabor: ksize must be odd and <= 25");
+    if (!filtered || !weights || !thetas) return fail(GHR_E_INVALID, "ghr_orient_gabor: NULL buffer");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::OrientGaborArgs a{W, H, filtered, n_filters, ksize, (ksize * ksize + 3) / 4, weights, thetas, deg, var, angle, conf, via_half != 0};
+    const dim3 grid((W + GHR_ORIENT_TW - 1) / GHR_ORIENT_TW, (H + GHR_ORIENT_TH - 1) / GHR_ORIENT_TH), block(64 * GHR_ORIENT_WAVES);
+    switch (orient_tiles_per_wave(n_filters)) {
+    case 1: hipLaunchKernelGGL(ghr::k_orient_gabor<1>, grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL(ghr::k_orient_gabor<2>, grid, block, 0, s, a); break;
+    case 3: hipLaunchKernelGGL(ghr::k_orient_gabor<3>, grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL(ghr::k_orient_gabor<4>, grid, block, 0, s, a);
+    }
     return finish(s, 0);
 }
 

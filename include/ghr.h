@@ -568,6 +568,28 @@ int ghr_camera_adam_step(void* stream, int32_t parametrisation, int32_t n, float
                          float* exp_avg_sq, int32_t stride, int32_t* steps, int32_t* touched, float lr_rotation,
                          float lr_translation, float lr_fov, double beta1, double beta2, float eps, int32_t train_mask);
 
+/* ---- ground-truth orientation maps from an image (src/preprocessing/calc_orientation_maps.py; loader: src/utils/camera_utils.py:66-68)
+ * Added without an ABI_VERSION bump: five new functions, no existing struct or signature changed.
+ * ghr_orient_dog: rgb2gray (0.2989 r + 0.5870 g + 0.1140 b; one channel: the value itself) and the difference of two Gaussians,
+ * both in double with indices clamped at the border (scipy.ndimage's mode 'nearest'), axis 0 then axis 1, narrowed to float32.
+ *   image [H][W][channels] (channels 1 or 3), uint8 (is_u8) or float32, device; w_low [2 r_low + 1] / w_high [2 r_high + 1]:
+ *   symmetric double taps on the DEVICE; scratch: ghr_orient_dog_scratch_bytes(W, H) bytes, 8-B aligned; filtered [H][W] f32.
+ * ghr_orient_gabor: cross-correlation of the zero-padded plane with n_filters (1 ... 256) filters of ksize x ksize (odd, <= 25)
+ * taps, F_k = |response_k|, deg = the FIRST arg-max, var = sum_k d_k^2 F_k / max(sum_k F_k, 1e-12) with d_k the distance of
+ * deg / n_filters * pi and thetas[k] on the circle of circumference pi; angle = deg / 180, conf = 1 / ((v / pi^2)^2 + 1e-7) with
+ * v = var, or var rounded through float16 when via_half.  deg (uint8), var, angle, conf [H][W]: each may be NULL.
+ *   weights: ghr_orient_bank_floats(n_filters, ksize) floats in the order the matrix unit reads them,
+ *   [tile][chunk][lane 0 .. 63] = w[filter 16 tile + (lane & 15)][tap 4 chunk + (lane >> 4)] (tap = row * ksize + column), zero where
+ *   the filter or the tap does not exist; tile < 4 ceil(ceil(n_filters / 16) / 4), chunk < ceil(ksize^2 / 4).
+ * Finite input is the caller's check.  The same input gives the same bytes on every run.  A refused call launches nothing. */
+size_t ghr_orient_dog_scratch_bytes(int32_t W, int32_t H);
+int ghr_orient_dog(void* stream, int32_t W, int32_t H, int32_t channels, int32_t is_u8, const void* image, int32_t r_low,
+                   const double* w_low, int32_t r_high, const double* w_high, void* scratch, float* filtered);
+size_t ghr_orient_bank_floats(int32_t n_filters, int32_t ksize);
+int ghr_orient_gabor(void* stream, int32_t W, int32_t H, const float* filtered, int32_t n_filters, int32_t ksize,
+                     const float* weights, const float* thetas, uint8_t* deg, float* var, float* angle, float* conf,
+                     int32_t via_half);
+
 /* Introspection for tests (device pointers into the workspaces; layout is otherwise private). */
 typedef struct ghr_ws_view {
     const float* rec;          /* [P][16]: x, y, conic a, b, c, opacity, features[10] */
