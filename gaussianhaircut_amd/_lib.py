@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GHR_LIB_PATH") or os.path.join(CSRC, "libghr_hip.so")  # override: kernel experiments
 SOURCES = ["ghr_capi.hip"]
 HEADERS = ["ghr_device.h", "ghr_preprocess.h", "ghr_binning.h", "ghr_render_fwd.h", "ghr_render_bwd.h", "ghr_render_bwd2.h", "ghr_render_bwd3.h",
-           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_orient.h"]
+           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_orient.h", "ghr_gt.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-fPIC",
                "-shared"]
 
@@ -153,7 +153,8 @@ EXPORTS = ["ghr_last_error", "ghr_abi_version", "ghr_forward_sizes", "ghr_binnin
            "ghr_knn_workspace_size", "ghr_knn_keys", "ghr_knn_mean_dist2",
            "ghr_camera_compose", "ghr_camera_compose_backward", "ghr_camera_adam_step",
            "ghr_eval_scratch_floats", "ghr_eval_metrics", "ghr_eval_products",
-           "ghr_orient_dog_scratch_bytes", "ghr_orient_dog", "ghr_orient_bank_floats", "ghr_orient_gabor"]
+           "ghr_orient_dog_scratch_bytes", "ghr_orient_dog", "ghr_orient_bank_floats", "ghr_orient_gabor",
+           "ghr_resample_scratch_bytes", "ghr_resample_u8", "ghr_gt_assemble", "ghr_gt_resize_variance"]
 
 _lib = None
 
@@ -229,12 +230,17 @@ def lib() -> ctypes.CDLL:
     L.ghr_orient_dog.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp]
     L.ghr_orient_bank_floats.argtypes = [i32, i32]
     L.ghr_orient_gabor.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32]
+    L.ghr_resample_scratch_bytes.argtypes = [i32] * 5
+    L.ghr_resample_u8.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp]
+    L.ghr_gt_assemble.argtypes = [vp, i32, i32] + [vp] * 5 + [i32, i32, vp, vp, i32, i32, i32] + [vp] * 4
+    L.ghr_gt_resize_variance.argtypes = [vp, i32, i32, vp, i32, i32, i32, vp]
     L.ghr_ws_inspect.argtypes = [i32, i32, i32, i32, u32, vp, vp, vp, ctypes.POINTER(WsView)]
     for name in EXPORTS:
         fn = getattr(L, name)
-        if name not in ("ghr_last_error", "ghr_eval_scratch_floats", "ghr_orient_dog_scratch_bytes", "ghr_orient_bank_floats"):
+        if name not in ("ghr_last_error", "ghr_eval_scratch_floats", "ghr_orient_dog_scratch_bytes", "ghr_orient_bank_floats",
+                        "ghr_resample_scratch_bytes"):
             fn.restype = ctypes.c_int
-    for name in ("ghr_eval_scratch_floats", "ghr_orient_dog_scratch_bytes", "ghr_orient_bank_floats"):
+    for name in ("ghr_eval_scratch_floats", "ghr_orient_dog_scratch_bytes", "ghr_orient_bank_floats", "ghr_resample_scratch_bytes"):
         getattr(L, name).restype = ctypes.c_size_t
     _lib = L
     return L

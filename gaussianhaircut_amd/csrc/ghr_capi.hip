@@ -21,6 +21,7 @@
 #include "ghr_loss.h"
 #include "ghr_eval.h"
 #include "ghr_orient.h"
+#include "ghr_gt.h"
 #include "ghr_preprocess.h"
 #include "ghr_project.h"
 #include "ghr_render_bwd.h"
@@ -1036,6 +1037,133 @@ int ghr_orient_gabor(void* stream, int32_t W, int32_t H, const float* filtered, 
     case 3: hipLaunchKernelGGL(ghr::k_orient_gabor<3>, grid, block, 0, s, a); break;
     default: hipLaunchKernelGGL(ghr::k_orient_gabor<4>, grid, block, 0, s, a);
     }
+    return finish(s, 0);
+}
+
+// ---- ground-truth loader (ghr_gt.h) ------------------------------------------------------------------------------------
+size_t ghr_resample_scratch_bytes(int32_t in_w, int32_t in_h, int32_t out_w, int32_t out_h, int32_t channels)
+{
+    if (in_w < 1 || in_h < 1 || out_w < 1 || out_h < 1 || (channels != 1 && channels != 3)) return 0;
+    if (in_w == out_w || in_h == out_h) return 0;   // one pass or none: no intermediate
+    return (size_t)in_h * (size_t)out_w * (size_t)channels;
+}
+
+namespace {
+// The bounds live on the device and decide which bytes a kernel reads: they are read back on the caller's stream (eight bytes
+// per output row or column) and checked before anything is launched.
+int resample_check_bounds(hipStream_t s, const char* axis, const int32_t* bounds, int32_t n_out, int32_t ksize, int32_t n_in,
+                          int32_t channels, bool* staged)
+{
+    std::vector<int32_t> h((size_t)n_out * 2);
+    GHR_HIP(hipMemcpyAsync(h.data(), bounds, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    GHR_HIP(hipStreamSynchronize(s));
+    for (int32_t i = 0; i < n_out; i++) {
+        const int32_t lo = h[2 * i], n = h[2 * i + 1];
+        if (lo < 0 || n < 0 || n > ksize || lo > n_in - n) {
+            std::snprintf(g_err, sizeof(g_err), "ghr_resample_u8: bounds_%s[%d] = (%d, %d) does not fit ksize %d and an input of %d",
+                          axis, i, lo, n, ksize, n_in);
+            return GHR_E_INVALID;
+        }
+    }
+    // k_resample_u8_h_lds stages the bytes between a workgroup's first window's start and its last window's end: every window
+    // of the workgroup has to lie in between, and the span and the taps have to fit its LDS
+    // Measured at 2160 x 3840 (profiles/ground_truth_loader.txt): with three channels the staged form is twice as fast as the direct
+    // one (33 against 64 us at 11 taps); with one channel it wins at 19 taps (17 against 29 us) and loses at 11 (37 against 24 us),
+    // where a workgroup's coefficients are more bytes than its pixels.
+    *staged = ksize <= GHR_RESAMPLE_HK && (channels == 3 || ksize > 11);
+    for (int32_t f = 0; f < n_out && *staged; f += GHR_RESAMPLE_HC) {
+        const int32_t l = std::min(f + GHR_RESAMPLE_HC, n_out) - 1;
+        const int32_t x0 = h[2 * f], x1 = h[2 * l] + h[2 * l + 1];
+        if ((int64_t)(x1 - x0) * channels > GHR_RESAMPLE_SPAN) *staged = false;
+        for (int32_t i = f; i <= l && *staged; i++)
+            if (h[2 * i] < x0 || h[2 * i] + h[2 * i + 1] > x1) *staged = false;
+    }
+    return GHR_OK;
+}
+}  // namespace
+
+int ghr_resample_u8(void* stream, int32_t in_w, int32_t in_h, int32_t channels, const uint8_t* in, int32_t out_w, int32_t out_h,
+                    uint8_t* out, const int32_t* bounds_x, const int32_t* coef_x, int32_t ksize_x, const int32_t* bounds_y,
+                    const int32_t* coef_y, int32_t ksize_y, void* scratch)
+{
+    if (in_w < 1 || in_h < 1 || out_w < 1 || out_h < 1) return fail(GHR_E_INVALID, "ghr_resample_u8: sizes must be >= 1");
+    if (channels != 1 && channels != 3) return fail(GHR_E_INVALID, "ghr_resample_u8: channels must be 1 or 3 (RGBA is not built)");
+    if (!in || !out) return fail(GHR_E_INVALID, "ghr_resample_u8: NULL image");
+    if (in_h > 4 * 65535 || ((size_t)out_w * channels + 1023) / 1024 > 65535)
+        return fail(GHR_E_INVALID, "ghr_resample_u8: image too large for the launch grid");
+    const bool hor = in_w != out_w, ver = in_h != out_h;
+    if (hor && (!bounds_x || !coef_x || ksize_x < 1))
+        return fail(GHR_E_INVALID, "ghr_resample_u8: the widths differ: bounds_x, coef_x and ksize_x >= 1 are needed");
+    if (ver && (!bounds_y || !coef_y || ksize_y < 1))
+        return fail(GHR_E_INVALID, "ghr_resample_u8: the heights differ: bounds_y, coef_y and ksize_y >= 1 are needed");
+    if (hor && ver && !scratch) return fail(GHR_E_INVALID, "ghr_resample_u8: two passes need ghr_resample_scratch_bytes of scratch");
+    if ((hor || ver) && in == out) return fail(GHR_E_INVALID, "ghr_resample_u8: in and out must not be the same buffer");
+    hipStream_t s = (hipStream_t)stream;
+    if (!hor && !ver) {   // Pillow returns a copy
+        if (in != out) GHR_HIP(hipMemcpyAsync(out, in, (size_t)in_w * in_h * channels, hipMemcpyDeviceToDevice, s));
+        return GHR_OK;
+    }
+    bool staged = false, unused = false;
+    if (hor)
+        if (int rc = resample_check_bounds(s, "x", bounds_x, out_w, ksize_x, in_w, channels, &staged)) return rc;
+    if (ver)
+        if (int rc = resample_check_bounds(s, "y", bounds_y, out_h, ksize_y, in_h, channels, &unused)) return rc;
+    const uint8_t* mid = in;
+    if (hor) {
+        uint8_t* dst = ver ? (uint8_t*)scratch : out;
+        ghr::ResampleArgs a{in_w, in_h, out_w, in_h, channels, in, dst, bounds_x, coef_x, ksize_x};
+        if (staged) {
+            const dim3 grid((out_w + GHR_RESAMPLE_HC - 1) / GHR_RESAMPLE_HC, (in_h + GHR_RESAMPLE_HR - 1) / GHR_RESAMPLE_HR);
+            if (channels == 3) hipLaunchKernelGGL(ghr::k_resample_u8_h_lds<3>, grid, dim3(256), 0, s, a);
+            else hipLaunchKernelGGL(ghr::k_resample_u8_h_lds<1>, grid, dim3(256), 0, s, a);
+        } else {
+            const dim3 grid((out_w + 63) / 64, (in_h + 3) / 4);
+            if (channels == 3) hipLaunchKernelGGL(ghr::k_resample_u8_h<3>, grid, dim3(256), 0, s, a);
+            else hipLaunchKernelGGL(ghr::k_resample_u8_h<1>, grid, dim3(256), 0, s, a);
+        }
+        mid = dst;
+    }
+    if (ver) {
+        ghr::ResampleArgs a{out_w, in_h, out_w, out_h, channels, mid, out, bounds_y, coef_y, ksize_y};
+        const size_t row = (size_t)out_w * channels;
+        const dim3 grid(out_h, (unsigned)((row + 1023) / 1024));
+        const bool vec = (row & 3) == 0 && ((uintptr_t)mid & 3u) == 0 && ((uintptr_t)out & 3u) == 0;
+        if (vec) hipLaunchKernelGGL(ghr::k_resample_u8_v<true>, grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(ghr::k_resample_u8_v<false>, grid, dim3(256), 0, s, a);
+    }
+    return finish(s, 0);
+}
+
+int ghr_gt_assemble(void* stream, int32_t W, int32_t H, const uint8_t* image, const uint8_t* mask_hair, const uint8_t* mask_body,
+                    const uint8_t* angle, const float* var, int32_t var_w, int32_t var_h, const float* div255_table,
+                    const float* div180_table, int32_t white_background, int32_t binarize, int32_t via_half, float* out_image,
+                    float* out_mask, float* out_angle, float* out_conf)
+{
+    if (W < 1 || H < 1) return fail(GHR_E_INVALID, "ghr_gt_assemble: W and H must be >= 1");
+    if (!image || !mask_hair || !mask_body || !div255_table || !out_image || !out_mask)
+        return fail(GHR_E_INVALID, "ghr_gt_assemble: NULL buffer");
+    if ((angle == nullptr) != (out_angle == nullptr)) return fail(GHR_E_INVALID, "ghr_gt_assemble: angle and out_angle come together");
+    if ((var == nullptr) != (out_conf == nullptr)) return fail(GHR_E_INVALID, "ghr_gt_assemble: var and out_conf come together");
+    if (angle && !div180_table) return fail(GHR_E_INVALID, "ghr_gt_assemble: angle needs div180_table");
+    if (var && (var_w < 1 || var_h < 1)) return fail(GHR_E_INVALID, "ghr_gt_assemble: var_w and var_h must be >= 1");
+    if (white_background != 0 && white_background != 1) return fail(GHR_E_INVALID, "ghr_gt_assemble: white_background must be 0 or 1");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::GtAssembleArgs a{W, H, image, mask_hair, mask_body, angle, var, var_w, var_h, div255_table, div180_table, white_background,
+                          binarize != 0, via_half != 0, out_image, out_mask, out_angle, out_conf};
+    const size_t N = (size_t)W * H;
+    hipLaunchKernelGGL(ghr::k_gt_assemble, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, a);
+    return finish(s, 0);
+}
+
+int ghr_gt_resize_variance(void* stream, int32_t W, int32_t H, const float* var, int32_t var_w, int32_t var_h, int32_t via_half,
+                           float* out)
+{
+    if (W < 1 || H < 1 || var_w < 1 || var_h < 1) return fail(GHR_E_INVALID, "ghr_gt_resize_variance: sizes must be >= 1");
+    if (!var || !out) return fail(GHR_E_INVALID, "ghr_gt_resize_variance: NULL buffer");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t N = (size_t)W * H;
+    hipLaunchKernelGGL(ghr::k_gt_resize_var, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, W, H, var, var_w, var_h,
+                       (int)(via_half != 0), out);
     return finish(s, 0);
 }
 

@@ -590,6 +590,36 @@ int ghr_orient_gabor(void* stream, int32_t W, int32_t H, const float* filtered, 
                      const float* weights, const float* thetas, uint8_t* deg, float* var, float* angle, float* conf,
                      int32_t via_half);
 
+/* ---- ground-truth loader (src/preprocessing/resize_images.py:101-106; src/utils/camera_utils.py:29-84; src/scene/cameras.py:51-64)
+ * Added without an ABI_VERSION bump: four new functions, no existing struct or signature changed.
+ * ghr_resample_u8: Pillow's 8-bit resampling (ImagingResample, any filter the coefficients describe; the loader uses bicubic)
+ * of in [in_h][in_w][channels] (channels 1 or 3, interleaved) to out [out_h][out_w][channels], bit for bit: the horizontal pass
+ * first and only if the widths differ, the vertical pass second and only if the heights differ, the intermediate
+ * [in_h][out_w][channels] clipped to uint8 in `scratch` (ghr_resample_scratch_bytes; needed only when both passes run); equal
+ * sizes: a device-to-device copy on the stream and no launch.  Per output index i of an axis: bounds[2 i] = the first source
+ * index, bounds[2 i + 1] = n taps, coef[i * ksize + 0 .. n) = the weights with 22 fractional bits as Pillow's
+ * precompute_coeffs / normalize_coeffs_8bpc give them; out = clip(((1 << 21) + sum in * coef) >> 22, 0, 255) in 32-bit integers.
+ * bounds and coef live on the DEVICE; the bounds are read back on the stream (which is synchronised once per pass) and a pair
+ * with n > ksize or first + n > the input's size refuses the call.  in and out must not overlap.
+ * ghr_gt_assemble: one launch for a view's tensors at W x H from the resized bytes: out_image [3][H][W] = (image / 255) * body +
+ * white_background * (1 - body); out_mask [2][H][W] = hair, body as m / 255, or (m >= 128) when binarize; out_angle [1][H][W] =
+ * clamp(angle / 180, 0, 1); out_conf [1][H][W] = 1 / ((v / pi^2)^2 + 1e-7), v = the variance map var [var_h][var_w] (rounded
+ * through float16 first when via_half) sampled as F.interpolate(mode='bilinear', align_corners=False) samples it, in float32:
+ * src = max(scale (dst + 0.5) - 0.5, 0), hy (hx a + lx b) + ly (hx c + lx d); at equal sizes the map's own value.
+ * div255_table / div180_table: 256 device floats i / 255 and i / 180 divided on the host.  (angle, out_angle) and (var, out_conf)
+ * may be NULL together.  ghr_gt_resize_variance: that bilinear sample alone, out [H][W].
+ * The same input gives the same bytes on every run.  A refused call launches nothing. */
+size_t ghr_resample_scratch_bytes(int32_t in_w, int32_t in_h, int32_t out_w, int32_t out_h, int32_t channels);
+int ghr_resample_u8(void* stream, int32_t in_w, int32_t in_h, int32_t channels, const uint8_t* in, int32_t out_w, int32_t out_h,
+                    uint8_t* out, const int32_t* bounds_x, const int32_t* coef_x, int32_t ksize_x, const int32_t* bounds_y,
+                    const int32_t* coef_y, int32_t ksize_y, void* scratch);
+int ghr_gt_assemble(void* stream, int32_t W, int32_t H, const uint8_t* image, const uint8_t* mask_hair, const uint8_t* mask_body,
+                    const uint8_t* angle, const float* var, int32_t var_w, int32_t var_h, const float* div255_table,
+                    const float* div180_table, int32_t white_background, int32_t binarize, int32_t via_half, float* out_image,
+                    float* out_mask, float* out_angle, float* out_conf);
+int ghr_gt_resize_variance(void* stream, int32_t W, int32_t H, const float* var, int32_t var_w, int32_t var_h, int32_t via_half,
+                           float* out);
+
 /* Introspection for tests (device pointers into the workspaces; layout is otherwise private). */
 typedef struct ghr_ws_view {
     const float* rec;          /* [P][16]: x, y, conic a, b, c, opacity, features[10] */
