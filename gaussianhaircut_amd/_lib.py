@@ -126,6 +126,28 @@ class LossArgs(ctypes.Structure):
                [(n, ctypes.c_float) for n in ("w_l1", "w_ssim", "w_mask", "w_orient")] + \
                [("unmasked_colours", ctypes.c_int32), ("gt_stats", ctypes.c_void_p)]
 
+
+class ShFoldArgs(ctypes.Structure):
+    """``ghr_sh_fold_args`` (include/ghr.h)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("P", "sh_degree", "sh_coeffs", "n_views")] + \
+               [("xyz", ctypes.c_void_p), ("campos", ctypes.c_void_p), ("campos_stride", ctypes.c_int64),
+                ("g_views", ctypes.c_void_p), ("view_stride", ctypes.c_int64), ("d_features_dc", ctypes.c_void_p),
+                ("d_features_rest", ctypes.c_void_p), ("accumulate", ctypes.c_int32)]
+
+
+class ViewStepArgs(ctypes.Structure):
+    """``ghr_view_step_args`` (include/ghr.h): one training view -- forward, loss, backward -- in one call."""
+    _fields_ = [("model", ModelArgs), ("R", ctypes.c_uint32), ("R_host", ctypes.c_void_p)] + \
+               [(n, ctypes.c_void_p) for n in ("geom_ws", "img_ws", "bin_ws", "radii", "means2D_out", "render")] + \
+               [("loss", LossArgs)] + \
+               [(n, ctypes.c_void_p) for n in ("maps", "sums", "loss_out", "grad_loss", "d_pix", "grad_scratch")] + \
+               [("prezero", ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ("d_means2D", "d_xyz", "d_log_scales", "d_rotations", "d_opacity_logit",
+                                               "d_label_logit", "d_orient_conf_log", "d_features_dc", "d_features_rest")] + \
+               [("accumulate", ctypes.c_int32), ("nan_flag", ctypes.c_void_p), ("sh_fold", ctypes.c_void_p),
+                ("count_event", ctypes.c_void_p), ("acc_wait_event", ctypes.c_void_p), ("acc_record_event", ctypes.c_void_p)]
+
+
 class EvalArgs(ctypes.Structure):
     """``ghr_eval_args`` (include/ghr.h)."""
     _fields_ = [("W", ctypes.c_int32), ("H", ctypes.c_int32)] + \
@@ -148,7 +170,7 @@ class WsView(ctypes.Structure):
 EXPORTS = ["ghr_last_error", "ghr_abi_version", "ghr_forward_sizes", "ghr_binning_size", "ghr_forward_stage1",
            "ghr_forward_stage2", "ghr_backward", "ghr_backward_ex", "ghr_mark_visible", "ghr_ws_inspect", "ghr_set_profile_events", "ghr_set_deterministic", "ghr_selftest_wave", "ghr_selftest_math", "ghr_model_forward_stage1",
            "ghr_model_backward", "ghr_model_forward_segment", "ghr_model_forward_finish", "ghr_render_backward",
-           "ghr_model_backward_segment", "ghr_camera_slots", "ghr_camera_grad_fold", "ghr_strand_build", "ghr_strand_build_backward", "ghr_strand_build_backward_ex", "ghr_sh_grad_from_views", "ghr_loss_sums_floats", "ghr_loss_forward", "ghr_loss_gt_stats", "ghr_loss_backward", "ghr_adam_step",
+           "ghr_model_backward_segment", "ghr_camera_slots", "ghr_camera_grad_fold", "ghr_strand_build", "ghr_strand_build_backward", "ghr_strand_build_backward_ex", "ghr_sh_grad_from_views", "ghr_loss_sums_floats", "ghr_loss_forward", "ghr_loss_gt_stats", "ghr_loss_backward", "ghr_view_step", "ghr_adam_step",
            "ghr_adam_step_range", "ghr_adam_step_range_to", "ghr_adam_nan_scan", "ghr_adam_relay_rows", "ghr_adam_fused_finish",
            "ghr_knn_workspace_size", "ghr_knn_keys", "ghr_knn_mean_dist2",
            "ghr_camera_compose", "ghr_camera_compose_backward", "ghr_camera_adam_step",
@@ -194,6 +216,7 @@ def lib() -> ctypes.CDLL:
     L.ghr_loss_forward.argtypes = [vp, ctypes.POINTER(LossArgs), vp, vp, vp]
     L.ghr_loss_gt_stats.argtypes = [vp, ctypes.POINTER(LossArgs), vp]
     L.ghr_loss_backward.argtypes = [vp, ctypes.POINTER(LossArgs)] + [vp] * 9
+    L.ghr_view_step.argtypes = [vp, ctypes.POINTER(ViewStepArgs)]
     L.ghr_adam_step.argtypes = [vp, ctypes.c_int64, vp, vp, vp, vp, vp, i32, ctypes.POINTER(ctypes.c_int64),
                                 ctypes.POINTER(ctypes.c_float), ctypes.c_double, ctypes.c_double, f32, i32, i32, u32]
     L.ghr_adam_step_range.argtypes = [vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, vp, vp, vp, vp, vp, i32,

@@ -444,6 +444,45 @@ int fill_model(const ghr_model_args* m, ghr::ModelArgs* a)
     return GHR_OK;
 }
 inline int n_blocks(int rows) { return (rows + GHR_BLOCK - 1) / GHR_BLOCK; }
+// The checks and the host-side table of a backward call that carries the optimizer update (ghr_adam_fuse): which group each
+// raw-parameter array of `a` lies in and its learning rate.  Launches nothing (ghr_view_step validates with it up front).
+int fill_adam_fuse(const ghr::ModelArgs& a, const ghr_adam_fuse* af, int32_t accumulate, const int32_t* nan_flag,
+                   ghr::ModelGrads* mg)
+{
+    if (a.mode == 1 && accumulate) return fail(GHR_E_INVALID, "ghr_adam_fuse: a strand segment carries the update only as the step's single view");
+    if (af->n <= 0 || !af->p_in || !af->m_in || !af->v_in || !af->p_out || !af->m_out || !af->v_out || !af->state || !af->flag ||
+        !af->flag_next || af->n_groups <= 0 || af->n_groups > GHR_ADAM_MAX_GROUPS || !af->group_end_host || !af->lr_host)
+        return fail(GHR_E_INVALID, "ghr_adam_fuse: NULL buffer / bad group table");
+    if (nan_flag != af->flag) return fail(GHR_E_INVALID, "ghr_adam_fuse: nan_flag of the backward call must be adam_fuse->flag");
+    const float* arrays[GHR_ADAM_FUSE_ARRAYS] = {a.xyz, a.log_scales, a.rotations, a.opacity_logit, a.label_logit,
+                                                 a.orient_conf_log, a.features_dc, a.features_rest};
+    // (mode 1, a strand segment: only the SH features are raw parameters of the optimizer; the other groups of its flat
+    // buffer -- strand directions, confidence -- get their gradients through autograd and are stepped by the caller)
+    const long long w6 = a.mode == 1 ? 0 : 1;
+    const long long width[GHR_ADAM_FUSE_ARRAYS] = {3 * w6, 3 * w6, 4 * w6, w6, w6, w6, 3, 3LL * (a.sh_coeffs - 1)};
+    long long covered = 0;
+    for (int k = 0; k < GHR_ADAM_FUSE_ARRAYS; k++) {
+        const long long len = width[k] * a.P;
+        if (len == 0) { mg->adam.lr[k] = 0.f; mg->adam.group[k] = 0; continue; }
+        const long long off = arrays[k] - af->p_in;
+        if (off < 0 || off + len > af->n)
+            return fail(GHR_E_INVALID, "ghr_adam_fuse: a raw-parameter array does not lie inside p_in");
+        int gi = 0;
+        while (gi < af->n_groups - 1 && off >= af->group_end_host[gi]) gi++;
+        if (off + len > af->group_end_host[gi])
+            return fail(GHR_E_INVALID, "ghr_adam_fuse: a raw-parameter array straddles two parameter groups");
+        mg->adam.group[k] = gi;
+        mg->adam.lr[k] = af->lr_host[gi];
+        covered += len;
+    }
+    if (a.mode == 0 && covered != af->n)
+        return fail(GHR_E_INVALID, "ghr_adam_fuse: the eight raw-parameter arrays must tile p_in (n floats)");
+    mg->adam.p_base = af->p_in; mg->adam.m_in = af->m_in; mg->adam.v_in = af->v_in;
+    mg->adam.p_out = af->p_out; mg->adam.m_out = af->m_out; mg->adam.v_out = af->v_out;
+    mg->adam.state = af->state; mg->adam.beta1 = af->beta1; mg->adam.beta2 = af->beta2; mg->adam.eps = af->eps;
+    mg->adam.on = 1;
+    return GHR_OK;
+}
 }  // namespace
 
 int ghr_model_forward_segment(void* stream, const ghr_model_args* m, int32_t rows_total, int32_t first, void* geom_ws,
@@ -602,38 +641,7 @@ int ghr_model_backward_segment(void* stream, const ghr_model_args* m, int32_t ro
     const ghr_adam_fuse* af = m->adam_fuse;
     if (af) {
         if (cam_only) return fail(GHR_E_INVALID, "ghr_adam_fuse: not with a cam_only segment");
-        if (a.mode == 1 && accumulate) return fail(GHR_E_INVALID, "ghr_adam_fuse: a strand segment carries the update only as the step's single view");
-        if (af->n <= 0 || !af->p_in || !af->m_in || !af->v_in || !af->p_out || !af->m_out || !af->v_out || !af->state || !af->flag ||
-            !af->flag_next || af->n_groups <= 0 || af->n_groups > GHR_ADAM_MAX_GROUPS || !af->group_end_host || !af->lr_host)
-            return fail(GHR_E_INVALID, "ghr_adam_fuse: NULL buffer / bad group table");
-        if (nan_flag != af->flag) return fail(GHR_E_INVALID, "ghr_adam_fuse: nan_flag of the backward call must be adam_fuse->flag");
-        const float* arrays[GHR_ADAM_FUSE_ARRAYS] = {a.xyz, a.log_scales, a.rotations, a.opacity_logit, a.label_logit,
-                                                     a.orient_conf_log, a.features_dc, a.features_rest};
-        // (mode 1, a strand segment: only the SH features are raw parameters of the optimizer; the other groups of its flat
-        // buffer -- strand directions, confidence -- get their gradients through autograd and are stepped by the caller)
-        const long long w6 = a.mode == 1 ? 0 : 1;
-        const long long width[GHR_ADAM_FUSE_ARRAYS] = {3 * w6, 3 * w6, 4 * w6, w6, w6, w6, 3, 3LL * (a.sh_coeffs - 1)};
-        long long covered = 0;
-        for (int k = 0; k < GHR_ADAM_FUSE_ARRAYS; k++) {
-            const long long len = width[k] * a.P;
-            if (len == 0) { mg.adam.lr[k] = 0.f; mg.adam.group[k] = 0; continue; }
-            const long long off = arrays[k] - af->p_in;
-            if (off < 0 || off + len > af->n)
-                return fail(GHR_E_INVALID, "ghr_adam_fuse: a raw-parameter array does not lie inside p_in");
-            int gi = 0;
-            while (gi < af->n_groups - 1 && off >= af->group_end_host[gi]) gi++;
-            if (off + len > af->group_end_host[gi])
-                return fail(GHR_E_INVALID, "ghr_adam_fuse: a raw-parameter array straddles two parameter groups");
-            mg.adam.group[k] = gi;
-            mg.adam.lr[k] = af->lr_host[gi];
-            covered += len;
-        }
-        if (a.mode == 0 && covered != af->n)
-            return fail(GHR_E_INVALID, "ghr_adam_fuse: the eight raw-parameter arrays must tile p_in (n floats)");
-        mg.adam.p_base = af->p_in; mg.adam.m_in = af->m_in; mg.adam.v_in = af->v_in;
-        mg.adam.p_out = af->p_out; mg.adam.m_out = af->m_out; mg.adam.v_out = af->v_out;
-        mg.adam.state = af->state; mg.adam.beta1 = af->beta1; mg.adam.beta2 = af->beta2; mg.adam.eps = af->eps;
-        mg.adam.on = 1;
+        if (int rc = fill_adam_fuse(a, af, accumulate, nan_flag, &mg)) return rc;
     }
     if (m->dens_img_ws && (af || m->overflow_raises_flag)) {
         // (steps with the fused optimizer update: EVERY view's backward checks its instance count and raises the step's flag)
@@ -919,6 +927,126 @@ int ghr_loss_backward(void* stream, const ghr_loss_args* l, const float* maps, c
     if (loss_vec_ok(l, maps)) hipLaunchKernelGGL(ghr::k_loss_bwd_v, loss_march_grid(l, a.seg), dim3(64), 0, s, a);
     else hipLaunchKernelGGL(ghr::k_loss_bwd, grid, dim3(256), 0, s, a);
     return finish(s, 0);
+}
+
+// ---- one call per training view (include/ghr.h, ghr_view_step) -------------------------------------------------
+namespace {
+int vs_bad(const char* what) { return fail(GHR_E_INVALID, "ghr_view_step: %s", what); }
+#define GHR_VS_PTR(p, name) \
+    do { if (!(p)) return vs_bad(name " is NULL"); } while (0)
+
+// Everything the six calls below would refuse, asked up front (they check as they go: a struct that only the last of them
+// refuses would otherwise leave five calls' kernels in the stream).  Launches nothing, touches no device memory.
+int check_view_step(const ghr_view_step_args* v)
+{
+    if (!v) return vs_bad("the argument struct is NULL");
+    const ghr_model_args* m = &v->model;
+    if (m->P <= 0) return vs_bad("model.P must be > 0");
+    if (m->W <= 0 || m->H <= 0) return vs_bad("model.W / model.H must be > 0");
+    if ((m->W + GHR_TILE - 1) / GHR_TILE > 65535 || (m->H + GHR_TILE - 1) / GHR_TILE > 65535)
+        return vs_bad("model.W / model.H: image too large for 16-bit tile coordinates");
+    if (m->mode != 0) return vs_bad("model.mode must be 0");
+    if (m->row0 != 0) return vs_bad("model.row0 must be 0");
+    if (m->debug != 0) return vs_bad("model.debug must be 0 (the call never waits for the device)");
+    if (m->cam_partial || m->cam_only || m->detach_means2D) return vs_bad("model.cam_partial / cam_only / detach_means2D: camera gradients are not part of the call");
+    if (m->fovx_dev || m->fovy_dev) return vs_bad("model.fovx_dev / fovy_dev must be NULL");
+    if (m->sh_degree < 0 || m->sh_degree > 3) return vs_bad("model.sh_degree must be 0 .. 3");
+    if ((m->sh_coeffs != 1 && m->sh_coeffs != 4 && m->sh_coeffs != 9 && m->sh_coeffs != 16) ||
+        m->sh_coeffs < (m->sh_degree + 1) * (m->sh_degree + 1))
+        return vs_bad("model.sh_coeffs must be (max_sh_degree + 1)^2 and cover model.sh_degree");
+    GHR_VS_PTR(m->xyz, "model.xyz"); GHR_VS_PTR(m->log_scales, "model.log_scales"); GHR_VS_PTR(m->rotations, "model.rotations");
+    GHR_VS_PTR(m->opacity_logit, "model.opacity_logit"); GHR_VS_PTR(m->label_logit, "model.label_logit");
+    GHR_VS_PTR(m->orient_conf_log, "model.orient_conf_log"); GHR_VS_PTR(m->features_dc, "model.features_dc");
+    if (m->sh_coeffs > 1) GHR_VS_PTR(m->features_rest, "model.features_rest");
+    GHR_VS_PTR(m->viewmatrix, "model.viewmatrix"); GHR_VS_PTR(m->projmatrix, "model.projmatrix");
+    GHR_VS_PTR(m->campos, "model.campos"); GHR_VS_PTR(m->background, "model.background");
+    GHR_VS_PTR(v->R_host, "R_host"); GHR_VS_PTR(v->geom_ws, "geom_ws"); GHR_VS_PTR(v->img_ws, "img_ws");
+    if (v->R > 0) { GHR_VS_PTR(v->bin_ws, "bin_ws"); GHR_VS_PTR(v->grad_scratch, "grad_scratch"); }
+    const size_t T = (size_t)grid_x(m->W) * grid_x(m->H);
+    if (ghr::mask_groups((size_t)v->R, T) * 128 >= ((size_t)1 << 32))
+        return vs_bad("R: too many instances for the 32-bit offsets of the cell masks");
+    if (g_deterministic && !ghr::b3_fits((size_t)m->P, v->R, (size_t)m->W, (size_t)m->H))
+        return vs_bad("model.P / R: " GHR_E_DETERMINISTIC_MSG);
+    GHR_VS_PTR(v->radii, "radii"); GHR_VS_PTR(v->render, "render");
+    const ghr_loss_args* l = &v->loss;
+    if (l->W != m->W || l->H != m->H) return vs_bad("loss.W / loss.H differ from model.W / model.H");
+    GHR_VS_PTR(l->gt_image, "loss.gt_image"); GHR_VS_PTR(l->gt_mask, "loss.gt_mask");
+    if (l->w_orient != 0.f) { GHR_VS_PTR(l->gt_orient_angle, "loss.gt_orient_angle"); GHR_VS_PTR(l->gt_orient_conf, "loss.gt_orient_conf"); }
+    GHR_VS_PTR(v->maps, "maps"); GHR_VS_PTR(v->sums, "sums"); GHR_VS_PTR(v->loss_out, "loss_out"); GHR_VS_PTR(v->d_pix, "d_pix");
+    GHR_VS_PTR(v->d_means2D, "d_means2D"); GHR_VS_PTR(v->d_xyz, "d_xyz"); GHR_VS_PTR(v->d_log_scales, "d_log_scales");
+    GHR_VS_PTR(v->d_rotations, "d_rotations"); GHR_VS_PTR(v->d_opacity_logit, "d_opacity_logit");
+    GHR_VS_PTR(v->d_label_logit, "d_label_logit"); GHR_VS_PTR(v->d_orient_conf_log, "d_orient_conf_log");
+    const ghr_adam_fuse* af = m->adam_fuse;
+    if (m->d_rgb && af) return vs_bad("model.d_rgb with model.adam_fuse (the view that carries the update stores no table)");
+    // (the SH gradient buffers may be NULL when nothing is stored there: ghr_model_backward_segment)
+    const bool sh_unstored = m->d_rgb != nullptr || (af != nullptr && !v->accumulate);
+    if (!sh_unstored && (!v->d_features_dc || (m->sh_coeffs > 1 && !v->d_features_rest)))
+        return vs_bad(af ? "d_features_dc / d_features_rest is NULL: model.adam_fuse with accumulate != 0 adds the earlier views' "
+                           "gradients from there"
+                         : "d_features_dc / d_features_rest is NULL (without model.d_rgb)");
+    const int n_dens = (m->dens_grad_accum != nullptr) + (m->dens_denom != nullptr) + (m->dens_max_radii2D != nullptr);
+    if (n_dens != 0 && n_dens != 3) return vs_bad("model.dens_grad_accum / dens_denom / dens_max_radii2D: all three or none");
+    if (m->dens_img_ws && m->dens_img_ws != v->img_ws) return vs_bad("model.dens_img_ws must be img_ws");
+    if (m->overflow_raises_flag && (!m->dens_img_ws || !v->nan_flag))
+        return vs_bad("model.overflow_raises_flag needs model.dens_img_ws and nan_flag");
+    ghr::ModelArgs a;
+    if (int rc = fill_model(m, &a)) return rc;
+    if (af) {
+        if (!m->dens_img_ws) return vs_bad("model.adam_fuse needs model.dens_img_ws (an overflowed view must not reach the parameters)");
+        ghr::ModelGrads mg;
+        if (int rc = fill_adam_fuse(a, af, v->accumulate, v->nan_flag, &mg)) return rc;
+    }
+    if (const ghr_sh_fold_args* f = v->sh_fold) {
+        if (f->P != m->P || f->sh_coeffs != m->sh_coeffs) return vs_bad("sh_fold.P / sh_fold.sh_coeffs differ from the model's");
+        if (f->n_views < 0 || f->sh_degree < 0 || (f->sh_degree + 1) * (f->sh_degree + 1) > f->sh_coeffs || f->view_stride < 0 ||
+            f->campos_stride < 0 || (f->n_views > 1 && f->view_stride < 3 * (int64_t)f->P))
+            return vs_bad("sh_fold: bad sizes / overlapping views");
+        GHR_VS_PTR(f->xyz, "sh_fold.xyz"); GHR_VS_PTR(f->d_features_dc, "sh_fold.d_features_dc");
+        if (f->sh_coeffs > 1) GHR_VS_PTR(f->d_features_rest, "sh_fold.d_features_rest");
+        if (f->n_views > 0) { GHR_VS_PTR(f->campos, "sh_fold.campos"); GHR_VS_PTR(f->g_views, "sh_fold.g_views"); }
+    }
+    return GHR_OK;
+}
+}  // namespace
+
+int ghr_view_step(void* stream, const ghr_view_step_args* v)
+{
+    if (int rc = check_view_step(v)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const ghr_model_args* m = &v->model;
+    const size_t n = (size_t)m->W * m->H;
+    if (int rc = ghr_model_forward_stage1(stream, m, v->geom_ws, v->img_ws, v->radii, v->means2D_out, v->R_host)) return rc;
+    if (v->count_event) GHR_HIP(hipEventRecord((hipEvent_t)v->count_event, s));
+    ghr_view_args va;
+    std::memset(&va, 0, sizeof(va));
+    va.P = m->P; va.W = m->W; va.H = m->H; va.C = GHR_NUM_CHANNELS; va.background = m->background;
+    if (int rc = ghr_forward_stage2(stream, &va, v->R, v->geom_ws, v->img_ws, v->bin_ws, v->render,
+                                    v->prezero ? v->grad_scratch : nullptr))
+        return rc;
+    ghr_loss_args l = v->loss;  // the rendered planes of the packed output (include/ghr.h, ghr_loss_args)
+    l.image = v->render; l.mask = v->render + 3 * n; l.dir2d = v->render + 5 * n; l.orient_conf = v->render + 8 * n;
+    if (int rc = ghr_loss_forward(stream, &l, v->maps, v->sums, v->loss_out)) return rc;
+    l.gt_stats = nullptr;  // (the backward pass reads no window moments)
+    float* d = v->d_pix;   // channels 7 and 9 carry no loss term: zero-filled by the loss backward
+    if (int rc = ghr_loss_backward(stream, &l, v->maps, v->sums, v->grad_loss, d, d + 3 * n, d + 5 * n, d + 8 * n, d + 7 * n,
+                                   d + 9 * n))
+        return rc;
+    if (int rc = ghr_render_backward(stream, m->P, m->W, m->H, v->R, m->background, v->geom_ws, v->img_ws, v->bin_ws, d,
+                                     v->grad_scratch, v->prezero))
+        return rc;
+    if (v->acc_wait_event) GHR_HIP(hipStreamWaitEvent(s, (hipEvent_t)v->acc_wait_event, 0));
+    if (const ghr_sh_fold_args* f = v->sh_fold)
+        if (int rc = ghr_sh_grad_from_views(stream, f->P, f->sh_degree, f->sh_coeffs, f->xyz, f->n_views, f->campos, f->campos_stride,
+                                            f->g_views, f->view_stride, f->d_features_dc, f->d_features_rest, f->accumulate,
+                                            nullptr, 0))
+            return rc;
+    if (int rc = ghr_model_backward_segment(stream, m, m->P, v->radii, v->geom_ws, v->grad_scratch, v->d_means2D, v->d_xyz,
+                                            v->d_log_scales, v->d_rotations, v->d_opacity_logit, v->d_label_logit,
+                                            v->d_orient_conf_log, v->d_features_dc, v->d_features_rest, nullptr, v->accumulate,
+                                            v->nan_flag, v->R, v->bin_ws, v->R))
+        return rc;
+    if (v->acc_record_event) GHR_HIP(hipEventRecord((hipEvent_t)v->acc_record_event, s));
+    return GHR_OK;
 }
 
 // ---- evaluation pass (ghr_eval.h) ------------------------------------------------------------------------------------

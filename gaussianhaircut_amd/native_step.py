@@ -1,0 +1,351 @@
+"""The native view step: render + stage-1 loss + backward of one training view as ONE library call (``ghr_view_step``,
+include/ghr.h) on buffers that are allocated once.
+
+``trainer.training_step(native=True)`` (or ``GHR_NATIVE_STEP=1``) routes the views of an eligible step through here instead of
+through the two ``autograd.Function`` round trips of ``render()`` / ``view_loss()`` / ``backward()``: the same kernels with the
+same arguments in the same order -- the library call is a composition of the six calls the Python path makes -- without a
+dozen ``torch.empty``, the autograd graph and five of the six ctypes crossings per view.  What a view needs lives in a *slot*
+per HIP stream the step's views run on (workspaces at the capacity guess, render and gradient planes, loss scratch) with one
+filled ``ghr_view_step_args`` of which only the per-step and per-view fields are rewritten.
+
+Everything about the step that is not the views -- plan, opening the optimizer, the update, the overflow recovery -- stays in
+``trainer``; the optimizer's host-side bookkeeping (``FusedAdam``: known-zero gradients, view slots, the fused update, the event
+chain around the shared gradient buffer) is driven through the same methods, in the same order, as ``gaussian_renderer.fused``
+drives it.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+from typing import List, Optional
+
+import torch
+
+from . import _lib
+from . import diff_gaussian_rasterization as _dgr
+from .diff_gaussian_rasterization import PendingCount
+from .gaussian_renderer import _tan_half
+from .gaussian_renderer import fused as _fused
+
+LOSS_RING = 256  # steps a returned loss scalar stays valid for (it is a row of a ring, not a fresh allocation)
+# Slots a stream keeps: one per image size among the views, the least recently made dropped beyond this many.  A slot holds what
+# the Python path allocates and frees per view -- geom / img / binning workspaces, the gradient lines (64 B per instance of
+# capacity: ~0.5 GB at 2 M Gaussians), four image-sized planes -- for as long as the model lives.
+MAX_SLOTS_PER_STREAM = 2
+_MAX_VIEWS_INIT = 8
+
+
+def _plain_f32(t) -> bool:
+    return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
+            not t.requires_grad)
+
+
+class _CamFields:
+    """Pointers of a constant camera and of its ground truth, remade when one of the tensors is replaced."""
+    __slots__ = ("tensors", "ptrs", "W", "H")
+
+    def __init__(self, tensors, W, H):
+        self.tensors, self.W, self.H = tensors, W, H
+        self.ptrs = tuple(t.data_ptr() for t in tensors)
+
+
+def _cam_tensors(cam):
+    return (cam.world_view_transform, cam.full_proj_transform, cam.camera_center, cam.original_image, cam.original_mask,
+            cam.original_orient_angle, cam.original_orient_conf)
+
+
+def _cam_fields(cam) -> Optional[_CamFields]:
+    """None: this camera's view cannot take the native path (its tensors are composed per access or trained, it belongs to
+    a camera bank, or its ground truth is not plain contiguous fp32 device data)."""
+    if hasattr(cam, "tensors") or getattr(cam, "bank", None) is not None:
+        return None
+    try:
+        ts = _cam_tensors(cam)
+    except AttributeError:
+        return None
+    c = cam.__dict__.get("_ghr_native_fields")
+    if c is not None and all(a is b for a, b in zip(c.tensors, ts)):
+        # (the same tensors: still constants?  requires_grad_() does not replace the object)
+        live = ts[0].requires_grad or ts[1].requires_grad or ts[2].requires_grad or \
+            any(isinstance(f, torch.Tensor) and f.requires_grad for f in (cam.FoVx, cam.FoVy))
+        return None if live else c
+    W, H = int(cam.image_width), int(cam.image_height)
+    if not all(_plain_f32(t) for t in ts):
+        return None
+    if any(isinstance(f, torch.Tensor) and f.requires_grad for f in (cam.FoVx, cam.FoVy)):
+        return None
+    if ts[0].numel() != 16 or ts[1].numel() != 16 or ts[2].numel() != 3 or tuple(ts[3].shape) != (3, H, W) or \
+            tuple(ts[4].shape) != (2, H, W) or ts[5].numel() != H * W or ts[6].numel() != H * W:
+        return None
+    c = _CamFields(ts, W, H)
+    cam.__dict__["_ghr_native_fields"] = c
+    return c
+
+
+def _leaves(g):
+    return (g._xyz, g._scaling, g._rotation, g._opacity, g._label, g._orient_conf, g._features_dc, g._features_rest)
+
+
+def ineligible(plan, gaussians, cams, background, pipe, bucket, banks) -> Optional[str]:
+    """Why this step cannot take the native path (None: it can).  Decided from the plan and the configuration only."""
+    from .optim import collectives_on
+    if not (plan.fused_sink and plan.all_direct and plan.defer):
+        return "the step is not all on the fused renderer's direct backward with deferred counts"
+    if gaussians._xyz.device != background.device:
+        return "the model and the background are on different devices"
+    if collectives_on() or bucket is not None:
+        return "data-parallel steps take the Python path"
+    if getattr(pipe, "debug", False):
+        return "pipe.debug"
+    if banks:
+        return "a camera bank among the views"
+    if plan.factored == "gathered":
+        return "gathered view tables"
+    if not cams or gaussians._xyz.shape[0] == 0:
+        return "no views / an empty model"
+    if not torch.is_grad_enabled():
+        return "grad mode is off"
+    if not _fused._grads_in_place(_leaves(gaussians)):
+        return "a parameter's .grad does not alias the optimizer's gradient buffer"
+    for c in cams:
+        if _cam_fields(c) is None:
+            return "a camera whose tensors are trained or composed per access, or ground truth that is not plain fp32 device data"
+    return None
+
+
+def has_capacity_guess(gaussians, background) -> bool:
+    """A view needs a capacity for its binning workspace before its count is known: the guess the blocking path learns
+    (``diff_gaussian_rasterization._R_HINT``).  Without one -- the first step, or the first after the model changed size -- the
+    step runs the Python way, which waits for the count."""
+    idx = background.device.index
+    P = int(gaussians._xyz.shape[0])
+    return bool(_dgr._R_HINT.get(idx)) and _dgr._R_P.get(idx, P) == P
+
+
+class _Slot:
+    """The buffers of the views that run on one stream, and their argument struct."""
+
+    def __init__(self, dev, P, W, H, K):
+        self.P, self.W, self.H, self.K = P, W, H, K
+        f32 = dict(dtype=torch.float32, device=dev)
+        gbytes, ibytes = _lib.forward_sizes(P, W, H, False)
+        self.geom = torch.empty((gbytes,), dtype=torch.uint8, device=dev)
+        self.img = torch.empty((ibytes,), dtype=torch.uint8, device=dev)
+        self.img_complete = False  # through stage 1 AND stage 2 once: its counters are back at zero (ghr_model_args.img_ws_recycled)
+        self.radii = torch.empty((P,), dtype=torch.int32, device=dev)
+        self.means2D = torch.empty((P, 3), **f32)
+        self.d_means2D = torch.empty((P, 3), **f32)
+        self.render = torch.empty((_lib.NUM_CHANNELS, H, W), **f32)
+        self.d_pix = torch.empty((_lib.NUM_CHANNELS, H, W), **f32)
+        self.maps = torch.empty((9, H, W), **f32)
+        self.sums = torch.empty(_lib.loss_sums_floats(W, H), **f32)
+        self.cap, self.bin, self.scratch = None, None, None
+        a = self.args = _lib.ViewStepArgs()
+        m = a.model
+        m.P, m.W, m.H, m.sh_coeffs = P, W, H, K
+        a.loss.W, a.loss.H = W, H
+        a.geom_ws, a.img_ws = self.geom.data_ptr(), self.img.data_ptr()
+        a.radii, a.means2D_out, a.d_means2D = self.radii.data_ptr(), self.means2D.data_ptr(), self.d_means2D.data_ptr()
+        a.render, a.d_pix = self.render.data_ptr(), self.d_pix.data_ptr()
+        a.maps, a.sums = self.maps.data_ptr(), self.sums.data_ptr()
+        self.step_id = -1
+
+    def set_capacity(self, cap, dev):
+        """Binning workspace and gradient lines on the capacity grid: re-made only when the guess moves to another grid point."""
+        if cap != self.cap:
+            self.bin = torch.empty((_lib.binning_size(cap, self.W, self.H),), dtype=torch.uint8, device=dev)
+            self.scratch = torch.empty((max(int(cap), 1), _lib.GRAD_STRIDE), dtype=torch.float32, device=dev)
+            self.cap = cap
+            a = self.args
+            a.R, a.bin_ws, a.grad_scratch = cap, self.bin.data_ptr(), self.scratch.data_ptr()
+
+
+class NativeViews:
+    """What the native views of one model need, allocated once (kept on the model: ``for_model``)."""
+
+    def __init__(self, dev):
+        self.dev = dev
+        self.slots = {}
+        self.one = torch.ones((), dtype=torch.float32, device=dev)
+        self.pinned = None
+        self.count_events: List[torch.cuda.Event] = []
+        self.acc_events: List[torch.cuda.Event] = []
+        self.ring = None
+        self.ring_pos = 0
+        self.step_id = 0
+        self._ensure_views(_MAX_VIEWS_INIT)
+
+    def __deepcopy__(self, memo):
+        return None  # (a copied model makes its own: events and workspaces are not state)
+
+    @staticmethod
+    def for_model(gaussians, dev) -> "NativeViews":
+        nv = gaussians.__dict__.get("_ghr_native_views")
+        if nv is None or nv.dev != dev:
+            nv = gaussians.__dict__["_ghr_native_views"] = NativeViews(dev)
+        return nv
+
+    @staticmethod
+    def _event(stream):
+        ev = torch.cuda.Event()
+        ev.record(stream)  # (the handle exists from the first record on; the library records it again for every view)
+        return ev
+
+    def _ensure_views(self, n):
+        """Per view position of a step: the pinned word its count lands in, the event behind its stage 1, the event behind its
+        accumulating kernels; and the ring of loss rows."""
+        if self.pinned is not None and len(self.count_events) >= n:
+            return
+        n = max(n, 2 * len(self.count_events))
+        with torch.cuda.device(self.dev):
+            stream = torch.cuda.current_stream(self.dev)
+            stream.synchronize()  # (growing: nobody is still writing the words that are replaced)
+            self.pinned = torch.zeros(n, dtype=torch.int32).pin_memory()
+            self.count_events = [self._event(stream) for _ in range(n)]
+            self.acc_events = [self._event(stream) for _ in range(n)]
+            # a row: the views' losses from column 0 (16-B aligned, like a fresh tensor), their sum in the last column
+            self.ring_width = (n + 1 + 3) // 4 * 4
+            self.ring = torch.zeros((LOSS_RING, self.ring_width), dtype=torch.float32, device=self.dev)
+
+    def _slot(self, stream_key, P, W, H, K):
+        key = (stream_key, P, W, H, K)
+        s = self.slots.get(key)
+        if s is None:
+            # (a model that changed size leaves its old slots behind: drop them, they hold workspaces of the old size; and a
+            # stream keeps slots for MAX_SLOTS_PER_STREAM image sizes, the oldest going first -- dicts keep insertion order)
+            mine = [k for k in self.slots if k[0] == stream_key]
+            stale = [k for k in mine if k[1] != P or k[4] != K]
+            keep = [k for k in mine if k not in stale]
+            for k in stale + keep[:max(0, len(keep) - (MAX_SLOTS_PER_STREAM - 1))]:
+                del self.slots[k]
+            s = self.slots[key] = _Slot(self.dev, P, W, H, K)
+        return s
+
+    def views_forward_backward(self, gaussians, cams, background, opt, plan, fuse, densify_stats):
+        """The native form of ``trainer._views_forward_backward``: returns (per-view loss scalars, PendingCounts, total loss)."""
+        # every stream, event and launch below is the MODEL's device's (as gaussian_renderer.fused and optim guard their calls)
+        with _dgr._on_device(self.dev):
+            return self._views_forward_backward(gaussians, cams, background, opt, plan, fuse, densify_stats)
+
+    def _views_forward_backward(self, gaussians, cams, background, opt, plan, fuse, densify_stats):
+        from .trainer import _gt_stats, _side_streams, _NO_STREAM
+        sink, V, dev = plan.sink, plan.V, self.dev
+        n = len(cams)
+        self._ensure_views(n)
+        self.step_id += 1
+        leaves = _leaves(gaussians)
+        P, K = int(leaves[0].shape[0]), 1 + int(leaves[7].shape[1])
+        p_ptrs = [t.data_ptr() for t in leaves]
+        g_ptrs = [t.grad.data_ptr() for t in leaves]
+        bg = background if _plain_f32(background) else background.detach().float().contiguous()
+        bg_ptr = bg.data_ptr()
+        sh_degree = int(gaussians.active_sh_degree)
+        eps = float(getattr(gaussians, "conic_eps", 1e-12))
+        dens_ptrs = None
+        if densify_stats:
+            stats = (gaussians.xyz_gradient_accum, gaussians.denom, gaussians.max_radii2D)
+            if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
+                       t.numel() == P for t in stats):
+                raise RuntimeError("densify_stats: xyz_gradient_accum / denom / max_radii2D must be contiguous fp32 device tensors "
+                                   "of P elements (GaussianModel.training_setup creates them)")
+            dens_ptrs = [t.data_ptr() for t in stats]
+        scale = 1.0 / V
+        w = (opt.lambda_dl1 * scale, opt.lambda_dssim * scale, opt.lambda_dmask * scale, opt.lambda_dorient * scale)
+        orient = float(w[3]) != 0.0
+        cap = int(_dgr._R_HINT[dev.index])
+        prezero = int(not os.environ.get("GHR_NO_PREZERO"))
+        recycle = _fused.RECYCLE_IMG_WS
+        row = self.ring[self.ring_pos]
+        self.ring_pos = (self.ring_pos + 1) % LOSS_RING
+        row_ptr = row.data_ptr()
+        pinned_ptr = self.pinned.data_ptr()
+        lib = _lib.lib()
+        losses, counts = [], []
+        main, side = None, ()
+        if plan.n_streams > 1:
+            main = torch.cuda.current_stream(dev)
+            side = _side_streams(dev, plan.n_streams)
+            for s in side:
+                s.wait_stream(main)  # parameters as the previous optimizer step left them
+            sink.concurrent = True
+        try:
+            for i, cam in enumerate(cams):
+                carries = bool(fuse) and i == n - 1  # this view's backward applies the optimizer update
+                with torch.cuda.stream(side[i % plan.n_streams]) if side else _NO_STREAM:
+                    stream = _dgr._stream()
+                    cf = _cam_fields(cam)
+                    slot = self._slot(stream.value or 0, P, cf.W, cf.H, K)
+                    slot.set_capacity(cap, dev)
+                    a = slot.args
+                    m, l = a.model, a.loss
+                    if slot.step_id != self.step_id:  # ---- what holds for every view of the step
+                        slot.step_id = self.step_id
+                        (m.xyz, m.log_scales, m.rotations, m.opacity_logit, m.label_logit, m.orient_conf_log, m.features_dc,
+                         m.features_rest) = p_ptrs
+                        (a.d_xyz, a.d_log_scales, a.d_rotations, a.d_opacity_logit, a.d_label_logit,
+                         a.d_orient_conf_log) = g_ptrs[:6]
+                        m.background, m.sh_degree, m.conic_eps, m.scale_modifier = bg_ptr, sh_degree, eps, 1.0
+                        l.w_l1, l.w_ssim, l.w_mask, l.w_orient = w[0], w[1], w[2], (w[3] if orient else 0.0)
+                        if dens_ptrs is not None:
+                            m.dens_grad_accum, m.dens_denom, m.dens_max_radii2D = dens_ptrs
+                        else:
+                            m.dens_grad_accum = m.dens_denom = m.dens_max_radii2D = None
+                        a.grad_loss, a.prezero = self.one.data_ptr(), prezero
+                    # ---- this view: camera, ground truth (+ its cached SSIM moments), where its outputs go
+                    pv, pp, pc, gi, gm, ga, gc = cf.ptrs
+                    m.viewmatrix, m.projmatrix, m.campos = pv, pp, pc
+                    m.tan_fovx, m.tan_fovy = _tan_half(cam.FoVx), _tan_half(cam.FoVy)
+                    l.gt_image, l.gt_mask = gi, gm
+                    l.gt_orient_angle, l.gt_orient_conf = (ga, gc) if orient else (None, None)
+                    stats = _gt_stats(cam, cf.tensors[3], cf.tensors[4], True)
+                    l.gt_stats = stats.data_ptr() if stats is not None else None
+                    m.img_ws_recycled = int(recycle and slot.img_complete)
+                    a.R_host = pinned_ptr + 4 * i
+                    a.loss_out = row_ptr + 4 * i
+                    a.count_event = int(self.count_events[i].cuda_event)
+                    # ---- the optimizer's side of a direct backward, as gaussian_renderer.fused._RenderModelFused.backward keeps it
+                    adam_fuse = sink.fused_step_args()
+                    if adam_fuse is not None:
+                        # a step whose LAST backward carries the update: every view checks its instance count on the device
+                        m.dens_img_ws, m.overflow_raises_flag = a.img_ws, 1
+                        m.adam_fuse = adam_fuse if carries else None
+                    else:
+                        m.dens_img_ws, m.overflow_raises_flag = (a.img_ws if dens_ptrs is not None else None), 0
+                        m.adam_fuse = None
+                    a.accumulate = 0 if sink.take_known_zero() else 1
+                    m.d_rgb, a.sh_fold = None, None
+                    a.d_features_dc, a.d_features_rest = g_ptrs[6], g_ptrs[7]
+                    if sink.views_open:
+                        if carries:
+                            # the earlier views' tables are folded into the flat gradient first, inside the call
+                            a.sh_fold = sink.fold_own_views_args()
+                        else:
+                            m.d_rgb = sink.next_view_slot(cf.tensors[2])
+                            a.d_features_dc = a.d_features_rest = None
+                    a.nan_flag = sink.nan_flag_ptr()
+                    a.acc_wait_event = a.acc_record_event = None
+                    if sink.concurrent:
+                        # only the kernels that add into the shared gradient buffer are ordered after the previous view's
+                        if sink._acc_event is not None:
+                            a.acc_wait_event = int(sink._acc_event.cuda_event)
+                        a.acc_record_event = int(self.acc_events[i].cuda_event)
+                    _lib.check(lib.ghr_view_step(stream, ctypes.byref(a)))
+                    if sink.concurrent:
+                        sink._acc_event = self.acc_events[i]
+                    slot.img_complete = True
+                    sink.note_direct_backward()
+                    if carries:
+                        sink.note_fused_update()
+                    losses.append(row[i])
+                    counts.append(PendingCount(self.pinned[i:i + 1], self.count_events[i], cap, dev.index, P))
+        finally:
+            if side:
+                sink.concurrent = False
+                for s in side:
+                    main.wait_stream(s)
+        if n == 1:
+            total = losses[0]
+        else:
+            total = row[self.ring_width - 1]
+            torch.sum(row[:n], dim=0, out=total)
+        return losses, counts, total

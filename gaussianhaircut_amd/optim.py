@@ -90,6 +90,7 @@ class FusedAdam:
     _views = None              # the view slots while they are open (begin_factored_views .. end_factored_views)
     _views_buf = None          # their buffer, kept from step to step
     _views_keep = None         # the gathered tables, until the stream has consumed them
+    _fold_args_keep = None     # the ghr_sh_fold_args handed out by fold_own_views_args, until the call has read it
     _fuse = None               # {"p", "m", "v": the second set; "flags": two int32 words; "parity"; "clean"}
     _fuse_step = None          # while a fused step is in progress: its ghr_adam_fuse + what keeps the pointers alive
     fused_steps = 0            # updates that were carried by a step's last backward
@@ -402,9 +403,8 @@ class FusedAdam:
         self._rebuild_sh_from_views(v["buf"][: v["next"]])
         v["next"] = 0
 
-    def _rebuild_sh_from_views(self, gathered: torch.Tensor, flags: bool = False):
-        """flat_grad[f_dc | f_rest] (+)= sum over the gathered views (rank-major, then slot order) -- ghr_sh_grad_from_views.
-        ``flags``: the rows also carry their owners' non-finite marks (float 3 P + 3 of a row): OR-ed into this rank's flag."""
+    def _sh_fold_args(self, gathered: torch.Tensor) -> "_lib.ShFoldArgs":
+        """The arguments of ``ghr_sh_grad_from_views`` for these view rows (``ghr_sh_fold_args``, without the flag word)."""
         v = self._views
         P, stride = v["P"], v["stride"]
         n_views = gathered.numel() // stride
@@ -414,14 +414,43 @@ class FusedAdam:
         act = K - 1 if self.active_rest_coeffs is None else int(self.active_rest_coeffs)
         deg = v["deg"] if v.get("deg") is not None else {0: 0, 3: 1, 8: 2, 15: 3}[act]
         base_g, base_p = self.flat_grad.data_ptr(), self.flat_param.data_ptr()
+        f = _lib.ShFoldArgs()
+        f.P, f.sh_degree, f.sh_coeffs, f.n_views = P, deg, K, n_views
+        f.xyz = base_p + 4 * a_xyz
+        f.campos, f.campos_stride = rows.data_ptr() + 4 * 3 * P, stride
+        f.g_views, f.view_stride = rows.data_ptr(), stride
+        f.d_features_dc, f.d_features_rest = base_g + 4 * a_dc, base_g + 4 * a_rest
+        f.accumulate = 0 if v["assign"] else 1
+        return f
+
+    def _rebuild_sh_from_views(self, gathered: torch.Tensor, flags: bool = False):
+        """flat_grad[f_dc | f_rest] (+)= sum over the gathered views (rank-major, then slot order) -- ghr_sh_grad_from_views.
+        ``flags``: the rows also carry their owners' non-finite marks (float 3 P + 3 of a row): OR-ed into this rank's flag."""
+        v = self._views
+        f = self._sh_fold_args(gathered)
         with _on_device(self.flat_param.device):
             _lib.check(_lib.lib().ghr_sh_grad_from_views(
-                _stream(), P, deg, K, ctypes.c_void_p(base_p + 4 * a_xyz), n_views,
-                ctypes.c_void_p(rows.data_ptr() + 4 * 3 * P), stride, _ptr(rows), stride,
-                ctypes.c_void_p(base_g + 4 * a_dc), ctypes.c_void_p(base_g + 4 * a_rest), 0 if v["assign"] else 1,
-                ctypes.c_void_p(self.state_dev.data_ptr() + 4) if flags else None, 3 * P + 3))
+                _stream(), f.P, f.sh_degree, f.sh_coeffs, ctypes.c_void_p(f.xyz), f.n_views,
+                ctypes.c_void_p(f.campos), f.campos_stride, ctypes.c_void_p(f.g_views), f.view_stride,
+                ctypes.c_void_p(f.d_features_dc), ctypes.c_void_p(f.d_features_rest), f.accumulate,
+                ctypes.c_void_p(self.state_dev.data_ptr() + 4) if flags else None, 3 * v["P"] + 3))
         v["assign"] = False  # (anything folded later in the same step comes on top)
         self._views_keep = gathered  # (alive until the stream has consumed them: replaced by the next step's)
+
+    def fold_own_views_args(self):
+        """``fold_own_views`` for a caller that launches the fold itself (native_step: inside ``ghr_view_step``, in front of the
+        projection backward that carries the update): address of the filled ``ghr_sh_fold_args``, or None without any filled
+        slot.  The host-side marks are set as if the fold had been launched here."""
+        v = self._views
+        if v is None or v["gather"] or v["next"] == 0:
+            return None
+        gathered = v["buf"][: v["next"]]
+        f = self._sh_fold_args(gathered)
+        v["assign"] = False
+        v["next"] = 0
+        self._views_keep = gathered
+        self._fold_args_keep = f  # (the struct, too, lives until the call has read it)
+        return ctypes.addressof(f)
 
     def note_direct_backward(self):
         self._direct_backwards += 1

@@ -35,6 +35,10 @@ OVERLAP_ALL_REDUCE_WITH_ADAM = os.environ.get("GHR_OVERLAP_AR_ADAM", "1") != "0"
 FUSE_STRAND_ADAM = os.environ.get("GHR_FUSE_STRAND_ADAM", "1") != "0"  # strand stage: the SH features' update in the backward
 FUSE_ADAM_INTO_BACKWARD = os.environ.get("GHR_FUSE_ADAM", "1") != "0"
 DEFER_GRAD_ZEROING = os.environ.get("GHR_DEFER_GRAD_ZEROING", "1") != "0"
+# The views of an eligible step as one library call each on buffers allocated once (native_step; include/ghr.h, ghr_view_step)
+# instead of render() + view_loss() + backward() through autograd: training_step(native=None) reads this, default off
+NATIVE_STEP_ENV = "GHR_NATIVE_STEP"
+_LAST_STEP_PATH = "python"
 CACHE_GT_SSIM_STATS = True  # keep the SSIM window moments of every camera's ground truth (2*3*H*W floats per camera)
 
 
@@ -315,7 +319,7 @@ def _update(plan: _StepPlan, gaussians, cams, bucket):
 def training_step(gaussians, cams: List, background, opt, iteration: int, bucket: Optional[FlatGradBucket] = None,
                   global_views: Optional[int] = None, pipe=PIPE, streams: Optional[int] = None,
                   defer_counts: Optional[bool] = None, densify_stats: bool = False, fuse_adam: Optional[bool] = None,
-                  views_per_rank: Optional[int] = None, camera_bank=None):
+                  views_per_rank: Optional[int] = None, camera_bank=None, native: Optional[bool] = None):
     """One global gradient step over this rank's views.  Returns the (detached) summed local loss.
 
     ``streams`` (default 2 with the fused path and more than one view): the views of the step are independent given
@@ -352,29 +356,71 @@ def training_step(gaussians, cams: List, background, opt, iteration: int, bucket
     joined -- ``camera_bank.step(iteration)`` steps the viewed cameras in one launch.  The views must be DISTINCT cameras (their
     rows are then disjoint across the view streams): that is checked for the cameras of ANY bank among the views, with or without
     this argument.  From ``opt.iterations_cam`` on the bank composes constants for the duration of the step and the views take the
-    constant-camera path.  A step that raises drops what its views left in their banks' gradient rows."""
+    constant-camera path.  A step that raises drops what its views left in their banks' gradient rows.
+
+    ``native`` (default: ``GHR_NATIVE_STEP``, off): every view of the step is ONE library call (``ghr_view_step``: the six calls
+    of render + loss + backward composed in C, the same kernels with the same arguments) on workspaces, planes and an argument
+    struct that are allocated once (``native_step``), instead of two ``autograd.Function`` round trips, six calls and a dozen
+    ``torch.empty`` per view.  Same parameters, moments, flags, statistics and loss, bit for bit.  Eligible is a step on one rank
+    whose views all take the fused renderer's direct backward with deferred counts (the default of this function on a ROCm
+    device), through constant cameras (no trained camera tensor, no camera bank), without ``pipe.debug``; streams, the per-view SH
+    tables, ``densify_stats`` and the update inside the last backward work as they do here.  Anything else takes the path above
+    untouched -- with ``native=True`` it raises instead.  A step without a capacity guess yet (the first one, or the first after
+    the model changed size) has to wait for its instance count and runs the Python way, whatever ``native`` says;
+    ``last_step_path()`` tells.  The returned scalar is a row of a ring of ``native_step.LOSS_RING`` steps, not a fresh tensor:
+    clone it to keep it longer."""
     banks = _check_bank_views(camera_bank, cams)
     try:
         with contextlib.ExitStack() as scopes:
             for b in banks:  # (a bank that is only viewed, not stepped here, keeps its own notion of whether it trains)
                 scopes.enter_context(b.step_scope(iteration if b is camera_bank else None))
             return _training_step(gaussians, cams, background, opt, iteration, bucket, global_views, pipe, streams, defer_counts,
-                                  densify_stats, fuse_adam, views_per_rank, camera_bank, banks)
+                                  densify_stats, fuse_adam, views_per_rank, camera_bank, banks, native)
     finally:  # (the optimizer's view slots never outlive the step)
         o = getattr(gaussians, "optimizer", None)
         if hasattr(o, "end_factored_views"):
             o.end_factored_views()
 
 
+def last_step_path() -> str:
+    """``"native"`` when the views of the last ``training_step`` ran as ``ghr_view_step`` calls, ``"python"`` otherwise."""
+    return _LAST_STEP_PATH
+
+
+def _native_views(native, plan, gaussians, cams, background, pipe, bucket, banks):
+    """The model's ``native_step.NativeViews`` when this step's views are to run natively, else None."""
+    forced = native is not None and bool(native)  # (the caller asked for it: an ineligible step is an error, not a fallback)
+    if native is None:
+        native = os.environ.get(NATIVE_STEP_ENV, "0") not in ("", "0")
+    if not native:
+        return None
+    from . import native_step
+    why = native_step.ineligible(plan, gaussians, cams, background, pipe, bucket, banks)
+    if why is not None:
+        if forced:
+            raise RuntimeError("training_step(native=True): this step cannot take the native path: " + why)
+        return None
+    if not native_step.has_capacity_guess(gaussians, background):
+        return None
+    return native_step.NativeViews.for_model(gaussians, background.device)
+
+
 def _training_step(gaussians, cams, background, opt, iteration, bucket, global_views, pipe, streams, defer_counts, densify_stats,
-                   fuse_adam, views_per_rank, camera_bank, banks):
+                   fuse_adam, views_per_rank, camera_bank, banks, native=None):
+    global _LAST_STEP_PATH
     gaussians.update_learning_rate(iteration)
     plan = _plan_step(gaussians, cams, background, bucket, global_views, pipe, streams, defer_counts, densify_stats,
                       fuse_adam, views_per_rank)
+    nv = _native_views(native, plan, gaussians, cams, background, pipe, bucket, banks)
+    _LAST_STEP_PATH = "python" if nv is None else "native"
     fuse = _open_step(plan, gaussians, cams)
+    native_total = None
     try:
-        losses, counts = _views_forward_backward(gaussians, cams, background, opt, plan.V, plan.run_pipe, plan.n_streams,
-                                                 plan.sink, plan.last_pipe if fuse else None)
+        if nv is not None:
+            losses, counts, native_total = nv.views_forward_backward(gaussians, cams, background, opt, plan, fuse, densify_stats)
+        else:
+            losses, counts = _views_forward_backward(gaussians, cams, background, opt, plan.V, plan.run_pipe, plan.n_streams,
+                                                     plan.sink, plan.last_pipe if fuse else None)
     finally:
         fused_done = plan.sink.end_fused_step() if fuse else False
     overflow = [c.resolve()[1] for c in counts if hasattr(c, "resolve")]  # resolve every one: they feed the next guess
@@ -383,7 +429,10 @@ def _training_step(gaussians, cams, background, opt, iteration, bucket, global_v
             b.discard_gradients()
         losses = _redo_overflowed_step(plan, gaussians, cams, background, opt, pipe, densify_stats, overflow, fused_done)
         fused_done = False
-    if not losses:  # a rank without views in this step still takes part in the collectives and the update
+        native_total = None
+    if native_total is not None:  # (summed in place: a native step allocates nothing)
+        total = native_total
+    elif not losses:  # a rank without views in this step still takes part in the collectives and the update
         total = torch.zeros((), device=background.device)
     else:
         total = losses[0] if len(losses) == 1 else torch.stack(losses).sum()

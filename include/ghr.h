@@ -404,6 +404,74 @@ int ghr_loss_backward(void* stream, const ghr_loss_args* a, const float* maps, c
                       const float* grad_loss, float* d_image, float* d_mask, float* d_dir2d, float* d_orient_conf,
                       float* zero_plane_a, float* zero_plane_b);
 
+/* ---- one call per training view (src/train_gaussians.py:104-147: render, the four loss terms, backward) ------------------------
+ * Added without an ABI_VERSION bump: one new function and two new structs, no existing struct or signature changed.
+ * ghr_view_step enqueues, on the caller's one stream, what ghr_model_forward_stage1, ghr_forward_stage2 (at capacity R),
+ * ghr_loss_forward, ghr_loss_backward, ghr_render_backward and ghr_model_backward_segment enqueue when called in that order with
+ * the same values -- it calls those functions: the same kernels, launch shapes and arguments -- so that a binding states the
+ * sequence, the hand-over of the workspaces and the flag discipline once, as one struct.  Every buffer is the caller's; the call
+ * allocates nothing and never waits for the device.  The instance count lands in *R_host as after stage 1; the caller reads it
+ * when it likes (after count_event, or after the stream) and, when it exceeds R, discards and recomputes the view: the kernels
+ * stay inside their buffers (ghr_forward_stage2, ghr_backward).
+ * The whole struct is validated first: a refused call has launched nothing and ghr_last_error() names the field. */
+typedef struct ghr_sh_fold_args {   /* the arguments of ghr_sh_grad_from_views without a flag word */
+    int32_t P, sh_degree, sh_coeffs, n_views;
+    const float* xyz;
+    const float* campos;
+    int64_t campos_stride;
+    const float* g_views;
+    int64_t view_stride;
+    float* d_features_dc;
+    float* d_features_rest;
+    int32_t accumulate;
+} ghr_sh_fold_args;
+typedef struct ghr_view_step_args {
+    /* mode 0, row0 0, P > 0, debug 0, no camera gradients (cam_partial, fovx_dev / fovy_dev NULL).  Forward fields and backward
+     * fields both filled: dens_* / dens_img_ws / overflow_raises_flag / adam_fuse / d_rgb / img_ws_recycled mean what they mean
+     * for the single calls (dens_img_ws, when set, must be img_ws below). */
+    ghr_model_args model;
+    uint32_t R;                /* capacity in instances of bin_ws and of grad_scratch (ghr_forward_stage2) */
+    uint32_t* R_host;          /* pinned host word that receives the instance count */
+    void* geom_ws;             /* ghr_forward_sizes(P, W, H, 0) */
+    void* img_ws;
+    void* bin_ws;              /* ghr_binning_size(R, W, H); may be NULL when R == 0 */
+    int32_t* radii;            /* [P] */
+    float* means2D_out;        /* [P,3] or NULL */
+    float* render;             /* [10,H,W]: the packed rasterizer output */
+    /* W, H (must equal the model's), the four ground-truth pointers, the weights, unmasked_colours and gt_stats are read; the
+     * rendered planes (image, mask, dir2d, orient_conf) are taken from `render` (channels 0, 3, 5, 8) whatever the fields hold */
+    ghr_loss_args loss;
+    float* maps;               /* 9*H*W floats */
+    float* sums;               /* ghr_loss_sums_floats(W, H) floats */
+    float* loss_out;           /* device scalar */
+    const float* grad_loss;    /* device scalar dL/dloss, NULL = 1 */
+    float* d_pix;              /* [10,H,W] scratch: the loss backward fills it, the gradient walk reads it */
+    float* grad_scratch;       /* R gradient lines of GHR_GRAD_STRIDE floats; may be NULL when R == 0 */
+    int32_t prezero;           /* != 0: stage 2 zeroes the lines and the gradient walk is told so (ghr_backward, prezeroed) */
+    /* the outputs and modes of ghr_model_backward; d_features_dc / d_features_rest may be NULL where that call lets them */
+    float* d_means2D;
+    float* d_xyz;
+    float* d_log_scales;
+    float* d_rotations;
+    float* d_opacity_logit;
+    float* d_label_logit;
+    float* d_orient_conf_log;
+    float* d_features_dc;
+    float* d_features_rest;
+    int32_t accumulate;
+    int32_t* nan_flag;
+    /* optional, NULL = not there.  sh_fold: ghr_sh_grad_from_views with these arguments between the gradient walk and the
+     * projection backward (the view that carries the update folds the earlier views' d_rgb tables first).
+     * The three hipEvent_t: count_event is recorded behind stage 1 (the count has landed once it completes); acc_wait_event is
+     * waited for and acc_record_event recorded around {sh_fold, projection backward}, the only kernels of a view that
+     * read-modify-write buffers shared with the step's other views -- views on several streams chain exactly those. */
+    const ghr_sh_fold_args* sh_fold;
+    void* count_event;
+    void* acc_wait_event;
+    void* acc_record_event;
+} ghr_view_step_args;
+int ghr_view_step(void* stream, const ghr_view_step_args* v);
+
 /* ---- evaluation pass (src/train_gaussians.py:232-293 training_report; src/metrics.py:71-78; src/render_gaussians.py:31-68) ----
  * Metrics of one view on the packed [10,H,W] rasterizer output `renders` (channels: rgb 0-2, mask 3-4, dir2d 5-6, orientation
  * confidence 8) against gt_image [3,H,W], gt_mask [2,H,W], gt_orient_angle [1,H,W], gt_orient_conf [1,H,W]; all terms on

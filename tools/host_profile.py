@@ -1,5 +1,7 @@
 """Where the HOST's time per training step goes (round 6): cProfile over steps of a workload small enough that the GPU idles
-(cfg1), so that wall time = host time.    python tools/host_profile.py [steps]"""
+(cfg1), so that wall time = host time.    python tools/host_profile.py [steps] [--native]
+``--native``: the views as one ``ghr_view_step`` call each (``training_step(native=True)``; the first warm-up step, which has no
+capacity guess yet, still runs the Python way)."""
 import cProfile
 import io
 import os
@@ -12,12 +14,14 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gaussianhaircut_amd.scene.cameras import ring_cameras  # noqa: E402
 from gaussianhaircut_amd.scene.gaussian_model import OptimizationParams  # noqa: E402
-from gaussianhaircut_amd.trainer import make_ground_truth, training_step  # noqa: E402
+from gaussianhaircut_amd.trainer import last_step_path, make_ground_truth, training_step  # noqa: E402
 from gaussianhaircut_amd.utils import synthetic as syn  # noqa: E402
 
 
 def main():
-    K = int(sys.argv[1]) if len(sys.argv) > 1 else 400
+    argv = [a for a in sys.argv[1:] if a != "--native"]
+    native = True if "--native" in sys.argv[1:] else False
+    K = int(argv[0]) if argv else 400
     dev = torch.device("cuda:0")
     spec = syn.CONFIGS["cfg1"]
     opt = OptimizationParams()
@@ -31,17 +35,17 @@ def main():
         make_ground_truth(gt, pool, bg)
     model.training_setup(opt)
     for i in range(50):
-        training_step(model, [pool[i % 4]], bg, opt, i + 1)
+        training_step(model, [pool[i % 4]], bg, opt, i + 1, native=native)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(K):
-        training_step(model, [pool[i % 4]], bg, opt, 51 + i)
+        training_step(model, [pool[i % 4]], bg, opt, 51 + i, native=native)
     torch.cuda.synchronize()
-    print("HOST %.4f ms per step (cfg1: the GPU idles)" % (1e3 * (time.perf_counter() - t0) / K))
+    print("HOST %.4f ms per step (cfg1: the GPU idles; %s path)" % (1e3 * (time.perf_counter() - t0) / K, last_step_path()))
     pr = cProfile.Profile()
     pr.enable()
     for i in range(K):
-        training_step(model, [pool[i % 4]], bg, opt, 51 + K + i)
+        training_step(model, [pool[i % 4]], bg, opt, 51 + K + i, native=native)
     torch.cuda.synchronize()
     pr.disable()
     s = io.StringIO()
