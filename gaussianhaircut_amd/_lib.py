@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GHR_LIB_PATH") or os.path.join(CSRC, "libghr_hip.so")  # override: kernel experiments
 SOURCES = ["ghr_capi.hip"]
 HEADERS = ["ghr_device.h", "ghr_preprocess.h", "ghr_binning.h", "ghr_render_fwd.h", "ghr_render_bwd.h", "ghr_render_bwd2.h", "ghr_render_bwd3.h",
-           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_orient.h", "ghr_gt.h"]
+           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-fPIC",
                "-shared"]
 
@@ -155,6 +155,19 @@ class EvalArgs(ctypes.Structure):
                [("with_ssim", ctypes.c_int32)]
 
 
+class LatentLossArgs(ctypes.Structure):
+    """``ghr_latent_loss_args`` (include/ghr.h)."""
+    _fields_ = [("W", ctypes.c_int32), ("H", ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ("image", "mask0", "dir2d", "orient_conf", "gt_image", "gt_mask0",
+                                               "gt_orient_angle", "gt_orient_conf")] + \
+               [(n, ctypes.c_float) for n in ("w_l1", "w_mask", "w_orient")]
+
+
+def latent_loss_sums_floats(W: int, H: int) -> int:
+    """floats of the latent-stage loss kernels' ``sums`` for a W x H image (``ghr_latent_loss_sums_floats``)."""
+    return int(lib().ghr_latent_loss_sums_floats(int(W), int(H)))
+
+
 def loss_sums_floats(W: int, H: int) -> int:
     """floats of the loss kernels' ``sums`` scratch for a W x H image (``ghr_loss_sums_floats``)."""
     return int(lib().ghr_loss_sums_floats(int(W), int(H)))
@@ -176,7 +189,9 @@ EXPORTS = ["ghr_last_error", "ghr_abi_version", "ghr_forward_sizes", "ghr_binnin
            "ghr_camera_compose", "ghr_camera_compose_backward", "ghr_camera_adam_step",
            "ghr_eval_scratch_floats", "ghr_eval_metrics", "ghr_eval_products",
            "ghr_orient_dog_scratch_bytes", "ghr_orient_dog", "ghr_orient_bank_floats", "ghr_orient_gabor",
-           "ghr_resample_scratch_bytes", "ghr_resample_u8", "ghr_gt_assemble", "ghr_gt_resize_variance"]
+           "ghr_resample_scratch_bytes", "ghr_resample_u8", "ghr_gt_assemble", "ghr_gt_resize_variance",
+           "ghr_strand_points_build", "ghr_strand_points_build_backward", "ghr_strand_rows_expand", "ghr_strand_rows_reduce",
+           "ghr_latent_loss_sums_floats", "ghr_latent_loss_forward", "ghr_latent_loss_backward"]
 
 _lib = None
 
@@ -257,13 +272,21 @@ def lib() -> ctypes.CDLL:
     L.ghr_resample_u8.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp]
     L.ghr_gt_assemble.argtypes = [vp, i32, i32] + [vp] * 5 + [i32, i32, vp, vp, i32, i32, i32] + [vp] * 4
     L.ghr_gt_resize_variance.argtypes = [vp, i32, i32, vp, i32, i32, i32, vp]
+    L.ghr_strand_points_build.argtypes = [vp, i32, i32, vp, f32, vp, vp, vp, vp]
+    L.ghr_strand_points_build_backward.argtypes = [vp, i32, i32] + [vp] * 6
+    L.ghr_strand_rows_expand.argtypes = [vp, i32, i32, i32, vp, vp]
+    L.ghr_strand_rows_reduce.argtypes = [vp, i32, i32, i32, vp, vp]
+    L.ghr_latent_loss_sums_floats.argtypes = [i32, i32]
+    L.ghr_latent_loss_forward.argtypes = [vp, ctypes.POINTER(LatentLossArgs), vp, vp]
+    L.ghr_latent_loss_backward.argtypes = [vp, ctypes.POINTER(LatentLossArgs), vp, vp, vp]
     L.ghr_ws_inspect.argtypes = [i32, i32, i32, i32, u32, vp, vp, vp, ctypes.POINTER(WsView)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("ghr_last_error", "ghr_eval_scratch_floats", "ghr_orient_dog_scratch_bytes", "ghr_orient_bank_floats",
-                        "ghr_resample_scratch_bytes"):
+                        "ghr_resample_scratch_bytes", "ghr_latent_loss_sums_floats"):
             fn.restype = ctypes.c_int
-    for name in ("ghr_eval_scratch_floats", "ghr_orient_dog_scratch_bytes", "ghr_orient_bank_floats", "ghr_resample_scratch_bytes"):
+    for name in ("ghr_eval_scratch_floats", "ghr_orient_dog_scratch_bytes", "ghr_orient_bank_floats", "ghr_resample_scratch_bytes",
+                 "ghr_latent_loss_sums_floats"):
         getattr(L, name).restype = ctypes.c_size_t
     _lib = L
     return L

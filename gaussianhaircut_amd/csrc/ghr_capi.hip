@@ -29,6 +29,7 @@
 #include "ghr_render_bwd3.h"
 #include "ghr_render_fwd.h"
 #include "ghr_strands.h"
+#include "ghr_latent.h"
 
 namespace {
 
@@ -1599,6 +1600,164 @@ int ghr_ws_inspect(int32_t P, int32_t W, int32_t H, int32_t mode_b, uint32_t R, 
     out->keys = b.keys;
     out->point_list = b.point_list;
     return GHR_OK;
+}
+
+// ---- the latent-strand stage (include/ghr.h; csrc/ghr_latent.h) -----------------------------------------------------------
+namespace {
+int lt_bad(const char* fn, const char* what) { return fail(GHR_E_INVALID, fn, what); }
+inline bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+inline unsigned lt_blocks(size_t n) { return (unsigned)((n + GHR_LATENT_BLOCK - 1) / GHR_LATENT_BLOCK); }
+
+int lt_points_shape(const char* fn, int32_t S, int32_t L)
+{
+    if (S < 0) return lt_bad(fn, "S < 0");
+    if (L < 2) return lt_bad(fn, "L < 2");
+    if ((int64_t)S * L > (int64_t)INT32_MAX / 4) return lt_bad(fn, "S * L too large");
+    return GHR_OK;
+}
+int lt_rows_shape(const char* fn, int32_t S, int32_t n_seg, int32_t C)
+{
+    if (S < 0) return lt_bad(fn, "S < 0");
+    if (n_seg < 1) return lt_bad(fn, "n_seg < 1");
+    if (C < 1) return lt_bad(fn, "C < 1");
+    if ((int64_t)S * n_seg > (int64_t)INT32_MAX / 4) return lt_bad(fn, "S * n_seg too large");
+    return GHR_OK;
+}
+// the whole struct, before any launch
+int lt_loss_check(const char* fn, const ghr_latent_loss_args* l)
+{
+    if (!l) return lt_bad(fn, "args is NULL");
+    if (l->W <= 0 || l->H <= 0) return lt_bad(fn, "W * H == 0");
+    if ((int64_t)l->W * l->H > ((int64_t)1 << 30)) return lt_bad(fn, "W * H too large");
+    if (!l->image) return lt_bad(fn, "image is NULL");
+    if (!l->mask0) return lt_bad(fn, "mask0 is NULL");
+    if (!l->dir2d) return lt_bad(fn, "dir2d is NULL");
+    if (!l->gt_image) return lt_bad(fn, "gt_image is NULL");
+    if (!l->gt_mask0) return lt_bad(fn, "gt_mask0 is NULL");
+    if (!l->gt_orient_angle) return lt_bad(fn, "gt_orient_angle is NULL");
+    return GHR_OK;
+}
+ghr::LatentLossArgs lt_loss_args(const ghr_latent_loss_args* l, float* sums, const float* grad_loss, float* d_packed)
+{
+    return ghr::LatentLossArgs{l->W, l->H, l->image, l->mask0, l->dir2d, l->orient_conf, l->gt_image, l->gt_mask0,
+                               l->gt_orient_angle, l->gt_orient_conf, l->w_l1, l->w_mask, l->w_orient, sums, grad_loss, d_packed};
+}
+// the float4 form: 16-B aligned planes of H W % 4 == 0 pixels (GHR_LATENT_SCALAR: test / measurement knob, read per call)
+bool lt_loss_vec(const ghr_latent_loss_args* l, const void* extra)
+{
+    if (std::getenv("GHR_LATENT_SCALAR") != nullptr || (((size_t)l->W * (size_t)l->H) & 3u) != 0) return false;
+    const void* ps[] = {l->image, l->mask0, l->dir2d, l->orient_conf, l->gt_image, l->gt_mask0, l->gt_orient_angle,
+                        l->gt_orient_conf, extra};
+    for (const void* p : ps)
+        if (!al16(p)) return false;
+    return true;
+}
+inline size_t lt_loss_wgs(int32_t W, int32_t H)
+{
+    const size_t per = (size_t)GHR_LATENT_BLOCK * GHR_LATENT_QUAD;
+    return ((size_t)W * (size_t)H + per - 1) / per;
+}
+}  // namespace
+
+int ghr_strand_points_build(void* stream, int32_t S, int32_t L, const float* p, float scale, float* xyz, float* rotation,
+                            float* scaling, float* dir_rows)
+{
+    static const char* fn = "ghr_strand_points_build: %s";
+    if (int rc = lt_points_shape(fn, S, L)) return rc;
+    if (S == 0) return GHR_OK;
+    if (!p) return lt_bad(fn, "p is NULL");
+    if (!xyz) return lt_bad(fn, "xyz is NULL");
+    if (!rotation) return lt_bad(fn, "rotation is NULL");
+    if (!al16(rotation)) return lt_bad(fn, "rotation is not 16-B aligned");
+    if (!scaling) return lt_bad(fn, "scaling is NULL");
+    if (!dir_rows) return lt_bad(fn, "dir_rows is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::PointsArgs a{S, L, p, scale, xyz, rotation, scaling, dir_rows};
+    hipLaunchKernelGGL(ghr::k_points_build, dim3(lt_blocks((size_t)S * (L - 1))), dim3(GHR_LATENT_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+int ghr_strand_points_build_backward(void* stream, int32_t S, int32_t L, const float* p, const float* d_xyz,
+                                     const float* d_rotation, const float* d_scaling, const float* d_dir_rows, float* d_p)
+{
+    static const char* fn = "ghr_strand_points_build_backward: %s";
+    if (int rc = lt_points_shape(fn, S, L)) return rc;
+    if (S == 0) return GHR_OK;
+    if (!p) return lt_bad(fn, "p is NULL");
+    if (!d_p) return lt_bad(fn, "d_p is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::PointsBwdArgs a{S, L, p, d_xyz, d_rotation, d_scaling, d_dir_rows, d_p};
+    hipLaunchKernelGGL(ghr::k_points_build_bwd, dim3(lt_blocks((size_t)S * L)), dim3(GHR_LATENT_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+int ghr_strand_rows_expand(void* stream, int32_t S, int32_t n_seg, int32_t C, const float* src, float* dst)
+{
+    static const char* fn = "ghr_strand_rows_expand: %s";
+    if (int rc = lt_rows_shape(fn, S, n_seg, C)) return rc;
+    if (S == 0) return GHR_OK;
+    if (!src) return lt_bad(fn, "src is NULL");
+    if (!dst) return lt_bad(fn, "dst is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = (size_t)S * n_seg * C;
+    if ((C & 3) == 0 && al16(src) && al16(dst))
+        hipLaunchKernelGGL(ghr::k_rows_expand<4>, dim3(lt_blocks(n / 4)), dim3(GHR_LATENT_BLOCK), 0, s, n / 4, n_seg, C, src, dst);
+    else
+        hipLaunchKernelGGL(ghr::k_rows_expand<1>, dim3(lt_blocks(n)), dim3(GHR_LATENT_BLOCK), 0, s, n, n_seg, C, src, dst);
+    return finish(s, 0);
+}
+
+int ghr_strand_rows_reduce(void* stream, int32_t S, int32_t n_seg, int32_t C, const float* g, float* out)
+{
+    static const char* fn = "ghr_strand_rows_reduce: %s";
+    if (int rc = lt_rows_shape(fn, S, n_seg, C)) return rc;
+    if (S == 0) return GHR_OK;
+    if (!g) return lt_bad(fn, "g is NULL");
+    if (!out) return lt_bad(fn, "out is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = (size_t)S * C;
+    if ((C & 3) == 0 && al16(g) && al16(out))
+        hipLaunchKernelGGL(ghr::k_rows_reduce<4>, dim3(lt_blocks(n / 4)), dim3(GHR_LATENT_BLOCK), 0, s, n / 4, n_seg, C, g, out);
+    else
+        hipLaunchKernelGGL(ghr::k_rows_reduce<1>, dim3(lt_blocks(n)), dim3(GHR_LATENT_BLOCK), 0, s, n, n_seg, C, g, out);
+    return finish(s, 0);
+}
+
+size_t ghr_latent_loss_sums_floats(int32_t W, int32_t H)
+{
+    if (W <= 0 || H <= 0) return 0;
+    return GHR_LATENT_AUX + GHR_LATENT_TERMS * lt_loss_wgs(W, H);
+}
+
+int ghr_latent_loss_forward(void* stream, const ghr_latent_loss_args* l, float* sums, float* loss_out)
+{
+    static const char* fn = "ghr_latent_loss_forward: %s";
+    if (int rc = lt_loss_check(fn, l)) return rc;
+    if (!sums) return lt_bad(fn, "sums is NULL");
+    if (!al16(sums)) return lt_bad(fn, "sums is not 16-B aligned");
+    if (!loss_out) return lt_bad(fn, "loss_out is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    const ghr::LatentLossArgs a = lt_loss_args(l, sums, nullptr, nullptr);
+    const unsigned wgs = (unsigned)lt_loss_wgs(l->W, l->H);
+    if (lt_loss_vec(l, nullptr)) hipLaunchKernelGGL(ghr::k_latent_loss_fwd<1>, dim3(wgs), dim3(GHR_LATENT_BLOCK), 0, s, a);
+    else hipLaunchKernelGGL(ghr::k_latent_loss_fwd<0>, dim3(wgs), dim3(GHR_LATENT_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_latent_loss_fold, dim3(1), dim3(GHR_LATENT_BLOCK), 0, s, a, (uint32_t)wgs, loss_out);
+    return finish(s, 0);
+}
+
+int ghr_latent_loss_backward(void* stream, const ghr_latent_loss_args* l, const float* sums, const float* grad_loss,
+                             float* d_packed)
+{
+    static const char* fn = "ghr_latent_loss_backward: %s";
+    if (int rc = lt_loss_check(fn, l)) return rc;
+    if (!sums) return lt_bad(fn, "sums is NULL");
+    if (!d_packed) return lt_bad(fn, "d_packed is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    const ghr::LatentLossArgs a = lt_loss_args(l, const_cast<float*>(sums), grad_loss, d_packed);
+    const unsigned wgs = (unsigned)lt_loss_wgs(l->W, l->H);
+    if (lt_loss_vec(l, d_packed)) hipLaunchKernelGGL(ghr::k_latent_loss_bwd<1>, dim3(wgs), dim3(GHR_LATENT_BLOCK), 0, s, a);
+    else hipLaunchKernelGGL(ghr::k_latent_loss_bwd<0>, dim3(wgs), dim3(GHR_LATENT_BLOCK), 0, s, a);
+    return finish(s, 0);
 }
 
 }  // extern "C"

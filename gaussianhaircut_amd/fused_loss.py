@@ -148,3 +148,61 @@ def stage1_loss(renders, gt_image, gt_mask, gt_orient_angle, gt_orient_conf, w_l
     mask_colours)`` of this view (same result, 40 % less window arithmetic in the forward)."""
     return _Stage1LossPacked.apply(renders, gt_image, gt_mask, gt_orient_angle, gt_orient_conf, float(w_l1),
                                    float(w_ssim), float(w_mask), float(w_orient), not mask_colours, gt_stats)
+
+
+class _LatentLossPacked(torch.autograd.Function):
+    """The latent-strand stage's loss (csrc/ghr_latent.h) on the packed [10,H,W] output; backward writes the whole packed gradient."""
+
+    @staticmethod
+    def forward(ctx, renders, gt_image, gt_mask0, gt_angle, gt_oconf, w_l1, w_mask, w_orient, train_conf):
+        assert renders.is_cuda, "fused loss has no CPU path"
+        C, H, W = renders.shape
+        assert C == _lib.NUM_CHANNELS
+        r = _f32c(renders)
+        gi, gm, ga = _f32c(gt_image), _f32c(gt_mask0), _f32c(gt_angle)
+        gc = _f32c(gt_oconf) if gt_oconf is not None else None
+        dev = renders.device
+        with _on_device(dev):
+            sums = torch.empty(_lib.latent_loss_sums_floats(W, H), dtype=torch.float32, device=dev)
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+            a = _latent_args(W, H, r, gi, gm, ga, gc, (w_l1, w_mask, w_orient), train_conf)
+            _lib.check(_lib.lib().ghr_latent_loss_forward(_stream(), ctypes.byref(a), _ptr(sums),
+                                                          ctypes.c_void_p(loss.data_ptr())))
+        ctx.save_for_backward(r, gi, gm, ga, sums, *([gc] if gc is not None else []))
+        ctx.w, ctx.train_conf = (w_l1, w_mask, w_orient), bool(train_conf)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        r, gi, gm, ga, sums, *o = ctx.saved_tensors
+        _, H, W = r.shape
+        with _on_device(r.device):
+            d = torch.empty_like(r)
+            gl = _f32c(grad_loss)
+            a = _latent_args(W, H, r, gi, gm, ga, o[0] if o else None, ctx.w, ctx.train_conf)
+            _lib.check(_lib.lib().ghr_latent_loss_backward(_stream(), ctypes.byref(a), _ptr(sums),
+                                                           ctypes.c_void_p(gl.data_ptr()), _ptr(d)))
+        return d, None, None, None, None, None, None, None, None
+
+
+def _latent_args(W, H, r, gt_image, gt_mask0, gt_angle, gt_oconf, w, train_conf):
+    n = H * W
+    a = _lib.LatentLossArgs()
+    a.W, a.H = int(W), int(H)
+    a.image, a.mask0, a.dir2d = _off(r, 0, n), _off(r, 3, n), _off(r, 5, n)
+    a.orient_conf = _off(r, 8, n) if train_conf else None
+    a.gt_image, a.gt_mask0, a.gt_orient_angle = _ptr(gt_image), _ptr(gt_mask0), _ptr(gt_angle)
+    a.gt_orient_conf = _ptr(gt_oconf) if gt_oconf is not None else None
+    a.w_l1, a.w_mask, a.w_orient = [float(x) for x in w]
+    return a
+
+
+def latent_loss(renders_packed, cam, opt, scale: float = 1.0):
+    """The three image terms of src/train_latent_strands.py:130-152 on the packed [10,H,W] rasterizer output: L1 on the whole
+    image, ``l1_loss(mask[:1], gt_mask[:1])``, the orientation loss (confidence only with ``opt.train_orient_conf``, weight
+    ``gt_orient_conf`` only with ``opt.use_gt_orient_conf``), each dropped when it is NaN; no SSIM.  The generator's term is the
+    caller's (``trainer.latent_view_loss``)."""
+    return _LatentLossPacked.apply(renders_packed, cam.original_image, cam.original_mask[:1], cam.original_orient_angle,
+                                   cam.original_orient_conf if opt.use_gt_orient_conf else None,
+                                   float(opt.lambda_dl1) * scale, float(opt.lambda_dmask) * scale,
+                                   float(opt.lambda_dorient) * scale, bool(opt.train_orient_conf))

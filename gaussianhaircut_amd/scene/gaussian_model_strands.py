@@ -158,8 +158,13 @@ class GaussianModelStrands(GaussianModel):
         ]
 
 
-# The reference's latent stage (src/scene/gaussian_model_latent_strands.py) has the same projection helpers line for line;
-# what differs is where the strand polylines come from (a latent texture decoded by an un-vendored strand prior: out of
-# scope).  For the hot path the two classes are the same object.
-GaussianModelLatentStrands = GaussianModelStrands
+# The reference's latent stage (src/scene/gaussian_model_latent_strands.py) has the same projection helpers line for line; its
+# strands arrive as points out of a generator: GaussianModelLatentStrands, in scene/gaussian_model_latent_strands.py.
+def __getattr__(name):
+    if name == "GaussianModelLatentStrands":
+        from .gaussian_model_latent_strands import GaussianModelLatentStrands
+        return GaussianModelLatentStrands
+    raise AttributeError(name)
+
+
 GaussianModelCurves = GaussianModelStrands  # the reference's class name in this module (src/scene/gaussian_model_strands.py:31)

@@ -579,6 +579,92 @@ def strand_training_step(gaussians, gaussians_hair, cams: List, background, opt,
     return losses[0] if len(losses) == 1 else torch.stack(losses).sum()
 
 
+def latent_view_loss(render_pkg, cam, opt, l_diff=None, fused=None):
+    """The latent-strand stage's loss (src/train_latent_strands.py:130-152): L1 on the whole image, L1 on mask channel 0, the
+    orientation loss and the generator's scalar ``l_diff`` (``gaussians_hair.LDiff``), each dropped when it is NaN; no SSIM.
+    On a ROCm device the three image terms are one HIP op (csrc/ghr_latent.h); the generator's term and its NaN rule are added
+    on a device scalar.  Nothing is read back.  (A dropped ``l_diff`` receives a ZERO cotangent here, not a cut graph: a generator
+    whose backward turns 0 into NaN needs the form of ``latent_strand_training_step``.)"""
+    image, mask = render_pkg["render"], render_pkg["mask"]
+    gt_image, gt_mask = cam.original_image, cam.original_mask
+    if fused is None:
+        fused = image.is_cuda
+    if fused and getattr(render_pkg, "renders_packed", None) is not None:
+        from .fused_loss import latent_loss
+        loss = latent_loss(render_pkg.renders_packed, cam, opt)
+    else:
+        LCE = l1_loss(mask[:1], gt_mask[:1])
+        Ll1 = l1_loss(image, gt_image)
+        w = torch.ones_like(gt_mask[:1])
+        if opt.use_gt_orient_conf:
+            w = w * cam.original_orient_conf
+        conf = render_pkg["orient_conf"] if opt.train_orient_conf else None
+        LOR = or_loss(render_pkg["orient_angle"], cam.original_orient_angle, conf, weight=w, mask=gt_mask[:1])
+        # :143-145 decide on the host; here the flag stays on the device: value 0 and a zero cotangent for a NaN term
+        zero = torch.zeros_like(Ll1)
+        loss = _drop_nan(Ll1, zero) * opt.lambda_dl1 + _drop_nan(LCE, zero) * opt.lambda_dmask + \
+            _drop_nan(LOR, zero) * opt.lambda_dorient
+    if l_diff is not None:
+        loss = loss + _drop_nan(l_diff.to(loss.dtype), torch.zeros_like(loss)) * getattr(opt, "lambda_dsds", 0.0)
+    return loss
+
+
+class _DropNan(torch.autograd.Function):
+    """``x if not isnan(x) else zero`` of a scalar, with a zero gradient for a dropped x (train_latent_strands.py:143-146), decided
+    on the device."""
+
+    @staticmethod
+    def forward(ctx, x, zero):
+        bad = torch.isnan(x)
+        ctx.save_for_backward(bad)
+        return torch.where(bad, zero, x)
+
+    @staticmethod
+    def backward(ctx, g):
+        (bad,) = ctx.saved_tensors
+        return torch.where(bad, torch.zeros_like(g), g), None
+
+
+def _drop_nan(x, zero):
+    return _DropNan.apply(x, zero)
+
+
+def latent_strand_training_step(gaussians, gaussians_hair, cams: List, background, opt, iteration: int, pipe=PIPE):
+    """One iteration of the latent-strand stage (src/train_latent_strands.py:103-164): the generator's strands -> segment
+    Gaussians, render head + hair, loss, backward, the NaN rule over the first parameter group, the caller's optimizer.
+    ``cams`` holds the iteration's view (the reference draws one).  Returns the detached device loss; nothing is read back
+    except by the reference's own NaN test on the gradients."""
+    gaussians_hair.initialize_gaussians_hair(iteration)
+    gaussians_hair.update_learning_rate(iteration)
+    cam = cams[0]
+    pkg = render_hair(cam, gaussians, gaussians_hair, pipe, background)
+    loss = latent_view_loss(pkg, cam, opt)
+    l_diff, o = gaussians_hair.LDiff, gaussians_hair.optimizer
+    if l_diff is None:
+        loss.backward(gradient=_one_like(loss))
+    else:
+        # :142, 146: the generator's term is dropped when it is NaN.  The reference decides on the host and cuts the graph; a
+        # zero cotangent sent into a graph that made a NaN comes out as 0 * NaN.  So the term is differentiated on its own and
+        # the select is made on its parameter gradients, on the device.
+        w = float(getattr(opt, "lambda_dsds", 0.0))
+        params = [q for g in o.param_groups for q in g['params'] if q.requires_grad]
+        loss.backward(gradient=_one_like(loss), retain_graph=True)
+        bad = torch.isnan(l_diff.detach())
+        for q, g in zip(params, torch.autograd.grad(l_diff, params, allow_unused=True)):
+            if g is not None:
+                g = torch.where(bad, torch.zeros_like(g), g * w)
+                q.grad = g if q.grad is None else q.grad.add_(g)
+        loss = loss.detach() + torch.where(bad, torch.zeros_like(loss), l_diff.detach().to(loss.dtype)) * w
+    if iteration < opt.iterations:
+        for param in o.param_groups[0]['params']:  # :157-162, call for call
+            if param.grad is not None and param.grad.isnan().any():
+                o.zero_grad()
+                print('NaN during backprop was found, skipping iteration...')
+        o.step()
+        o.zero_grad(set_to_none=True)
+    return loss.detach()
+
+
 def _world_size() -> int:
     import torch.distributed as dist
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1

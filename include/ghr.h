@@ -688,6 +688,47 @@ int ghr_gt_assemble(void* stream, int32_t W, int32_t H, const uint8_t* image, co
 int ghr_gt_resize_variance(void* stream, int32_t W, int32_t H, const float* var, int32_t var_w, int32_t var_h, int32_t via_half,
                            float* out);
 
+/* ---- the latent-strand stage (src/train_latent_strands.py:103-164; src/scene/gaussian_model_latent_strands.py:451-499)
+ * Added without an ABI_VERSION bump: seven new functions and one new struct, no existing struct or signature changed.
+ * ghr_strand_points_build: strands given as POINTS p [S][L][3], L >= 2 (no upper bound), n_seg = L - 1; row s n_seg + k is
+ * segment k of strand s (the layout of ghr_strand_build): xyz = (p[k+1] + p[k]) * 0.5 and dir_rows = p[k+1] - p[k], bit for bit
+ * the PyTorch expressions; rotation [.][4] (16-B aligned) and scaling [.][3] as ghr_strand_build makes them from the direction.
+ * ghr_strand_points_build_backward: d_p [S][L][3] is ASSIGNED; each cotangent may be NULL, of d_scaling only column 0 is read.
+ * Point j gets  d_xyz / 2 + g  of segment j - 1 first, then  d_xyz / 2 - g  of segment j, g = the segment's whole direction
+ * cotangent (rotation, scaling[0], d_dir_rows).  No atomics: the same input gives the same bytes on every run.
+ * ghr_strand_rows_expand: dst [S n_seg][C] = src [S][C] repeated over a strand's segments (C >= 1);
+ * ghr_strand_rows_reduce: out [S][C] = the sum of the strand's n_seg rows of g in index order, one fp32 accumulator each.
+ * ghr_latent_loss_*: loss = w_l1 mean_{3HW}|image - gt_image| + w_mask mean_{HW}|mask0 - gt_mask0| + w_orient or_loss(angle(dir2d),
+ * gt_orient_angle, orient_conf, weight = gt_orient_conf, mask = gt_mask0) (src/utils/loss_utils.py:31-47); each term is dropped
+ * (value 0, gradient 0) exactly when it is NaN.  The rendered planes may point into one packed [10][H][W] output.
+ * sums: ghr_latent_loss_sums_floats(W, H) floats, 16-B aligned, nothing to pre-fill: {Ll1, LCE, LOR, their three NaN flags, the
+ * sum of the orientation weights, 0} then one slot {l1, ce, or_num, or_den} per 1024 pixels.  The backward recomputes pointwise
+ * from the same args and `sums`, and writes ALL ten planes of d_packed [10][H][W] (image 0-2, mask0 3, dir2d 5-6, confidence 8;
+ * zeros elsewhere); grad_loss: device scalar or NULL (1).  The whole struct is checked before any launch and ghr_last_error()
+ * names the field.  A refused call launches nothing. */
+typedef struct ghr_latent_loss_args {
+    int32_t W, H;
+    const float* image;            /* [3][H][W] rendered */
+    const float* mask0;            /* [1][H][W] rendered hair label */
+    const float* dir2d;            /* [2][H][W] rendered 2D direction */
+    const float* orient_conf;      /* [1][H][W] rendered confidence, or NULL: train_orient_conf = False */
+    const float* gt_image;         /* [3][H][W] */
+    const float* gt_mask0;         /* [1][H][W] */
+    const float* gt_orient_angle;  /* [1][H][W] */
+    const float* gt_orient_conf;   /* [1][H][W], or NULL: weight 1 (use_gt_orient_conf = False) */
+    float w_l1, w_mask, w_orient;
+} ghr_latent_loss_args;
+int ghr_strand_points_build(void* stream, int32_t S, int32_t L, const float* p, float scale, float* xyz, float* rotation,
+                            float* scaling, float* dir_rows);
+int ghr_strand_points_build_backward(void* stream, int32_t S, int32_t L, const float* p, const float* d_xyz,
+                                     const float* d_rotation, const float* d_scaling, const float* d_dir_rows, float* d_p);
+int ghr_strand_rows_expand(void* stream, int32_t S, int32_t n_seg, int32_t C, const float* src, float* dst);
+int ghr_strand_rows_reduce(void* stream, int32_t S, int32_t n_seg, int32_t C, const float* g, float* out);
+size_t ghr_latent_loss_sums_floats(int32_t W, int32_t H);
+int ghr_latent_loss_forward(void* stream, const ghr_latent_loss_args* l, float* sums, float* loss_out);
+int ghr_latent_loss_backward(void* stream, const ghr_latent_loss_args* l, const float* sums, const float* grad_loss,
+                             float* d_packed);
+
 /* Introspection for tests (device pointers into the workspaces; layout is otherwise private). */
 typedef struct ghr_ws_view {
     const float* rec;          /* [P][16]: x, y, conic a, b, c, opacity, features[10] */
