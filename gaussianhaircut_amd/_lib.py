@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GHR_LIB_PATH") or os.path.join(CSRC, "libghr_hip.so")  # override: kernel experiments
 SOURCES = ["ghr_capi.hip"]
 HEADERS = ["ghr_device.h", "ghr_preprocess.h", "ghr_binning.h", "ghr_render_fwd.h", "ghr_render_bwd.h", "ghr_render_bwd2.h", "ghr_render_bwd3.h",
-           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h"]
+           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-fPIC",
                "-shared"]
 
@@ -163,6 +163,11 @@ class LatentLossArgs(ctypes.Structure):
                [(n, ctypes.c_float) for n in ("w_l1", "w_mask", "w_orient")]
 
 
+class SharedFeatures(ctypes.Structure):
+    """``ghr_shared_features`` (include/ghr.h): a segment whose SH coefficients are stored once per strand."""
+    _fields_ = [("n_strands", ctypes.c_int32), ("rows_per_strand", ctypes.c_int32)]
+
+
 def latent_loss_sums_floats(W: int, H: int) -> int:
     """floats of the latent-stage loss kernels' ``sums`` for a W x H image (``ghr_latent_loss_sums_floats``)."""
     return int(lib().ghr_latent_loss_sums_floats(int(W), int(H)))
@@ -191,7 +196,8 @@ EXPORTS = ["ghr_last_error", "ghr_abi_version", "ghr_forward_sizes", "ghr_binnin
            "ghr_orient_dog_scratch_bytes", "ghr_orient_dog", "ghr_orient_bank_floats", "ghr_orient_gabor",
            "ghr_resample_scratch_bytes", "ghr_resample_u8", "ghr_gt_assemble", "ghr_gt_resize_variance",
            "ghr_strand_points_build", "ghr_strand_points_build_backward", "ghr_strand_rows_expand", "ghr_strand_rows_reduce",
-           "ghr_latent_loss_sums_floats", "ghr_latent_loss_forward", "ghr_latent_loss_backward"]
+           "ghr_latent_loss_sums_floats", "ghr_latent_loss_forward", "ghr_latent_loss_backward",
+           "ghr_model_forward_segment_shared", "ghr_model_backward_segment_shared", "ghr_shared_sh_fold"]
 
 _lib = None
 
@@ -279,6 +285,11 @@ def lib() -> ctypes.CDLL:
     L.ghr_latent_loss_sums_floats.argtypes = [i32, i32]
     L.ghr_latent_loss_forward.argtypes = [vp, ctypes.POINTER(LatentLossArgs), vp, vp]
     L.ghr_latent_loss_backward.argtypes = [vp, ctypes.POINTER(LatentLossArgs), vp, vp, vp]
+    L.ghr_model_forward_segment_shared.argtypes = [vp, ctypes.POINTER(ModelArgs), ctypes.POINTER(SharedFeatures), i32, i32,
+                                                   vp, vp, vp, vp]
+    L.ghr_model_backward_segment_shared.argtypes = [vp, ctypes.POINTER(ModelArgs), ctypes.POINTER(SharedFeatures), i32] + \
+        [vp] * 13 + [vp, u32, vp, u32, vp]
+    L.ghr_shared_sh_fold.argtypes = [vp, ctypes.POINTER(SharedFeatures), i32, i32] + [vp] * 6
     L.ghr_ws_inspect.argtypes = [i32, i32, i32, i32, u32, vp, vp, vp, ctypes.POINTER(WsView)]
     for name in EXPORTS:
         fn = getattr(L, name)

@@ -30,6 +30,7 @@
 #include "ghr_render_fwd.h"
 #include "ghr_strands.h"
 #include "ghr_latent.h"
+#include "ghr_shared.h"
 
 namespace {
 
@@ -486,8 +487,49 @@ int fill_adam_fuse(const ghr::ModelArgs& a, const ghr_adam_fuse* af, int32_t acc
 }
 }  // namespace
 
+namespace {
+// Everything a shared-feature segment call refuses, before anything else is looked at (and long before a launch).
+int check_shared(const char* who, const ghr_model_args* m, const ghr_shared_features* sf)
+{
+    if (!m) return fail(GHR_E_INVALID, "ghr_model_args is NULL");
+    if (!sf) return fail(GHR_E_INVALID, "%s: ghr_shared_features is NULL", who);
+    if (m->mode != 1) return fail(GHR_E_INVALID, "%s: mode must be 1 (explicit Gaussians)", who);
+    if (m->sh_coeffs != 1 && m->sh_coeffs != 4 && m->sh_coeffs != 9 && m->sh_coeffs != 16)
+        return fail(GHR_E_INVALID, "%s: sh_coeffs must be 1, 4, 9 or 16", who);
+    if (sf->rows_per_strand < 1) return fail(GHR_E_INVALID, "%s: rows_per_strand must be >= 1", who);
+    if (sf->n_strands < 0 || (long long)sf->n_strands * sf->rows_per_strand != (long long)m->P)
+        return fail(GHR_E_INVALID, "%s: P must equal n_strands * rows_per_strand", who);
+    if (m->adam_fuse) return fail(GHR_E_INVALID, "%s: adam_fuse is not available for per-strand features", who);
+    if (m->cam_only) return fail(GHR_E_INVALID, "%s: cam_only is not available for per-strand features", who);
+    if (m->d_rgb) return fail(GHR_E_INVALID, "%s: d_rgb is set by the call itself (pass d_rgb_ws)", who);
+    return GHR_OK;
+}
+
+// sf != NULL: features_dc / features_rest of `m` are per strand (checked by check_shared)
+int forward_segment(const ghr_model_args* m, const ghr_shared_features* sf, void* stream, int32_t rows_total, int32_t first,
+                    void* geom_ws, void* img_ws, int32_t* radii, float* means2D_out);
+}  // namespace
+
 int ghr_model_forward_segment(void* stream, const ghr_model_args* m, int32_t rows_total, int32_t first, void* geom_ws,
                               void* img_ws, int32_t* radii, float* means2D_out)
+{
+    return forward_segment(m, nullptr, stream, rows_total, first, geom_ws, img_ws, radii, means2D_out);
+}
+
+int ghr_model_forward_segment_shared(void* stream, const ghr_model_args* m, const ghr_shared_features* sf, int32_t rows_total,
+                                     int32_t first, void* geom_ws, void* img_ws, int32_t* radii, float* means2D_out)
+{
+    if (int rc = check_shared("ghr_model_forward_segment_shared", m, sf)) return rc;
+    if (m->P == 0) {  // nothing to project, nothing launched (not even the `first` segment's counter reset)
+        ghr::ModelArgs a;
+        return fill_model(m, &a);
+    }
+    return forward_segment(m, sf, stream, rows_total, first, geom_ws, img_ws, radii, means2D_out);
+}
+
+namespace {
+int forward_segment(const ghr_model_args* m, const ghr_shared_features* sf, void* stream, int32_t rows_total, int32_t first,
+                    void* geom_ws, void* img_ws, int32_t* radii, float* means2D_out)
 {
     ghr::ModelArgs a;
     if (int rc = fill_model(m, &a)) return rc;
@@ -521,10 +563,17 @@ int ghr_model_forward_segment(void* stream, const ghr_model_args* m, int32_t row
     if (a.P == 0) return finish(s, m->debug);
     a.rec = g.rec; a.depths = g.depths; a.rects = g.rects; a.radii = radii; a.means2D = means2D_out;
     a.tile_count = im.tile_count; a.slot_blk = g.slot_blk; a.pos = g.pos;
-    if (a.sh_coeffs > 1) hipLaunchKernelGGL(ghr::k_project<true>, dim3(n_blocks(a.P)), dim3(GHR_BLOCK), 0, s, a);
+    if (sf) {
+        const ghr::SharedFeat k{sf->n_strands, sf->rows_per_strand, a.features_dc, a.features_rest};
+        a.features_dc = a.xyz;  // load_raw reads 3 floats per ROW there; the kernel replaces them by the strand's
+        a.features_rest = nullptr;
+        if (a.sh_coeffs > 1) hipLaunchKernelGGL(ghr::k_shared_proj_fwd<true>, dim3(n_blocks(a.P)), dim3(GHR_BLOCK), 0, s, a, k);
+        else hipLaunchKernelGGL(ghr::k_shared_proj_fwd<false>, dim3(n_blocks(a.P)), dim3(GHR_BLOCK), 0, s, a, k);
+    } else if (a.sh_coeffs > 1) hipLaunchKernelGGL(ghr::k_project<true>, dim3(n_blocks(a.P)), dim3(GHR_BLOCK), 0, s, a);
     else hipLaunchKernelGGL(ghr::k_project<false>, dim3(n_blocks(a.P)), dim3(GHR_BLOCK), 0, s, a);
     return finish(s, m->debug);
 }
+}  // namespace
 
 int ghr_model_forward_finish(void* stream, int32_t rows_total, int32_t W, int32_t H, int32_t debug, void* geom_ws,
                              void* img_ws, uint32_t* R_host)
@@ -580,12 +629,73 @@ int ghr_render_backward(void* stream, int32_t rows_total, int32_t W, int32_t H, 
     return finish(s, 0);
 }
 
+namespace {
+// sf != NULL (checked by check_shared): the projection backward in factored form into d_rgb_ws, then the per-strand fold into
+// d_features_dc [S,1,3] / d_features_rest [S,K-1,3]
+int backward_segment(const ghr_model_args* m, const ghr_shared_features* sf, float* d_rgb_ws, void* stream, int32_t rows_total,
+                     const int32_t* radii, const void* geom_ws, const float* grad_scratch, float* d_means2D, float* d_xyz,
+                     float* d_log_scales, float* d_rotations, float* d_opacity_logit, float* d_label_logit,
+                     float* d_orient_conf_log, float* d_features_dc, float* d_features_rest, float* d_dir3d,
+                     int32_t accumulate, int32_t* nan_flag, uint32_t grad_rows, const void* bin_ws, uint32_t R);
+}  // namespace
+
 int ghr_model_backward_segment(void* stream, const ghr_model_args* m, int32_t rows_total, const int32_t* radii,
                                const void* geom_ws, const float* grad_scratch, float* d_means2D, float* d_xyz,
                                float* d_log_scales, float* d_rotations, float* d_opacity_logit, float* d_label_logit,
                                float* d_orient_conf_log, float* d_features_dc, float* d_features_rest, float* d_dir3d,
                                int32_t accumulate, int32_t* nan_flag, uint32_t grad_rows, const void* bin_ws,
                                uint32_t R)
+{
+    return backward_segment(m, nullptr, nullptr, stream, rows_total, radii, geom_ws, grad_scratch, d_means2D, d_xyz, d_log_scales,
+                            d_rotations, d_opacity_logit, d_label_logit, d_orient_conf_log, d_features_dc, d_features_rest,
+                            d_dir3d, accumulate, nan_flag, grad_rows, bin_ws, R);
+}
+
+int ghr_model_backward_segment_shared(void* stream, const ghr_model_args* m, const ghr_shared_features* sf, int32_t rows_total,
+                                      const int32_t* radii, const void* geom_ws, const float* grad_scratch, float* d_means2D,
+                                      float* d_xyz, float* d_log_scales, float* d_rotations, float* d_opacity_logit,
+                                      float* d_label_logit, float* d_orient_conf_log, float* d_features_dc,
+                                      float* d_features_rest, float* d_dir3d, int32_t* nan_flag, uint32_t grad_rows,
+                                      const void* bin_ws, uint32_t R, float* d_rgb_ws)
+{
+    static const char* who = "ghr_model_backward_segment_shared";
+    if (int rc = check_shared(who, m, sf)) return rc;
+    if (m->P > 0 && !d_rgb_ws) return fail(GHR_E_INVALID, "%s: d_rgb_ws is NULL", who);
+    if (m->P > 0 && !d_features_dc) return fail(GHR_E_INVALID, "%s: d_features_dc is NULL", who);
+    if (m->P > 0 && m->sh_coeffs > 1 && !d_features_rest) return fail(GHR_E_INVALID, "%s: d_features_rest is NULL", who);
+    return backward_segment(m, sf, d_rgb_ws, stream, rows_total, radii, geom_ws, grad_scratch, d_means2D, d_xyz, d_log_scales,
+                            d_rotations, d_opacity_logit, d_label_logit, d_orient_conf_log, d_features_dc, d_features_rest,
+                            d_dir3d, 0, nan_flag, grad_rows, bin_ws, R);
+}
+
+int ghr_shared_sh_fold(void* stream, const ghr_shared_features* sf, int32_t sh_degree, int32_t sh_coeffs, const float* xyz,
+                       const float* campos, const float* d_rgb, float* d_features_dc, float* d_features_rest, int32_t* nan_flag)
+{
+    static const char* who = "ghr_shared_sh_fold";
+    if (!sf) return fail(GHR_E_INVALID, "%s: ghr_shared_features is NULL", who);
+    if (sf->rows_per_strand < 1 || sf->n_strands < 0 || (long long)sf->n_strands * sf->rows_per_strand > 0x7fffffffLL)
+        return fail(GHR_E_INVALID, "%s: bad n_strands / rows_per_strand", who);
+    if (sh_coeffs != 1 && sh_coeffs != 4 && sh_coeffs != 9 && sh_coeffs != 16)
+        return fail(GHR_E_INVALID, "%s: sh_coeffs must be 1, 4, 9 or 16", who);
+    if (sh_degree < 0 || (sh_degree + 1) * (sh_degree + 1) > sh_coeffs) return fail(GHR_E_INVALID, "%s: bad sh_degree", who);
+    if (sf->n_strands == 0) return GHR_OK;
+    if (!xyz || !campos || !d_rgb || !d_features_dc || (sh_coeffs > 1 && !d_features_rest))
+        return fail(GHR_E_INVALID, "%s: NULL buffer", who);
+    ghr::SharedFoldArgs fa;
+    fa.S = sf->n_strands; fa.n_seg = sf->rows_per_strand; fa.sh_degree = sh_degree; fa.sh_coeffs = sh_coeffs;
+    fa.xyz = xyz; fa.campos = campos; fa.d_rgb = d_rgb; fa.d_dc = d_features_dc; fa.d_rest = d_features_rest;
+    fa.nan_flag = nan_flag;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ghr::k_shared_sh_fold, dim3(fa.S), dim3(GHR_PBW_BLOCK), 0, s, fa);
+    return finish(s, 0);
+}
+
+namespace {
+int backward_segment(const ghr_model_args* m, const ghr_shared_features* sf, float* d_rgb_ws, void* stream, int32_t rows_total,
+                     const int32_t* radii, const void* geom_ws, const float* grad_scratch, float* d_means2D, float* d_xyz,
+                     float* d_log_scales, float* d_rotations, float* d_opacity_logit, float* d_label_logit,
+                     float* d_orient_conf_log, float* d_features_dc, float* d_features_rest, float* d_dir3d,
+                     int32_t accumulate, int32_t* nan_flag, uint32_t grad_rows, const void* bin_ws, uint32_t R)
 {
     ghr::ModelArgs a;
     if (int rc = fill_model(m, &a)) return rc;
@@ -600,7 +710,7 @@ int ghr_model_backward_segment(void* stream, const ghr_model_args* m, int32_t ro
         return fail(GHR_E_INVALID, "ghr_model_backward_segment: the segment's camera columns exceed cam_slots");
     if (!radii || !geom_ws)
         return fail(GHR_E_INVALID, "ghr_model_backward_segment: NULL buffer");
-    const bool factored_sh = m->d_rgb != nullptr;  // ABI 19: the SH gradients leave as d_rgb, their own buffers may be NULL
+    const bool factored_sh = m->d_rgb != nullptr || sf != nullptr;  // ABI 19: the SH gradients leave as d_rgb, their own buffers may be NULL
     // (the SH gradient buffers may be NULL when nothing is stored there: the factored form, or the update carried by this
     // call -- ghr_adam_fuse -- without earlier views' gradients to add)
     const bool sh_unstored = factored_sh || (m->adam_fuse != nullptr && !accumulate);
@@ -623,6 +733,7 @@ int ghr_model_backward_segment(void* stream, const ghr_model_args* m, int32_t ro
     mg.d_rotations = d_rotations; mg.d_opacity_logit = d_opacity_logit; mg.d_label_logit = d_label_logit;
     mg.d_orient_conf_log = d_orient_conf_log; mg.d_features_dc = d_features_dc; mg.d_features_rest = d_features_rest;
     mg.d_rgb = m->d_rgb;
+    if (sf) { mg.d_rgb = d_rgb_ws; mg.d_features_dc = mg.d_features_rest = nullptr; }
     mg.d_dir3d = a.mode == 1 ? d_dir3d : nullptr;
     mg.accumulate = accumulate; mg.nan_flag = cam_only ? nullptr : nan_flag;
     mg.cam_partial = m->cam_partial; mg.cam_slot0 = (uint32_t)m->cam_slot0; mg.cam_stride = (uint32_t)m->cam_slots;
@@ -651,7 +762,16 @@ int ghr_model_backward_segment(void* stream, const ghr_model_args* m, int32_t ro
         mg.dens_count = im.R_dev; mg.dens_cap = R; mg.overflow_is_bad = 1;
     }
     const dim3 grid((a.P + GHR_PBW_BLOCK - 1) / GHR_PBW_BLOCK), block(GHR_PBW_BLOCK);
-    if (af) {
+    if (sf) {
+        const ghr::SharedFeat k{sf->n_strands, sf->rows_per_strand, a.features_dc, a.features_rest};
+        const float *xyz = a.xyz, *campos = a.campos;
+        const int deg = a.sh_degree, K = a.sh_coeffs;
+        a.features_dc = a.xyz;  // (see forward_segment)
+        a.features_rest = nullptr;
+        if (mg.cam_partial) hipLaunchKernelGGL(ghr::k_shared_proj_bwd<true>, grid, block, 0, s, a, mg, k);
+        else hipLaunchKernelGGL(ghr::k_shared_proj_bwd<false>, grid, block, 0, s, a, mg, k);
+        if (int rc = ghr_shared_sh_fold(stream, sf, deg, K, xyz, campos, d_rgb_ws, d_features_dc, d_features_rest, nan_flag)) return rc;
+    } else if (af) {
         if (mg.cam_partial) hipLaunchKernelGGL((ghr::k_project_bwd<true, true>), grid, block, 0, s, a, mg);
         else hipLaunchKernelGGL((ghr::k_project_bwd<false, true>), grid, block, 0, s, a, mg);
         // (a strand segment leaves the finish to the caller -- ghr_adam_fused_finish -- who first steps the groups whose
@@ -663,6 +783,7 @@ int ghr_model_backward_segment(void* stream, const ghr_model_args* m, int32_t ro
     else hipLaunchKernelGGL((ghr::k_project_bwd<false, false>), grid, block, 0, s, a, mg);
     return finish(s, m->debug);
 }
+}  // namespace
 
 int ghr_adam_fused_finish(void* stream, const ghr_adam_fuse* af)
 {

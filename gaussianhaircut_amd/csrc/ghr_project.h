@@ -673,7 +673,9 @@ GHR_HD void project_bwd_geom(const ModelArgs& a, const RawIn& in, int radius, co
 
 // ---- SH colour (clamp_min(sh + .5, 0)) incl. the view-direction dependence on xyz (added to o.dxyz behind the geometry
 // terms).  d_rest may alias rest: every element is read (cf) before it is overwritten, channel by channel.
-template <bool CAM>
+// STORE = false: the products basis_k x gch are not stored at all and d_rest is not touched (the factored form of a segment whose
+// `rest` block is SHARED by the rows of a strand, ghr_shared.h: a store through the block would clobber a neighbour's coefficients).
+template <bool CAM, bool STORE = true>
 GHR_HD void project_bwd_sh(const ModelArgs& a, const RawIn& in, int radius, const float* ga, const float* rest, float* d_rest,
                            ProjBwdOut& o, float* cam)
 {
@@ -710,7 +712,7 @@ GHR_HD void project_bwd_sh(const ModelArgs& a, const RawIn& in, int radius, cons
                 ddc[ch] = basis[0] * gch;
 #pragma unroll
                 for (int k = 0; k < GHR_SH_MAX; k++) {
-                    if (k > 0 && k < K) d_rest[(k - 1) * 3 + ch] = basis[k] * gch;
+                    if (STORE && k > 0 && k < K) d_rest[(k - 1) * 3 + ch] = basis[k] * gch;
                     vk[k] += gch * cf[k];
                 }
             }
@@ -723,7 +725,8 @@ GHR_HD void project_bwd_sh(const ModelArgs& a, const RawIn& in, int radius, cons
             cpg0 = -dd[0]; cpg1 = -dd[1]; cpg2 = -dd[2];  // dir = xyz - camera_center (gaussian_renderer/__init__.py:59)
         }
     } else {
-        for (int k = 0; k < 3 * (K - 1); k++) d_rest[k] = 0.f;
+        if (STORE)
+            for (int k = 0; k < 3 * (K - 1); k++) d_rest[k] = 0.f;
         o.grgb[0] = o.grgb[1] = o.grgb[2] = 0.f;
     }
     if (CAM) { cam[26] = cpg0; cam[27] = cpg1; cam[28] = cpg2; }
@@ -1158,11 +1161,33 @@ __device__ __forceinline__ int cam_butterfly_component(int lane)
 }
 #endif
 
-// CAM: the camera cotangents as well (ModelGrads::cam_partial); the default instantiation carries none of it.
-#if defined(__HIP_DEVICE_COMPILE__)
-template <bool CAM, bool ADAM>
-__device__ __forceinline__ void project_bwd_body(const ModelArgs& a, const ModelGrads& g)
+// A mode-1 segment whose SH coefficients are stored once per STRAND (ghr_shared.h): row i reads dc[i / n_seg] and
+// rest[i / n_seg].  An extra kernel argument of its own -- ModelArgs / ModelGrads keep their layouts.  The kernels that take it
+// are handed a ModelArgs whose features_dc points at xyz (load_raw reads 3 floats per ROW there and the value is replaced).
+struct SharedFeat {
+    int n_strands, n_seg;
+    const float* dc;    // [S,1,3]
+    const float* rest;  // [S,K-1,3]
+};
+
+// The strands' `rest` rows first_strand .. first_strand + n - 1 into LDS.  Their start is 4-B aligned only (36 / 96 / 180 bytes
+// a strand), so dwords, coalesced; the first piece without a branch (load_raw), the others in a loop: at the 99 rows a strand
+// of the latent stage a workgroup spans at most four strands, 180 floats.
+template <int BLK>
+__device__ __forceinline__ void shared_rest_to_lds(float* dst, const float* src, int n_floats, int tid)
 {
+    const float v = src[tid < n_floats ? tid : 0];
+    if (tid < n_floats) dst[tid] = v;
+    for (int i = tid + BLK; i < n_floats; i += BLK) dst[i] = src[i];
+}
+
+// CAM: the camera cotangents as well (ModelGrads::cam_partial); the default instantiation carries none of it.
+// SHARED (k_shared_proj_bwd, never with ADAM): the coefficients are per strand (sf), the SH gradients leave in factored form only.
+#if defined(__HIP_DEVICE_COMPILE__)
+template <bool CAM, bool ADAM, bool SHARED = false>
+__device__ __forceinline__ void project_bwd_body(const ModelArgs& a, const ModelGrads& g, const SharedFeat& sf = SharedFeat())
+{
+    static_assert(!(SHARED && ADAM), "a shared segment's features are no optimizer leaves");
     constexpr int BLK = GHR_PBW_BLOCK;
     __shared__ __attribute__((aligned(16))) float s_rest[BLK * GHR_REST_MAX];  // coefficients in, gradients out
     const int row = 3 * (a.sh_coeffs - 1);
@@ -1182,6 +1207,13 @@ __device__ __forceinline__ void project_bwd_body(const ModelArgs& a, const Model
     f4 q0 = a.rec[4 * rowc], q1 = a.rec[4 * rowc + 1];  // pixel mean / conic / opacity
     RawIn in;
     load_raw(a, idc, in);
+    int strand = 0, strand0 = 0;
+    if constexpr (SHARED) {
+        strand = idc / sf.n_seg;
+        strand0 = base / sf.n_seg;
+#pragma unroll
+        for (int i = 0; i < 3; i++) in.dc[i] = sf.dc[3 * (size_t)strand + i];
+    }
     const int radius = a.radii[rowc];
     if (idx >= a.P) r = make_rect4(0, 0, 0, 0, 0u);
     // ADAM: the per-array coefficients of the fused update, one array per lane, under the first round trip of the loads above
@@ -1200,7 +1232,11 @@ __device__ __forceinline__ void project_bwd_body(const ModelArgs& a, const Model
     // here, with a wait that costs nothing, or it would protect the first use of `radius` below with a vmcnt(0) that
     // waits for the slab.  0x0f70 = vmcnt(0), expcnt / lgkmcnt untouched.)
     __builtin_amdgcn_s_waitcnt(0x0f70);
-    if (row > 0) slab_dma<BLK>(s_rest, a.features_rest + (size_t)base * row, (size_t)nb * row, threadIdx.x);
+    if constexpr (SHARED) {
+        // the workgroup's 64 rows span at most min(64, 63 / n_seg + 2) strands
+        const int n_str = (base + nb - 1) / sf.n_seg - strand0 + 1;
+        if (row > 0) shared_rest_to_lds<BLK>(s_rest, sf.rest + (size_t)strand0 * row, n_str * row, threadIdx.x);
+    } else if (row > 0) slab_dma<BLK>(s_rest, a.features_rest + (size_t)base * row, (size_t)nb * row, threadIdx.x);
     ProjBwdOut o;
     float cam[CAM ? GHR_CAM_PARTIALS : 1];
     if (CAM) {
@@ -1222,7 +1258,8 @@ __device__ __forceinline__ void project_bwd_body(const ModelArgs& a, const Model
     bool bad = false;
     if (CAM) cam[CAM ? 26 : 0] = cam[CAM ? 27 : 0] = cam[CAM ? 28 : 0] = 0.f;   // (lanes past the end of the segment)
     if (idx < a.P) {
-        project_bwd_sh<CAM>(a, in, radius, ga, s_rest + threadIdx.x * row, s_rest + threadIdx.x * row, o, cam);
+        if constexpr (SHARED) project_bwd_sh<CAM, false>(a, in, radius, ga, s_rest + (strand - strand0) * row, nullptr, o, cam);
+        else project_bwd_sh<CAM>(a, in, radius, ga, s_rest + threadIdx.x * row, s_rest + threadIdx.x * row, o, cam);
         if constexpr (ADAM) bad = project_bwd_store(a, g, idx, ga, o, radius, &in, ss, b2);
         else bad = project_bwd_store(a, g, idx, ga, o, radius);
     }
@@ -1231,7 +1268,7 @@ __device__ __forceinline__ void project_bwd_body(const ModelArgs& a, const Model
         if (row > 0)
             bad |= slab_out_adam<BLK>(g.d_features_rest + (size_t)base * row, a.features_rest + (size_t)base * row, s_rest,
                                       (size_t)nb * row, threadIdx.x, g.accumulate, g.adam, ss[7], b2[7]);
-    } else if (row > 0 && !g.cam_only && g.d_features_rest != nullptr)
+    } else if (!SHARED && row > 0 && !g.cam_only && g.d_features_rest != nullptr)
         bad |= slab_out<BLK>(g.d_features_rest + (size_t)base * row, s_rest, (size_t)nb * row, threadIdx.x, g.accumulate);
     if (g.overflow_is_bad && g.dens_count != nullptr && *reinterpret_cast<const volatile uint32_t*>(g.dens_count) > g.dens_cap)
         bad = true;

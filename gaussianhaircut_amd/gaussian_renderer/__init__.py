@@ -241,8 +241,17 @@ def _use_fused_hair(pc, pc_hair, pipe, cam=None) -> bool:
     return bool(getattr(pipe, "fused_projection", True) and hair_ok and head_ok and pc_hair.get_xyz.is_cuda)
 
 
+def _check_hair_features(pc_hair):
+    """Per-strand ``_features_dc`` / ``_features_rest`` ([S, ., 3] for S n_seg Gaussians) are accepted only from a model that
+    declares them (``feature_rows_per_strand = n_seg``, GaussianModelLatentStrands(shared_appearance=True)): ValueError otherwise."""
+    if _has(pc_hair, "_features_dc") and _has(pc_hair, "_features_rest") and _has(pc_hair, "get_xyz"):
+        from .fused import hair_feature_rows
+        hair_feature_rows(pc_hair)
+
+
 def render_hair(viewpoint_camera, pc, pc_hair, pipe, bg_color: torch.Tensor, scaling_modifier=1.0):
     """Frozen head Gaussians (``*_precomp`` attributes of ``pc``) + trainable hair strands (reference :116-214)."""
+    _check_hair_features(pc_hair)  # (the generic path below reads get_features, which such a model expands itself)
     if _use_fused_hair(pc, pc_hair, pipe, viewpoint_camera):
         from .fused import render_hair_fused
         renders, radii, screenspace_points = render_hair_fused(viewpoint_camera, pc, pc_hair, bg_color,

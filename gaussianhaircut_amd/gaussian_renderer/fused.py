@@ -311,6 +311,17 @@ def _ptr_rows(t, rows: int, row_bytes: int):
 # ghr_model_forward_segment): no concatenation of 60-float rows, no ~60 PyTorch projection kernels, and the backward
 # goes straight to the strand quantities (xyz, scaling, rotation, direction, SH, confidence), from where autograd
 # continues to the strand parameters (`_dirs`) through initialize_gaussians_hair().
+def _shared_features(cfg, n_hair):
+    """``ghr_shared_features`` of a strand segment whose SH coefficients are stored once per strand (cfg["shared_rows"] rows a
+    strand: GaussianModelLatentStrands(shared_appearance=True)), or None."""
+    n_seg = int(cfg.get("shared_rows") or 0)
+    if n_seg <= 0:
+        return None
+    sf = _lib.SharedFeatures()
+    sf.n_strands, sf.rows_per_strand = n_hair // n_seg, n_seg
+    return sf
+
+
 def _seg_args(P, row0, W, H, sh_degree, K, t, cam_t, cfg, eps, consts):
     m = _lib.ModelArgs()
     m.P, m.W, m.H, m.sh_degree, m.sh_coeffs = int(P), int(W), int(H), int(sh_degree), int(K)
@@ -370,8 +381,18 @@ class _RenderHairFused(torch.autograd.Function):
             pinned = _pinned(dev)
             _lib.check(L.ghr_model_forward_segment(_stream(), ctypes.byref(m_head), rows, 1, _ptr(geom), _ptr(img),
                                                    _ptr(radii_ws), _ptr(m2d)))
-            _lib.check(L.ghr_model_forward_segment(_stream(), ctypes.byref(m_hair), rows, 0, _ptr(geom), _ptr(img),
-                                                   _ptr_rows(radii_ws, -pad, 4), _ptr_rows(m2d, -pad, 12)))
+            sf = _shared_features(cfg, n_hair)
+            if sf is not None and n_hair > 0:
+                # per-strand coefficients: f_dc [S,1,3] / f_rest [S,K-1,3] are read in place, no expanded copy exists
+                if f_dc.shape[0] * sf.rows_per_strand != n_hair or f_rest.shape[0] != f_dc.shape[0]:
+                    raise RuntimeError("render_hair: per-strand features %s / %s do not match %d rows at %d rows a strand"
+                                       % (tuple(f_dc.shape), tuple(f_rest.shape), n_hair, sf.rows_per_strand))
+                _lib.check(L.ghr_model_forward_segment_shared(_stream(), ctypes.byref(m_hair), ctypes.byref(sf), rows, 0,
+                                                              _ptr(geom), _ptr(img), _ptr_rows(radii_ws, -pad, 4),
+                                                              _ptr_rows(m2d, -pad, 12)))
+            else:
+                _lib.check(L.ghr_model_forward_segment(_stream(), ctypes.byref(m_hair), rows, 0, _ptr(geom), _ptr(img),
+                                                       _ptr_rows(radii_ws, -pad, 4), _ptr_rows(m2d, -pad, 12)))
             _lib.check(L.ghr_model_forward_finish(_stream(), rows, W, H, int(bool(cfg["debug"])), _ptr(geom), _ptr(img),
                                                   ctypes.c_void_p(pinned.data_ptr())))
             va = _lib.ViewArgs()
@@ -429,7 +450,9 @@ class _RenderHairFused(torch.autograd.Function):
             # (the step's first backward) they are ASSIGNED in place by the kernel -- autograd's AccumulateGrad otherwise reads
             # the 570 MB of zeros, adds and writes them back (0.43 ms per iteration at the reference's 30 000 strands) -- and the
             # kernel raises the optimizer's non-finite flag for everything it stores (the scan over 52 floats per Gaussian goes)
-            sink = cfg.get("grad_sink")
+            sf = _shared_features(cfg, n_hair)
+            # (per-strand features are non-leaf tensors out of a decoder: no optimizer's flat buffer to assign into)
+            sink = cfg.get("grad_sink") if sf is None else None
             if sink is not None:
                 # (a buffer left undefined by step(zero_grad="defer") is only made whole by a backward that assigns EVERY
                 # group; this one assigns two of four: the others would be accumulated into garbage)
@@ -446,6 +469,8 @@ class _RenderHairFused(torch.autograd.Function):
                 d_fdc, d_frest = ctx.sh_leaves[0].grad, ctx.sh_leaves[1].grad
             elif fuse:
                 d_fdc = d_frest = None
+            elif sf is not None:
+                d_fdc, d_frest = torch.empty((sf.n_strands, 1, 3), **f32), torch.empty((sf.n_strands, K - 1, 3), **f32)
             else:
                 d_fdc, d_frest = torch.empty((n_hair, 1, 3), **f32), torch.empty((n_hair, K - 1, 3), **f32)
             scratch = getattr(ctx, "scratch", None)  # made (and zeroed) by the forward pass when it knew of a backward
@@ -479,7 +504,16 @@ class _RenderHairFused(torch.autograd.Function):
                 _lib.check(L.ghr_model_backward_segment(_stream(), ctypes.byref(m_head), rows, _ptr(radii_ws), _ptr(geom),
                                                         _ptr(scratch), None, None, None, None, None, None, None, None, None,
                                                         None, 0, None, scratch.shape[0], _ptr(binb), ctx.cap))
-            if n_hair > 0:
+            if n_hair > 0 and sf is not None:
+                # factored projection backward (12 B per row into d_rgb) + the per-strand fold: [S,1,3] / [S,K-1,3] to autograd
+                d_rgb = torch.empty((n_hair, 3), **f32)
+                _lib.check(L.ghr_model_backward_segment_shared(_stream(), ctypes.byref(m_hair), ctypes.byref(sf), rows,
+                                                               _ptr_rows(radii_ws, -pad, 4), _ptr(geom), _ptr(scratch),
+                                                               _ptr_rows(d_m2d, -pad, 12), _ptr(d_xyz), _ptr(d_sc), _ptr(d_rot),
+                                                               None, None, _ptr(d_conf), _ptr(d_fdc), _ptr(d_frest),
+                                                               _ptr(d_dir), None, scratch.shape[0], _ptr(binb), ctx.cap,
+                                                               _ptr(d_rgb)))
+            elif n_hair > 0:
                 _lib.check(L.ghr_model_backward_segment(_stream(), ctypes.byref(m_hair), rows, _ptr_rows(radii_ws, -pad, 4),
                                                         _ptr(geom), _ptr(scratch), _ptr_rows(d_m2d, -pad, 12), _ptr(d_xyz), _ptr(d_sc),
                                                         _ptr(d_rot), None, None, _ptr(d_conf),
@@ -512,6 +546,21 @@ def head_segment(pc):
     return cache[1]
 
 
+def hair_feature_rows(pc_hair) -> int:
+    """Rows of the strand model that share one row of ``_features_dc`` / ``_features_rest``: 1 for per-Gaussian features; the
+    model's ``feature_rows_per_strand`` (> 1) when it says they are per strand and the shapes agree.  Anything else is refused."""
+    P, F = int(pc_hair.get_xyz.shape[0]), int(pc_hair._features_dc.shape[0])
+    if int(pc_hair._features_rest.shape[0]) != F:
+        raise ValueError("render_hair: _features_dc has %d rows, _features_rest %d" % (F, int(pc_hair._features_rest.shape[0])))
+    n_seg = int(getattr(pc_hair, "feature_rows_per_strand", 0) or 0)
+    if n_seg > 1 and F * n_seg == P:
+        return n_seg
+    if F == P and n_seg <= 1:
+        return 1
+    raise ValueError("render_hair: %d feature rows for %d Gaussians (feature_rows_per_strand = %d): per-strand features are "
+                     "taken only from a model that sets feature_rows_per_strand = P / rows" % (F, P, n_seg))
+
+
 def render_hair_fused(cam, pc, pc_hair, bg_color, scaling_modifier, debug, fuse_adam=False):
     """Returns (renders[10,H,W], radii[n_head + n_hair], screenspace_points leaf)."""
     head = head_segment(pc)
@@ -525,7 +574,11 @@ def render_hair_fused(cam, pc, pc_hair, bg_color, scaling_modifier, debug, fuse_
                debug=bool(debug), grad_enabled=torch.is_grad_enabled())
     from ..optim import FusedAdam
     opt = getattr(pc_hair, "optimizer", None)
-    if isinstance(opt, FusedAdam) and opt.direct_grads and torch.is_grad_enabled():
+    n_seg = hair_feature_rows(pc_hair)
+    if n_seg > 1:
+        # SH coefficients stored once per strand (ghr_model_forward_segment_shared); never an optimizer's leaves
+        cfg["shared_rows"] = n_seg
+    elif isinstance(opt, FusedAdam) and opt.direct_grads and torch.is_grad_enabled():
         cfg["grad_sink"] = opt
         cfg["fuse_adam"] = bool(fuse_adam)
     renders, radii = _RenderHairFused.apply(xyz, pc_hair.get_scaling, pc_hair._rotation, pc_hair._dir,

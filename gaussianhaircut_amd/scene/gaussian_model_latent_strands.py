@@ -7,7 +7,12 @@ The Gaussian side of the latent-strand stage.  The strand prior that decodes a l
 output at the top of every iteration (:451-499) is in scope and fused (csrc/ghr_latent.h):
   * points ``p [S, L, 3]`` -> ``_xyz / _rotation / _scaling / _dir`` of the ``S (L - 1)`` segment Gaussians, one kernel each way;
   * per-strand appearance ``repeat``-ed over the segments, one kernel each way (the backward sums a strand's rows in order).
-On a non-ROCm device, or with ``fused=False``, the same tensors come from the PyTorch expressions of the reference."""
+On a non-ROCm device, or with ``fused=False``, the same tensors come from the PyTorch expressions of the reference.
+
+``shared_appearance=True`` (or ``GHR_LATENT_SHARED_FEATURES=1``; off by default) goes one step further for per-strand SH
+features on a ROCm device: they are not expanded at all.  ``_features_dc`` / ``_features_rest`` stay ``[S, ., 3]``,
+``feature_rows_per_strand`` says how many Gaussians share a row, and ``render_hair`` projects them with the kernels of
+csrc/ghr_shared.h, whose backward returns the per-strand gradients directly.  ``get_features`` still returns ``[P, K, 3]``."""
 from __future__ import annotations
 
 import os
@@ -19,6 +24,7 @@ from ..utils.general_utils import parallel_transport
 from .gaussian_model_strands import GaussianModelStrands
 
 FUSED_LATENT_BUILD = os.environ.get("GHR_FUSED_LATENT_BUILD", "1") != "0"
+SHARED_FEATURES = os.environ.get("GHR_LATENT_SHARED_FEATURES", "0") == "1"
 
 
 def _fusable(t) -> bool:
@@ -112,8 +118,11 @@ class GaussianModelLatentStrands(GaussianModelStrands):
       reference splits ``z_app``; optional ``orient_conf`` (log space, [S, 1] or [S (L-1), 1]); optional ``L_diff``.
     ``color_decoder`` is whatever module the caller wants in the checkpoint next to the generator (it may be None)."""
 
-    def __init__(self, sh_degree: int, generator=None, color_decoder=None, scale: float = 1e-3, fused: bool = True):
+    def __init__(self, sh_degree: int, generator=None, color_decoder=None, scale: float = 1e-3, fused: bool = True,
+                 shared_appearance: bool = False):
         super().__init__(sh_degree, scale=scale)
+        self.shared_appearance = bool(shared_appearance) or SHARED_FEATURES
+        self.feature_rows_per_strand = 0  # > 1: _features_dc / _features_rest hold one row per STRAND (set by _split)
         self.active_sh_degree = self.max_sh_degree  # the reference's constructor (:64)
         self.strands_generator = generator
         self.color_decoder = color_decoder
@@ -130,18 +139,36 @@ class GaussianModelLatentStrands(GaussianModelStrands):
             raise ValueError("features must be [S, %d] or [S (L-1), %d], got %s" % (K3, K3, tuple(feats.shape)))
         fused = self.fused and FUSED_LATENT_BUILD
         dc, rest = feats[:, :3], feats[:, 3:]
-        if feats.shape[0] == S and n_seg > 1:
+        self.feature_rows_per_strand = 0
+        if feats.shape[0] == S and n_seg > 1 and self.shared_appearance and fused and _fusable(feats):
+            # per strand and kept so: the projection indexes them by strand (csrc/ghr_shared.h), its backward returns [S, ., 3]
+            self.feature_rows_per_strand = n_seg
+            self._features_dc = dc.reshape(S, 1, 3)
+            self._features_rest = rest.reshape(S, (self.max_sh_degree + 1) ** 2 - 1, 3)
+        elif feats.shape[0] == S and n_seg > 1:
             # per strand (one segment a strand: both readings are the same rows).  Split first, on the [S, K 3] rows, so that each
             # expanded tensor is contiguous and its gradient reaches the reduce without a slice's zero-padded copy
             dc, rest = expand_rows(dc, n_seg, fused), expand_rows(rest, n_seg, fused)
-        self._features_dc = dc.reshape(S * n_seg, 1, 3)
-        self._features_rest = rest.reshape(S * n_seg, (self.max_sh_degree + 1) ** 2 - 1, 3)
+        if self.feature_rows_per_strand == 0:
+            self._features_dc = dc.reshape(S * n_seg, 1, 3)
+            self._features_rest = rest.reshape(S * n_seg, (self.max_sh_degree + 1) ** 2 - 1, 3)
         conf = out.get("orient_conf")
         if conf is None:
             conf = torch.zeros((S * n_seg, 1), dtype=feats.dtype, device=feats.device)
         elif conf.shape[0] == S and n_seg > 1:
             conf = expand_rows(conf.reshape(S, 1), n_seg, fused)
         self._orient_conf = conf.reshape(S * n_seg, 1)
+
+    @property
+    def get_features(self):
+        """[P, K, 3] whatever the storage: per-strand rows are ``repeat``-ed (:465-467) for the generic render path and any
+        other reader."""
+        f = torch.cat((self._features_dc, self._features_rest), dim=1)
+        n = self.feature_rows_per_strand
+        if n > 1:
+            S, K = f.shape[0], f.shape[1]
+            f = f.view(S, 1, K, 3).repeat(1, n, 1, 1).reshape(S * n, K, 3)
+        return f
 
     def initialize_gaussians_hair(self, iteration=0, num_strands=-1):
         """:451-499: call the generator, build the segment Gaussians, expand per-strand appearance, set ``LDiff``."""

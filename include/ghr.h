@@ -729,6 +729,41 @@ int ghr_latent_loss_forward(void* stream, const ghr_latent_loss_args* l, float* 
 int ghr_latent_loss_backward(void* stream, const ghr_latent_loss_args* l, const float* sums, const float* grad_loss,
                              float* d_packed);
 
+/* ---- per-strand SH coefficients in the segmented form (csrc/ghr_shared.h)
+ * Added without an ABI_VERSION bump: three new functions and one new struct, no existing struct or signature changed.
+ * A mode-1 segment whose features_dc is [S][1][3] and features_rest [S][K-1][3]: row i of the segment (P = S rows_per_strand
+ * rows, row s rows_per_strand + k = segment k of strand s) reads the coefficients of strand i / rows_per_strand.  Everything else
+ * is as in ghr_model_forward_segment / ghr_model_backward_segment, and such a segment may be mixed freely with ordinary
+ * segments of the same rasterizer state: the records, radii, means2D and every per-row gradient have the bits those calls
+ * give for the coefficients repeated over the rows.
+ * ghr_model_backward_segment_shared runs the projection backward in factored form into d_rgb_ws [P][3] (caller-owned scratch,
+ * ASSIGNED: dL/d(rgb) behind the colour clamp) and then folds it: d_features_dc [S][1][3] and d_features_rest [S][K-1][3] are
+ * ASSIGNED the sums over the strand's rows j = 0 .. rows_per_strand - 1, in index order, one fp32 accumulator each, of
+ * basis_k(normalize(xyz_j - campos)) d_rgb_j[c] -- the products the ordinary call stores per row, summed as
+ * ghr_strand_rows_reduce sums them (a row without gradient contributes +0; its direction is not evaluated).  There is no
+ * `accumulate`.  nan_flag is raised for a non-finite value in any gradient written, the folded ones included.
+ * The whole argument set is checked before any launch and ghr_last_error() names the field.  Refused: mode != 1;
+ * P != n_strands * rows_per_strand; rows_per_strand < 1; adam_fuse, cam_only or d_rgb set in `m`; sh_coeffs outside 1, 4, 9, 16;
+ * (backward, P > 0) NULL d_rgb_ws, d_features_dc, or d_features_rest with K > 1.  A refused call launches nothing.  P == 0 is
+ * GHR_OK and launches nothing -- not even the counter reset of a `first` forward segment: give `first` to a segment with rows
+ * or to an ordinary (possibly empty) one.
+ * ghr_shared_sh_fold is the second half of that backward on its own, for a caller that holds a d_rgb table already: xyz and
+ * d_rgb are [S rows_per_strand][3], campos [3] (device), both outputs ASSIGNED; n_strands == 0 is GHR_OK and launches nothing. */
+typedef struct ghr_shared_features {
+    int32_t n_strands;        /* S */
+    int32_t rows_per_strand;  /* n_seg >= 1; the segment's P must equal S * n_seg */
+} ghr_shared_features;
+int ghr_model_forward_segment_shared(void* stream, const ghr_model_args* m, const ghr_shared_features* sf, int32_t rows_total,
+                                     int32_t first, void* geom_ws, void* img_ws, int32_t* radii, float* means2D_out);
+int ghr_model_backward_segment_shared(void* stream, const ghr_model_args* m, const ghr_shared_features* sf, int32_t rows_total,
+                                      const int32_t* radii, const void* geom_ws, const float* grad_scratch, float* d_means2D,
+                                      float* d_xyz, float* d_log_scales, float* d_rotations, float* d_opacity_logit,
+                                      float* d_label_logit, float* d_orient_conf_log, float* d_features_dc,
+                                      float* d_features_rest, float* d_dir3d, int32_t* nan_flag, uint32_t grad_rows,
+                                      const void* bin_ws, uint32_t R, float* d_rgb_ws);
+int ghr_shared_sh_fold(void* stream, const ghr_shared_features* sf, int32_t sh_degree, int32_t sh_coeffs, const float* xyz,
+                       const float* campos, const float* d_rgb, float* d_features_dc, float* d_features_rest, int32_t* nan_flag);
+
 /* Introspection for tests (device pointers into the workspaces; layout is otherwise private). */
 typedef struct ghr_ws_view {
     const float* rec;          /* [P][16]: x, y, conic a, b, c, opacity, features[10] */

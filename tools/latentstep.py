@@ -1,7 +1,12 @@
 """Time of one iteration of the latent-strand stage, fused (csrc/ghr_latent.h) against composed (the PyTorch expressions of
-src/scene/gaussian_model_latent_strands.py:451-499 and src/train_latent_strands.py:130-152), in ONE process on one GPU:
+src/scene/gaussian_model_latent_strands.py:451-499 and src/train_latent_strands.py:130-152) and against `shared` (the fused
+form with per-strand SH features read inside the projection, csrc/ghr_shared.h: GaussianModelLatentStrands(shared_appearance=True)),
+in ONE process on one GPU:
 
     python tools/latentstep.py [out-file, default profiles/latent_stage.txt]
+
+The three forms alternate, two passes; the spread of the `fused` form between the passes is printed next to the figures (it is the
+yardstick: the same code with the option off).  Peak allocated memory is taken per form over its timed iterations.
 
 Size: 30 000 strands x 100 points + 100 000 frozen head Gaussians at 1920 x 1080 -- the strand stage's bench size, CHOSEN HERE, not
 read from a reference config.  The generator is a toy: a parameter tensor of points, a per-strand code and one linear layer to
@@ -52,6 +57,73 @@ def timed(fn, n):
     return e0.elapsed_time(e1) / n
 
 
+def projection_parts(head, model, cam, bg, opt):
+    """Device time of the hair segment's projection launches in `model`'s form -- k_project / k_project_bwd on expanded arrays, or
+    k_shared_proj_fwd / k_shared_proj_bwd + k_shared_sh_fold on per-strand ones -- through the C ABI on the state of one real step
+    (its gradient lines included: a zero d_rgb table would let the fold skip every row)."""
+    import ctypes
+    from gaussianhaircut_amd import _lib
+    from gaussianhaircut_amd.gaussian_renderer import fused as fz
+    from gaussianhaircut_amd.diff_gaussian_rasterization import _ptr, _stream
+    lib = _lib.lib()
+    model.initialize_gaussians_hair(0)
+    pkg = render_hair(cam, head, model, PIPE, bg)
+    latent_view_loss(pkg, cam, opt).backward(retain_graph=True)
+    ctx = pkg.renders_packed.grad_fn
+    xyz, scaling, rotation, dirs, conf, fdc, frest, view, proj, campos, bgt, radii_ws, geom, img, binb = ctx.saved_tensors
+    n_head, n_hair, row0, rows = ctx.dims
+    cfg, K, dev = ctx.cfg, ctx.K, xyz.device
+    hair = dict(xyz=xyz, scaling=scaling, rotation=rotation, dir=dirs, conf=conf, fdc=fdc, frest=frest)
+    m = fz._seg_args(n_hair, row0, cfg["W"], cfg["H"], cfg["sh_degree"], K, hair, [view, proj, campos, bgt, ctx.fov], cfg,
+                     cfg["eps_hair"], (1.0, 1.0, 0.0))
+    sf = fz._shared_features(cfg, n_hair)
+    f32 = dict(dtype=torch.float32, device=dev)
+    F = fdc.shape[0]
+    d = dict(m2d=torch.empty((rows, 3), **f32), xyz=torch.empty((n_hair, 3), **f32), sc=torch.empty((n_hair, 3), **f32),
+             rot=torch.empty((n_hair, 4), **f32), conf=torch.empty((n_hair, 1), **f32), dir=torch.empty((n_hair, 3), **f32),
+             fdc=torch.empty((F, 1, 3), **f32), frest=torch.empty((F, K - 1, 3), **f32), rgb=torch.empty((n_hair, 3), **f32))
+    pad = row0 - n_head
+    radii_p = fz._ptr_rows(radii_ws, -pad, 4)
+    scratch = ctx.scratch
+    common = (rows, radii_p, _ptr(geom), _ptr(scratch), _ptr(d["m2d"]), _ptr(d["xyz"]), _ptr(d["sc"]), _ptr(d["rot"]), None, None,
+              _ptr(d["conf"]), _ptr(d["fdc"]), _ptr(d["frest"]), _ptr(d["dir"]))
+
+    def bwd():
+        if sf is not None:
+            _lib.check(lib.ghr_model_backward_segment_shared(_stream(), ctypes.byref(m), ctypes.byref(sf), *common, None,
+                                                             scratch.shape[0], _ptr(binb), ctx.cap, _ptr(d["rgb"])))
+        else:
+            _lib.check(lib.ghr_model_backward_segment(_stream(), ctypes.byref(m), *common, 0, None, scratch.shape[0], _ptr(binb),
+                                                      ctx.cap))
+
+    def fold():
+        _lib.check(lib.ghr_shared_sh_fold(_stream(), ctypes.byref(sf), cfg["sh_degree"], K, _ptr(xyz), _ptr(campos), _ptr(d["rgb"]),
+                                          _ptr(d["fdc"]), _ptr(d["frest"]), None))
+    out = {}
+    timed(bwd, 3)
+    out["bwd"] = timed(bwd, 20)
+    if sf is not None:
+        timed(fold, 3)
+        out["fold"] = timed(fold, 20)
+    # the forward launch into a workspace of its own (the step's state stays as the backward needs it); `first` = 1: the
+    # counters are reset in front of every launch, in both forms
+    gbytes, ibytes = _lib.forward_sizes(rows, cfg["W"], cfg["H"], False)
+    geom2, img2 = torch.empty((gbytes,), dtype=torch.uint8, device=dev), torch.empty((ibytes,), dtype=torch.uint8, device=dev)
+    radii2, m2d2 = torch.empty((rows,), dtype=torch.int32, device=dev), torch.empty((rows, 3), **f32)
+
+    def fwd():
+        if sf is not None:
+            _lib.check(lib.ghr_model_forward_segment_shared(_stream(), ctypes.byref(m), ctypes.byref(sf), rows, 1, _ptr(geom2),
+                                                            _ptr(img2), _ptr(radii2), _ptr(m2d2)))
+        else:
+            _lib.check(lib.ghr_model_forward_segment(_stream(), ctypes.byref(m), rows, 1, _ptr(geom2), _ptr(img2), _ptr(radii2),
+                                                     _ptr(m2d2)))
+    timed(fwd, 3)
+    out["fwd"] = timed(fwd, 20)
+    del pkg
+    return out
+
+
 def main():
     out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                                    "profiles", "latent_stage.txt")
@@ -79,8 +151,8 @@ def main():
         cam.original_orient_conf = torch.ones_like(pkg["orient_conf"]).detach()
         del gt, pkg
     models = {}
-    for name, fused in (("fused", True), ("composed", False)):
-        m = gml.GaussianModelLatentStrands(3, Toy(pts), fused=fused)
+    for name, fused in (("fused", True), ("composed", False), ("shared", True)):
+        m = gml.GaussianModelLatentStrands(3, Toy(pts), fused=fused, shared_appearance=name == "shared")
         m.training_setup(opt)
         models[name] = m
     it = [0]
@@ -103,12 +175,21 @@ def main():
         o.step()
         o.zero_grad(set_to_none=True)
 
-    steps = {"fused": fused_step, "composed": composed_step}
-    res = {}
+    def shared_step():
+        it[0] += 1
+        latent_strand_training_step(head, models["shared"], [cam], bg, opt, it[0], pipe=PIPE)
+
+    steps = {"fused": fused_step, "composed": composed_step, "shared": shared_step}
+    res, passes, peak = {}, ({}, {}), {}
     for rnd in range(2):
         for name, fn in steps.items():
             timed(fn, 3 if rnd == 0 else 1)
-            res[name] = timed(fn, 8)
+            torch.cuda.reset_peak_memory_stats()
+            res[name] = passes[rnd][name] = timed(fn, 8)
+            peak[name] = torch.cuda.max_memory_allocated()
+    assert models["shared"].feature_rows_per_strand == L - 1 and models["fused"].feature_rows_per_strand == 0
+    spread = abs(passes[0]["fused"] - passes[1]["fused"])
+    proj = {name: projection_parts(head, models[name], cam, bg, opt) for name in ("fused", "shared")}
 
     # the parts, on the step's tensors
     P = S * (L - 1)
@@ -162,6 +243,17 @@ def main():
              "device: %s, torch %s" % (torch.cuda.get_device_name(0), torch.__version__),
              "",
              "iteration  fused %.3f ms   composed %.3f ms   (%.2fx)" % (res["fused"], res["composed"], res["composed"] / res["fused"]),
+             "iteration  shared %.3f ms  (fused - shared = %.3f ms; the fused form's two passes: %.3f / %.3f ms, spread %.3f ms)"
+             % (res["shared"], res["fused"] - res["shared"], passes[0]["fused"], passes[1]["fused"], spread),
+             "peak allocated, MB   fused %.0f   composed %.0f   shared %.0f" % tuple(peak[k] / 1e6 for k in ("fused", "composed", "shared")),
+             "",
+             "the hair segment's projection launches on the step's own state, ms (mean of 20)",
+             "%-34s %10s %10s" % ("", "expanded", "per strand"),
+             "%-34s %10.4f %10.4f" % ("projection forward", proj["fused"]["fwd"], proj["shared"]["fwd"]),
+             "%-34s %10.4f %10.4f" % ("projection backward (+ fold)", proj["fused"]["bwd"], proj["shared"]["bwd"]),
+             "fold alone %.4f ms: %d rows x 24 B = %.1f MB read, %.0f GB/s (derived floor at 8 TB/s: %.1f us, reached to %.0f %%)"
+             % (proj["shared"]["fold"], P, P * 24 / 1e6, P * 24 / 1e6 / proj["shared"]["fold"], P * 24 / 8e6,
+                100.0 * (P * 24 / 8e6) / (proj["shared"]["fold"] * 1e3)),
              "",
              "parts, ms (mean of 20; the composed form includes the `p * 1.0` / angle ops a caller also pays)",
              "%-12s %10s %10s" % ("", "fused", "composed")]
