@@ -153,56 +153,51 @@ class _RenderModelFused(torch.autograd.Function):
                 # the stage-1 loop's per-iteration statistics (train_gaussians.py:161-165) ride along in k_project_bwd
                 m.dens_grad_accum, m.dens_denom, m.dens_max_radii2D = [_ptr(t) for t in dens]
                 m.dens_img_ws = _ptr(img)  # (a view whose capacity guess overflowed leaves the statistics alone: it is redone)
-            adam_fuse = sink.fused_step_args() if direct and P > 0 else None
-            fuse = adam_fuse is not None
-            if fuse:
-                # a step whose LAST backward carries the optimizer update (optim.FusedAdam.begin_fused_step): every view checks
-                # its instance count on the device (an overflowed speculative pass must raise the step's flag) ...
-                m.dens_img_ws, m.overflow_raises_flag = _ptr(img), 1
-                if cfg.get("fuse_adam"):  # ... and this one IS the last
-                    m.adam_fuse = adam_fuse
-            # the step's first gradients into a buffer that is known to hold zeros are assigned, not added (optim.py)
-            acc = 0 if P > 0 and direct and sink.take_known_zero() else 1
             p_fdc, p_frest = _ptr(d_fdc), _ptr(d_frest)
-            fold_first = False
-            if P > 0 and direct and sink.views_open:
-                if fuse and cfg.get("fuse_adam"):
-                    # the view that carries the optimizer update needs the step's whole SH gradient in the flat buffer: the
-                    # earlier views' tables are folded into it first (one launch), this view's terms are added by the kernel
-                    fold_first = True
-                else:
+            h = acc_event = None
+            if direct:
+                # the optimizer's side of a direct backward: accumulate into the flat gradient buffer or assign, under which flag
+                h = sink.open_view(cfg.get("fuse_adam"), campos)
+                if h.check_overflow:
+                    # a step whose LAST backward carries the optimizer update (optim.FusedAdam.begin_fused_step): every view checks
+                    # its instance count on the device (an overflowed speculative pass must raise the step's flag) ...
+                    m.dens_img_ws, m.overflow_raises_flag = _ptr(img), 1
+                    m.adam_fuse = h.adam_fuse  # ... and this one may BE the last
+                if h.d_rgb is not None:
                     # the SH gradients of this view in factored form (optim.FusedAdam.begin_factored_views): its dL/d(rgb)
                     # table instead of 192 B per Gaussian read, added and written back in the flat gradient
-                    m.d_rgb = sink.next_view_slot(campos)
+                    m.d_rgb = h.d_rgb
                     p_fdc = p_frest = None
-            if P > 0 and direct and sink.concurrent:
+            if direct and sink.concurrent:
                 # this view shares the GPU with its neighbours (trainer.training_step): only the kernel that adds into
                 # the shared gradient buffer is ordered after the previous view's
                 stream = torch.cuda.current_stream()
                 _lib.check(L.ghr_render_backward(_stream(), P, cfg["W"], cfg["H"], ctx.cap, _ptr(bg), _ptr(geom),
                                                  _ptr(img), _ptr(binb), _ptr(dL), _ptr(scratch), prezeroed))
-                sink.accumulate_begin(stream)
-                if fold_first:
+                if h.wait_event is not None:
+                    stream.wait_event(h.wait_event)
+                if h.fold:
+                    # the view that carries the optimizer update needs the step's whole SH gradient in the flat buffer: the
+                    # earlier views' tables are folded into it first (one launch), this view's terms are added by the kernel
                     sink.fold_own_views()
                 _lib.check(L.ghr_model_backward_segment(_stream(), ctypes.byref(m), P, _ptr(radii), _ptr(geom),
                                                         _ptr(scratch), _ptr(d_m2d), _ptr(d_xyz), _ptr(d_ls), _ptr(d_rot),
                                                         _ptr(d_op), _ptr(d_label), _ptr(d_conf), p_fdc,
-                                                        p_frest, None, acc, sink.nan_flag_ptr(), rows,
+                                                        p_frest, None, h.accumulate, h.nan_flag, rows,
                                                         _ptr(binb), ctx.cap))
-                sink.accumulate_end(stream)
+                acc_event = torch.cuda.Event()
+                acc_event.record(stream)
             elif P > 0:
-                if fold_first:
+                if direct and h.fold:
                     sink.fold_own_views()
                 _lib.check(L.ghr_model_backward(_stream(), ctypes.byref(m), ctx.cap, _ptr(radii), _ptr(geom), _ptr(img),
                                                 _ptr(binb), _ptr(dL), _ptr(scratch), _ptr(d_m2d), _ptr(d_xyz),
                                                 _ptr(d_ls), _ptr(d_rot), _ptr(d_op), _ptr(d_label), _ptr(d_conf),
-                                                p_fdc, p_frest, acc if direct else 0,
-                                                sink.nan_flag_ptr() if direct else None, prezeroed))
+                                                p_fdc, p_frest, h.accumulate if direct else 0,
+                                                h.nan_flag if direct else None, prezeroed))
             d_cam = _camera_grads(cam_partial, ctx.cam_meta, ctx.needs_input_grad[9:14], dev, ctx.fov) if want_cam else (None,) * 5
         if direct:
-            sink.note_direct_backward()
-            if fuse and cfg.get("fuse_adam"):
-                sink.note_fused_update()
+            sink.close_view(h, acc_event)
             return (None, None, None, None, None, None, None, None, d_m2d) + d_cam + (None,)
         return (d_xyz, d_ls, d_rot, d_op, d_label, d_conf, d_fdc, d_frest, d_m2d) + d_cam + (None,)
 
@@ -242,6 +237,16 @@ def _camera_grads(cam_partial, meta, needs, dev, fov):
     return tuple(out)
 
 
+def densify_stats_tensors(pc, P):
+    """The model's densification statistics as the backward pass updates them (``ghr_model_args.dens_*``), checked."""
+    stats = (pc.xyz_gradient_accum, pc.denom, pc.max_radii2D)
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
+               t.numel() == P for t in stats):
+        raise RuntimeError("densify_stats: xyz_gradient_accum / denom / max_radii2D must be contiguous fp32 device tensors "
+                           "of P elements (GaussianModel.training_setup creates them)")
+    return stats
+
+
 def render_model_fused(cam, pc, bg_color, scaling_modifier, debug, defer_count=False, densify_stats=False, fuse_adam=False):
     """Returns (renders[10,H,W], radii[P], screenspace_points[P,3] leaf whose .grad receives dL/d(NDC mean),
     num_rendered: int, or a PendingCount with ``defer_count``).  ``densify_stats``: the backward pass of this view also
@@ -265,12 +270,7 @@ def render_model_fused(cam, pc, bg_color, scaling_modifier, debug, defer_count=F
     if fuse_adam and "grad_sink" in cfg:
         cfg["fuse_adam"] = True
     if densify_stats and torch.is_grad_enabled():
-        stats = (pc.xyz_gradient_accum, pc.denom, pc.max_radii2D)
-        if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
-                   t.numel() == P for t in stats):
-            raise RuntimeError("densify_stats: xyz_gradient_accum / denom / max_radii2D must be contiguous fp32 device tensors "
-                               "of P elements (GaussianModel.training_setup creates them)")
-        cfg["densify_stats"] = stats
+        cfg["densify_stats"] = densify_stats_tensors(pc, P)
     renders, radii = _RenderModelFused.apply(xyz, pc._scaling, pc._rotation, pc._opacity, pc._label, pc._orient_conf,
                                              pc._features_dc, pc._features_rest, screenspace_points, view, proj, campos,
                                              fovx, fovy, cfg)

@@ -10,8 +10,8 @@ filled ``ghr_view_step_args`` of which only the per-step and per-view fields are
 
 Everything about the step that is not the views -- plan, opening the optimizer, the update, the overflow recovery -- stays in
 ``trainer``; the optimizer's host-side bookkeeping (``FusedAdam``: known-zero gradients, view slots, the fused update, the event
-chain around the shared gradient buffer) is driven through the same methods, in the same order, as ``gaussian_renderer.fused``
-drives it.
+chain around the shared gradient buffer) is driven through the same two calls as ``gaussian_renderer.fused`` drives it:
+``FusedAdam.open_view`` / ``close_view``.
 """
 from __future__ import annotations
 
@@ -228,7 +228,7 @@ class NativeViews:
             return self._views_forward_backward(gaussians, cams, background, opt, plan, fuse, densify_stats)
 
     def _views_forward_backward(self, gaussians, cams, background, opt, plan, fuse, densify_stats):
-        from .trainer import _gt_stats, _side_streams, _NO_STREAM
+        from .trainer import _gt_stats, _view_streams
         sink, V, dev = plan.sink, plan.V, self.dev
         n = len(cams)
         self._ensure_views(n)
@@ -241,14 +241,7 @@ class NativeViews:
         bg_ptr = bg.data_ptr()
         sh_degree = int(gaussians.active_sh_degree)
         eps = float(getattr(gaussians, "conic_eps", 1e-12))
-        dens_ptrs = None
-        if densify_stats:
-            stats = (gaussians.xyz_gradient_accum, gaussians.denom, gaussians.max_radii2D)
-            if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and
-                       t.numel() == P for t in stats):
-                raise RuntimeError("densify_stats: xyz_gradient_accum / denom / max_radii2D must be contiguous fp32 device tensors "
-                                   "of P elements (GaussianModel.training_setup creates them)")
-            dens_ptrs = [t.data_ptr() for t in stats]
+        dens_ptrs = [t.data_ptr() for t in _fused.densify_stats_tensors(gaussians, P)] if densify_stats else None
         scale = 1.0 / V
         w = (opt.lambda_dl1 * scale, opt.lambda_dssim * scale, opt.lambda_dmask * scale, opt.lambda_dorient * scale)
         orient = float(w[3]) != 0.0
@@ -261,17 +254,9 @@ class NativeViews:
         pinned_ptr = self.pinned.data_ptr()
         lib = _lib.lib()
         losses, counts = [], []
-        main, side = None, ()
-        if plan.n_streams > 1:
-            main = torch.cuda.current_stream(dev)
-            side = _side_streams(dev, plan.n_streams)
-            for s in side:
-                s.wait_stream(main)  # parameters as the previous optimizer step left them
-            sink.concurrent = True
-        try:
-            for i, cam in enumerate(cams):
-                carries = bool(fuse) and i == n - 1  # this view's backward applies the optimizer update
-                with torch.cuda.stream(side[i % plan.n_streams]) if side else _NO_STREAM:
+        with _view_streams(dev, plan.n_streams, sink, n) as (_, on_stream):
+            for i, (cam, ctx) in enumerate(zip(cams, on_stream)):
+                with ctx:
                     stream = _dgr._stream()
                     cf = _cam_fields(cam)
                     slot = self._slot(stream.value or 0, P, cf.W, cf.H, K)
@@ -303,46 +288,25 @@ class NativeViews:
                     a.R_host = pinned_ptr + 4 * i
                     a.loss_out = row_ptr + 4 * i
                     a.count_event = int(self.count_events[i].cuda_event)
-                    # ---- the optimizer's side of a direct backward, as gaussian_renderer.fused._RenderModelFused.backward keeps it
-                    adam_fuse = sink.fused_step_args()
-                    if adam_fuse is not None:
-                        # a step whose LAST backward carries the update: every view checks its instance count on the device
-                        m.dens_img_ws, m.overflow_raises_flag = a.img_ws, 1
-                        m.adam_fuse = adam_fuse if carries else None
-                    else:
-                        m.dens_img_ws, m.overflow_raises_flag = (a.img_ws if dens_ptrs is not None else None), 0
-                        m.adam_fuse = None
-                    a.accumulate = 0 if sink.take_known_zero() else 1
-                    m.d_rgb, a.sh_fold = None, None
-                    a.d_features_dc, a.d_features_rest = g_ptrs[6], g_ptrs[7]
-                    if sink.views_open:
-                        if carries:
-                            # the earlier views' tables are folded into the flat gradient first, inside the call
-                            a.sh_fold = sink.fold_own_views_args()
-                        else:
-                            m.d_rgb = sink.next_view_slot(cf.tensors[2])
-                            a.d_features_dc = a.d_features_rest = None
-                    a.nan_flag = sink.nan_flag_ptr()
-                    a.acc_wait_event = a.acc_record_event = None
-                    if sink.concurrent:
-                        # only the kernels that add into the shared gradient buffer are ordered after the previous view's
-                        if sink._acc_event is not None:
-                            a.acc_wait_event = int(sink._acc_event.cuda_event)
-                        a.acc_record_event = int(self.acc_events[i].cuda_event)
+                    # ---- the optimizer's side of a direct backward (the last view's applies the update of a fused step)
+                    h = sink.open_view(bool(fuse) and i == n - 1, cf.tensors[2])
+                    # a step whose LAST backward carries the update: every view checks its instance count on the device
+                    m.dens_img_ws = a.img_ws if h.check_overflow or dens_ptrs is not None else None
+                    m.overflow_raises_flag, m.adam_fuse = int(h.check_overflow), h.adam_fuse
+                    a.accumulate, a.nan_flag, m.d_rgb = h.accumulate, h.nan_flag, h.d_rgb
+                    a.d_features_dc, a.d_features_rest = (g_ptrs[6], g_ptrs[7]) if h.d_rgb is None else (None, None)
+                    # the earlier views' tables are folded into the flat gradient first, inside the call
+                    a.sh_fold = sink.fold_own_views_args() if h.fold else None
+                    # concurrent views: only the kernels that add into the shared gradient buffer are ordered after the
+                    # previous view's
+                    acc_event = self.acc_events[i] if sink.concurrent else None
+                    a.acc_wait_event = None if h.wait_event is None else int(h.wait_event.cuda_event)
+                    a.acc_record_event = None if acc_event is None else int(acc_event.cuda_event)
                     _lib.check(lib.ghr_view_step(stream, ctypes.byref(a)))
-                    if sink.concurrent:
-                        sink._acc_event = self.acc_events[i]
                     slot.img_complete = True
-                    sink.note_direct_backward()
-                    if carries:
-                        sink.note_fused_update()
+                    sink.close_view(h, acc_event)
                     losses.append(row[i])
                     counts.append(PendingCount(self.pinned[i:i + 1], self.count_events[i], cap, dev.index, P))
-        finally:
-            if side:
-                sink.concurrent = False
-                for s in side:
-                    main.wait_stream(s)
         if n == 1:
             total = losses[0]
         else:

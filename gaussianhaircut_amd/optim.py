@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Dict, List
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 import torch.distributed as dist
@@ -69,12 +69,24 @@ def _group_ranges(param_groups):
         off += k
 
 
+class ViewHandOff(NamedTuple):
+    """What ``FusedAdam.open_view`` tells the caller to put into a view's ``ghr_model_args`` / ``ghr_view_step_args``."""
+    accumulate: int              # 0: the view's gradients are assigned (the buffer holds nothing yet), 1: added
+    nan_flag: ctypes.c_void_p    # the flag word the view raises for a non-finite gradient
+    adam_fuse: Optional[int]     # address of the step's ghr_adam_fuse when THIS view carries the update
+    check_overflow: bool         # a fused step is open: dens_img_ws + overflow_raises_flag
+    d_rgb: Optional[ctypes.c_void_p]  # the view's dL/d(rgb) table, instead of the f_dc / f_rest gradient pointers
+    fold: bool                   # the earlier views' tables go into the flat gradient in front of the projection backward:
+    #                              fold_own_views(), or fold_own_views_args() for a caller that launches the fold itself
+    wait_event: Optional[object]  # concurrent views: behind the previous view's accumulating kernels
+
+
 class FusedAdam:
     # ---- every field of the optimizer's host state and its value outside a step; __init__ adds the buffers.  (Class-level, so
     # that an object made by hand around a few attributes -- the plan tests -- reads the same defaults.)
-    concurrent = False         # set by the trainer while a step's views run on several streams
+    concurrent = False         # while a step's views run on several streams (set_concurrent)
     _direct_backwards = 0      # fused backwards that stored into flat_grad since the last update (note_direct_backward)
-    _acc_event = None          # the last accumulating kernel of a concurrent step (accumulate_begin / accumulate_end)
+    _acc_event = None          # the last accumulating kernel of a concurrent step (open_view / close_view)
     # groups whose parameters were replaced since the last step (densification / opacity reset): the reference's new
     # nn.Parameters have grad None, so its optimizer.step() passes them by on that iteration -- no moment decay, no
     # update, no step count (train_gaussians.py:158-181).  Bit g = group g; consumed by the next step.  Contract: the
@@ -457,18 +469,32 @@ class FusedAdam:
         self._zero_version = None
         self._skip_next = 0  # fresh gradients for the (new) parameters: they take part in the coming step
 
-    # ---- views of one step on several HIP streams (trainer.training_step): the direct backward ACCUMULATES into the
-    # flat gradient buffer with plain read-modify-writes, so the accumulating kernels of different views are chained
-    # by events (everything else of a view -- forward, loss, render backward -- may overlap with its neighbours)
-    def accumulate_begin(self, stream):
-        if self.concurrent and self._acc_event is not None:
-            stream.wait_event(self._acc_event)
+    # ---- the hand-off of one training view's direct backward (gaussian_renderer.fused, native_step): open_view decides,
+    # in this order, everything the view's call needs from the optimizer; close_view books the view once it is launched.
+    # Views of one step on several HIP streams (set_concurrent): the direct backward ACCUMULATES into the flat gradient buffer
+    # with plain read-modify-writes, so the accumulating kernels of different views are chained by events (everything else of
+    # a view -- forward, loss, render backward -- may overlap with its neighbours)
+    def set_concurrent(self, on: bool):
+        self.concurrent = bool(on)
 
-    def accumulate_end(self, stream):
+    def open_view(self, carries: bool, campos: torch.Tensor) -> ViewHandOff:
+        adam_fuse = self.fused_step_args()
+        carries = bool(carries) and adam_fuse is not None
+        # the step's first gradients into a buffer that is known to hold zeros are assigned, not added
+        accumulate = 0 if self.take_known_zero() else 1
+        d_rgb = None
+        if self.views_open and not carries:
+            d_rgb = self.next_view_slot(campos)
+        return ViewHandOff(accumulate, self.nan_flag_ptr(), adam_fuse if carries else None, adam_fuse is not None, d_rgb,
+                           self.views_open and carries, self._acc_event if self.concurrent else None)
+
+    def close_view(self, hand_off: ViewHandOff, recorded_event=None):
+        """``recorded_event``: recorded behind the view's accumulating kernels (concurrent views: the next one waits for it)."""
         if self.concurrent:
-            ev = torch.cuda.Event()
-            ev.record(stream)
-            self._acc_event = ev
+            self._acc_event = recorded_event
+        self.note_direct_backward()
+        if hand_off.adam_fuse is not None:
+            self.note_fused_update()
 
     # ---- the update fused into the step's last projection backward (include/ghr.h, ghr_adam_fuse; round 6) ----------------
     # One rank, every view through the fused renderer's direct backward, no group sitting the step out: the LAST view's

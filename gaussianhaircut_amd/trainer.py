@@ -100,11 +100,27 @@ _SIDE_STREAMS = {}
 _NO_STREAM = contextlib.nullcontext()  # (a view on the current stream)
 
 
-def _side_streams(device, n):
-    key = (device.index, n)
+@contextlib.contextmanager
+def _view_streams(device, n_streams, sink, n_views):
+    """The streams the views of a step run on: yields (the current stream or None, one stream context per view).  With
+    ``n_streams`` > 1 the views alternate on that many side streams, forked off the current one and joined to it at the end, and
+    the optimizer chains their accumulating kernels meanwhile (FusedAdam.set_concurrent); otherwise every view stays put."""
+    if n_streams <= 1:
+        yield None, [_NO_STREAM] * n_views
+        return
+    key = (device.index, n_streams)
     if key not in _SIDE_STREAMS:
-        _SIDE_STREAMS[key] = [torch.cuda.Stream(device=device) for _ in range(n)]
-    return _SIDE_STREAMS[key]
+        _SIDE_STREAMS[key] = [torch.cuda.Stream(device=device) for _ in range(n_streams)]
+    main, side = torch.cuda.current_stream(device), _SIDE_STREAMS[key]
+    for s in side:
+        s.wait_stream(main)  # parameters as the previous optimizer step left them
+    sink.set_concurrent(True)
+    try:
+        yield main, [torch.cuda.stream(side[i % n_streams]) for i in range(n_views)]
+    finally:
+        sink.set_concurrent(False)
+        for s in side:
+            main.wait_stream(s)
 
 
 def _views_forward_backward(gaussians, cams, background, opt, V, pipe, n_streams, sink, last_pipe=None):
@@ -114,30 +130,18 @@ def _views_forward_backward(gaussians, cams, background, opt, V, pipe, n_streams
     pipes = [pipe] * len(cams)
     if last_pipe is not None and cams:
         pipes[-1] = last_pipe
-    main, side = None, ()
-    if n_streams > 1:
-        main = torch.cuda.current_stream(background.device)
-        side = _side_streams(background.device, n_streams)
-        for s in side:
-            s.wait_stream(main)  # parameters as the previous optimizer step left them
-        sink.concurrent = True
-    try:
-        for i, (cam, pipe) in enumerate(zip(cams, pipes)):
-            with torch.cuda.stream(side[i % n_streams]) if side else _NO_STREAM:
+    with _view_streams(background.device, n_streams, sink, len(cams)) as (main, on_stream):
+        for cam, pipe, ctx in zip(cams, pipes, on_stream):
+            with ctx:
                 pkg = render(cam, gaussians, pipe, background)
                 loss = view_loss(pkg, cam, opt, scale=1.0 / V)
                 loss.backward(gradient=_one_like(loss))
                 _generic_densify_stats(gaussians, pkg, pipe)
                 ld = loss.detach()
-                if side:
+                if main is not None:
                     ld.record_stream(main)
                 losses.append(ld)
                 counts.append(getattr(pkg, "count", None))
-    finally:
-        if side:
-            sink.concurrent = False
-            for s in side:
-                main.wait_stream(s)
     return losses, counts
 
 
@@ -326,7 +330,7 @@ def training_step(gaussians, cams: List, background, opt, iteration: int, bucket
     the parameters, so consecutive views run on alternating HIP streams -- the next view's projection / binning /
     compositing / loss fills the CUs the current view's VALU-bound backward leaves idle and vice versa (measured
     3.38 -> 3.08 ms for the 4-view step).  Only the kernels that add into the shared flat gradient buffer are
-    chained (FusedAdam.accumulate_begin/end); the optimizer step waits for every stream.
+    chained (FusedAdam.open_view / close_view); the optimizer step waits for every stream.
 
     ``defer_counts`` (default on with the fused path): no view waits for its ``num_rendered`` -- the forward runs with
     the capacity guessed from the previous frame and the counts are checked once, after everything is queued (the host
