@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GHR_LIB_PATH") or os.path.join(CSRC, "libghr_hip.so")  # override: kernel experiments
 SOURCES = ["ghr_capi.hip"]
 HEADERS = ["ghr_device.h", "ghr_preprocess.h", "ghr_binning.h", "ghr_render_fwd.h", "ghr_render_bwd.h", "ghr_render_bwd2.h", "ghr_render_bwd3.h",
-           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h"]
+           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-fPIC",
                "-shared"]
 
@@ -168,6 +168,18 @@ class SharedFeatures(ctypes.Structure):
     _fields_ = [("n_strands", ctypes.c_int32), ("rows_per_strand", ctypes.c_int32)]
 
 
+class MeshGrid(ctypes.Structure):
+    """``ghr_mesh_grid`` (include/ghr.h): the header of a containment grid blob."""
+    _fields_ = [("magic", ctypes.c_uint32), ("G", ctypes.c_int32), ("n_faces", ctypes.c_int32), ("n_vertices", ctypes.c_int32),
+                ("lo", ctypes.c_float * 3), ("hi", ctypes.c_float * 3), ("scale", ctypes.c_float * 3),
+                ("list_total", ctypes.c_uint32 * 3), ("list_max", ctypes.c_uint32 * 3), ("pad_", ctypes.c_uint32),
+                ("off_rec", ctypes.c_uint64 * 3), ("off_start", ctypes.c_uint64 * 3), ("off_list", ctypes.c_uint64 * 3),
+                ("bytes", ctypes.c_uint64)]
+
+
+PROBE_REFERENCE, PROBE_AXIS_SCALED = 0, 1  # GHR_PROBE_*
+
+
 def latent_loss_sums_floats(W: int, H: int) -> int:
     """floats of the latent-stage loss kernels' ``sums`` for a W x H image (``ghr_latent_loss_sums_floats``)."""
     return int(lib().ghr_latent_loss_sums_floats(int(W), int(H)))
@@ -197,7 +209,8 @@ EXPORTS = ["ghr_last_error", "ghr_abi_version", "ghr_forward_sizes", "ghr_binnin
            "ghr_resample_scratch_bytes", "ghr_resample_u8", "ghr_gt_assemble", "ghr_gt_resize_variance",
            "ghr_strand_points_build", "ghr_strand_points_build_backward", "ghr_strand_rows_expand", "ghr_strand_rows_reduce",
            "ghr_latent_loss_sums_floats", "ghr_latent_loss_forward", "ghr_latent_loss_backward",
-           "ghr_model_forward_segment_shared", "ghr_model_backward_segment_shared", "ghr_shared_sh_fold"]
+           "ghr_model_forward_segment_shared", "ghr_model_backward_segment_shared", "ghr_shared_sh_fold",
+           "ghr_mesh_grid_sizes", "ghr_mesh_grid_build", "ghr_mesh_contains", "ghr_gaussian_probe_outside"]
 
 _lib = None
 
@@ -290,6 +303,10 @@ def lib() -> ctypes.CDLL:
     L.ghr_model_backward_segment_shared.argtypes = [vp, ctypes.POINTER(ModelArgs), ctypes.POINTER(SharedFeatures), i32] + \
         [vp] * 13 + [vp, u32, vp, u32, vp]
     L.ghr_shared_sh_fold.argtypes = [vp, ctypes.POINTER(SharedFeatures), i32, i32] + [vp] * 6
+    L.ghr_mesh_grid_sizes.argtypes = [i32, vp, i32, vp, i32, ctypes.POINTER(MeshGrid)]
+    L.ghr_mesh_grid_build.argtypes = [i32, vp, i32, vp, i32, vp, ctypes.c_size_t]
+    L.ghr_mesh_contains.argtypes = [vp, ctypes.POINTER(MeshGrid), vp, ctypes.c_int64, vp, vp, vp]
+    L.ghr_gaussian_probe_outside.argtypes = [vp, ctypes.POINTER(MeshGrid), vp, ctypes.c_int64, vp, vp, vp, i32, vp]
     L.ghr_ws_inspect.argtypes = [i32, i32, i32, i32, u32, vp, vp, vp, ctypes.POINTER(WsView)]
     for name in EXPORTS:
         fn = getattr(L, name)

@@ -31,6 +31,7 @@
 #include "ghr_strands.h"
 #include "ghr_latent.h"
 #include "ghr_shared.h"
+#include "ghr_mesh.h"
 
 namespace {
 
@@ -1878,6 +1879,95 @@ int ghr_latent_loss_backward(void* stream, const ghr_latent_loss_args* l, const 
     const unsigned wgs = (unsigned)lt_loss_wgs(l->W, l->H);
     if (lt_loss_vec(l, d_packed)) hipLaunchKernelGGL(ghr::k_latent_loss_bwd<1>, dim3(wgs), dim3(GHR_LATENT_BLOCK), 0, s, a);
     else hipLaunchKernelGGL(ghr::k_latent_loss_bwd<0>, dim3(wgs), dim3(GHR_LATENT_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+}  // extern "C"
+
+// ---- containment in a triangle mesh (include/ghr.h; csrc/ghr_mesh.h) ---------------------------------------------------------
+namespace {
+static_assert(sizeof(ghr_mesh_grid) == sizeof(ghr::MeshGrid), "ghr_mesh_grid is ghr::MeshGrid");
+
+int mesh_header_check(const char* fn, const ghr_mesh_grid* h, const void* grid_dev)
+{
+    if (!h) return lt_bad(fn, "header is NULL");
+    if (h->magic != GHR_MESH_MAGIC) return lt_bad(fn, "header is not a grid header (magic)");
+    if (h->G < 1 || h->G > GHR_MESH_G_MAX) return lt_bad(fn, "header.G outside 1 .. 256");
+    if (h->n_faces < 0) return lt_bad(fn, "header.n_faces < 0");
+    if (!grid_dev) return lt_bad(fn, "grid_dev is NULL");
+    if (!al16(grid_dev)) return lt_bad(fn, "grid_dev is not 16-B aligned");
+    const uint64_t cells = (uint64_t)h->G * h->G;
+    for (int a = 0; a < 3; a++) {
+        if ((h->off_rec[a] | h->off_start[a] | h->off_list[a]) & 15u) return lt_bad(fn, "header offsets are not 16-B aligned");
+        if (h->off_rec[a] + 4ull * GHR_MESH_REC_WORDS * (uint64_t)h->n_faces > h->bytes ||
+            h->off_start[a] + 4ull * (cells + 1) > h->bytes || h->off_list[a] + 4ull * h->list_total[a] > h->bytes)
+            return lt_bad(fn, "header offsets reach past header.bytes");
+    }
+    return GHR_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int ghr_mesh_grid_sizes(int32_t n_vertices, const float* vertices, int32_t n_faces, const int32_t* faces, int32_t G,
+                        ghr_mesh_grid* header)
+{
+    static const char* fn = "ghr_mesh_grid_sizes: %s";
+    if (!header) return lt_bad(fn, "header is NULL");
+    if (const char* why = ghr::mesh_grid_plan(n_vertices, vertices, n_faces, faces, G, reinterpret_cast<ghr::MeshGrid*>(header)))
+        return lt_bad(fn, why);
+    return GHR_OK;
+}
+
+int ghr_mesh_grid_build(int32_t n_vertices, const float* vertices, int32_t n_faces, const int32_t* faces, int32_t G,
+                        void* blob, size_t bytes)
+{
+    static const char* fn = "ghr_mesh_grid_build: %s";
+    ghr::MeshGrid plan;
+    if (const char* why = ghr::mesh_grid_plan(n_vertices, vertices, n_faces, faces, G, &plan)) return lt_bad(fn, why);
+    if (!blob) return lt_bad(fn, "blob is NULL");
+    if (!al16(blob)) return lt_bad(fn, "blob is not 16-B aligned");
+    if ((uint64_t)bytes != plan.bytes) return lt_bad(fn, "bytes is not what ghr_mesh_grid_sizes reports for this mesh and G");
+    if (const char* why = ghr::mesh_grid_fill(vertices, faces, plan, blob)) return lt_bad(fn, why);
+    return GHR_OK;
+}
+
+int ghr_mesh_contains(void* stream, const ghr_mesh_grid* header, const void* grid_dev, int64_t Q, const float* points,
+                      uint8_t* inside, uint32_t* crossings)
+{
+    static const char* fn = "ghr_mesh_contains: %s";
+    if (int rc = mesh_header_check(fn, header, grid_dev)) return rc;
+    if (Q < 0) return lt_bad(fn, "Q < 0");
+    if (Q > ((int64_t)1 << 40)) return lt_bad(fn, "Q too large");
+    if (Q == 0) return GHR_OK;
+    if (!points) return lt_bad(fn, "points is NULL");
+    if (!inside) return lt_bad(fn, "inside is NULL");
+    const uint64_t blocks = ((uint64_t)Q + GHR_MESH_BLOCK - 1) / GHR_MESH_BLOCK;
+    if (blocks > 0x7fffffffull) return lt_bad(fn, "Q too large");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::MeshQueryArgs a{ghr::mesh_view(*reinterpret_cast<const ghr::MeshGrid*>(header), grid_dev), Q, points, inside, crossings};
+    hipLaunchKernelGGL(ghr::k_mesh_contains, dim3((unsigned)blocks), dim3(GHR_MESH_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+int ghr_gaussian_probe_outside(void* stream, const ghr_mesh_grid* header, const void* grid_dev, int64_t P, const float* xyz,
+                               const float* scaling, const float* rotation, int32_t probe, uint8_t* outside)
+{
+    static const char* fn = "ghr_gaussian_probe_outside: %s";
+    if (int rc = mesh_header_check(fn, header, grid_dev)) return rc;
+    if (probe != GHR_PROBE_REFERENCE && probe != GHR_PROBE_AXIS_SCALED) return lt_bad(fn, "probe is neither GHR_PROBE_REFERENCE nor GHR_PROBE_AXIS_SCALED");
+    if (P < 0) return lt_bad(fn, "P < 0");
+    if (P == 0) return GHR_OK;
+    if (!xyz) return lt_bad(fn, "xyz is NULL");
+    if (!scaling) return lt_bad(fn, "scaling is NULL");
+    if (!rotation) return lt_bad(fn, "rotation is NULL");
+    if (!outside) return lt_bad(fn, "outside is NULL");
+    const uint64_t blocks = ((uint64_t)P * 16 + GHR_MESH_BLOCK - 1) / GHR_MESH_BLOCK;  // a 16-lane row per Gaussian
+    if (P > ((int64_t)1 << 36) || blocks > 0x7fffffffull) return lt_bad(fn, "P too large");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::MeshProbeArgs a{ghr::mesh_view(*reinterpret_cast<const ghr::MeshGrid*>(header), grid_dev), P, probe, xyz, scaling, rotation,
+                         outside};
+    hipLaunchKernelGGL(ghr::k_gaussian_probe_outside, dim3((unsigned)blocks), dim3(GHR_MESH_BLOCK), 0, s, a);
     return finish(s, 0);
 }
 

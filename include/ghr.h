@@ -764,6 +764,44 @@ int ghr_model_backward_segment_shared(void* stream, const ghr_model_args* m, con
 int ghr_shared_sh_fold(void* stream, const ghr_shared_features* sf, int32_t sh_degree, int32_t sh_coeffs, const float* xyz,
                        const float* campos, const float* d_rgb, float* d_features_dc, float* d_features_rest, int32_t* nan_flag);
 
+/* ---- point-in-mesh containment and the Gaussian probe filter (csrc/ghr_mesh.h)
+ * Added without an ABI_VERSION bump: four new functions and one new struct, no existing struct or signature changed.
+ * The definition of "inside" is the one at the top of csrc/ghr_mesh.h: three axis rays, exact complementary edge predicates,
+ * the majority of the three parities; a query with a non-finite coordinate or outside the mesh's bounding box is outside.
+ * ghr_mesh_grid_sizes / ghr_mesh_grid_build run on the HOST (plain C++, deterministic: the same mesh gives the same bytes):
+ * vertices [V][3] finite floats, faces [F][3] indices into them, G the cells per side of each axis' grid (0: ceil(sqrt(F)),
+ * at most 256).  _sizes validates the mesh and fills *header, whose `bytes` is the size of the blob; _build fills `blob`
+ * (host memory, 16-B aligned, `bytes` long), which starts with the finished header (list_max filled in).  The caller copies
+ * the blob to the device as it is.
+ * ghr_mesh_contains: points [Q][3]; inside [Q] bytes 0 / 1; crossings [Q][3] (the three axes' crossing counts) or NULL.
+ * ghr_gaussian_probe_outside: xyz [P][3], scaling [P][3] ACTIVATED, rotation [P][4] raw (normalised in the kernel);
+ * outside [P] bytes: 1 iff all twelve probes xyz + (3-sigma image of a level-0 icosphere vertex) are outside.
+ * probe: GHR_PROBE_REFERENCE, the points of src/preprocessing/filter_flame_intersections.py:88,109 (R diag(3 s) v + xyz: that
+ * script's build_rotation returns the transpose of the rotation matrix R); GHR_PROBE_AXIS_SCALED, diag(3 s) Rt v + xyz.
+ * `header` is the HOST copy of the blob's header, `grid_dev` the blob on the device.  Q == 0 / P == 0 is GHR_OK and launches
+ * nothing.  A refused call launches nothing and ghr_last_error() says why. */
+#define GHR_PROBE_REFERENCE 0
+#define GHR_PROBE_AXIS_SCALED 1
+typedef struct ghr_mesh_grid {
+    uint32_t magic;
+    int32_t G, n_faces, n_vertices;
+    float lo[3], hi[3];      /* bounding box of the mesh */
+    float scale[3];          /* cells per unit along each world coordinate */
+    uint32_t list_total[3];  /* entries of each axis' cell lists */
+    uint32_t list_max[3];    /* longest cell list of each axis (filled by ghr_mesh_grid_build) */
+    uint32_t pad_;
+    uint64_t off_rec[3], off_start[3], off_list[3];  /* byte offsets into the blob */
+    uint64_t bytes;
+} ghr_mesh_grid;
+int ghr_mesh_grid_sizes(int32_t n_vertices, const float* vertices, int32_t n_faces, const int32_t* faces, int32_t G,
+                        ghr_mesh_grid* header);
+int ghr_mesh_grid_build(int32_t n_vertices, const float* vertices, int32_t n_faces, const int32_t* faces, int32_t G,
+                        void* blob, size_t bytes);
+int ghr_mesh_contains(void* stream, const ghr_mesh_grid* header, const void* grid_dev, int64_t Q, const float* points,
+                      uint8_t* inside, uint32_t* crossings);
+int ghr_gaussian_probe_outside(void* stream, const ghr_mesh_grid* header, const void* grid_dev, int64_t P, const float* xyz,
+                               const float* scaling, const float* rotation, int32_t probe, uint8_t* outside);
+
 /* Introspection for tests (device pointers into the workspaces; layout is otherwise private). */
 typedef struct ghr_ws_view {
     const float* rec;          /* [P][16]: x, y, conic a, b, c, opacity, features[10] */
