@@ -64,31 +64,6 @@ int k8_variant()
     return (e && std::strcmp(e, "cell") == 0) ? 0 : 2;
 }
 
-int launch_k8(size_t rows, uint32_t T, hipStream_t s, int W, int H, int gx, uint32_t T_tiles, const uint32_t* tile_start,
-               const uint32_t* point_list, const ghr::f4* rec, const float* bg, const float* final_T,
-               const uint32_t* n_contrib, const float* dL_dpix, const ghr::rect4* rects, float* ginst, uint32_t cap,
-               const unsigned long long* cell_mask, const uint32_t* cell_last, bool prezeroed,
-               const uint32_t* tile_order)
-{
-    const dim3 grid(ghr::xcd_grid(T)), block(GHR_BLOCK);
-    int v = k8_variant();
-    if (g_deterministic) v = 2;  // the ordered walk exists in the cell-list form
-    if (v == 2 && !ghr::b3_fits(rows, cap, (size_t)W, (size_t)H)) {
-        if (g_deterministic) return -1;  // the caller reports it: determinism is never dropped silently
-        v = 0;  // its 32-bit offsets
-    }
-    switch (v) {
-    case 2:
-        hipLaunchKernelGGL(ghr::k_render_bwd_cells, grid, dim3(GHR_B3_THREADS), 0, s, W, H, gx, T_tiles, tile_start, point_list, rec, bg,
-                           final_T, n_contrib, dL_dpix, rects, ginst, cap, cell_mask, cell_last, g_deterministic,
-                           prezeroed ? 1 : 0, tile_order);
-        break;
-    default:
-        hipLaunchKernelGGL(ghr::k_render_bwd, grid, block, 0, s, W, H, gx, T_tiles, tile_start, point_list, rec, bg,
-                           final_T, n_contrib, dL_dpix, rects, ginst, cap);
-    }
-    return 0;
-}
 #define GHR_E_DETERMINISTIC_MSG "ghr_set_deterministic(1) cannot be honoured at this size (the ordered walk needs 32-bit byte offsets: < 2^26 rows / instances)"
 
 int fail(int code, const char* fmt, const char* detail = "")
@@ -153,6 +128,8 @@ size_t carve_geom(char* base, size_t P, bool mode_b, Geom* g)
     ghr::rect4* rects = (ghr::rect4*)take(P * 16);
     uint32_t* slot_blk = (uint32_t*)take(((P + GHR_BLOCK - 1) / GHR_BLOCK) * 4);
     uint32_t* pos = (uint32_t*)take(P * 4 * GHR_BIG_RECT);
+    // cov3D stays last: an entry that is not told the mode (stage 2, the model calls) carves with mode_b = false and finds every
+    // other plane where a mode-B stage 1 put it
     float* cov3D = mode_b ? (float*)take(P * 24) : nullptr;
     if (g) *g = Geom{rec, depths, rects, slot_blk, pos, cov3D};
     return off + ALIGN;
@@ -215,6 +192,104 @@ int finish(hipStream_t s, int debug)
 }
 
 inline int grid_x(int W) { return (W + GHR_TILE - 1) / GHR_TILE; }
+inline int n_blocks(int rows) { return (rows + GHR_BLOCK - 1) / GHR_BLOCK; }
+inline float focal(int extent, float tan_fov) { return extent / (2.0f * tan_fov); }  // rasterizer_impl.cu:224-225
+
+// A view's three workspaces, carved: every entry point that touches them asks here, so there is one layout.  NULL
+// workspaces give NULL members.
+struct ViewWs {
+    Geom g; Img im; Bin b;
+    int gx, gy, T;
+};
+// `mode_b` (ghr_view_args without conic_precomp: stage 1 stores 3D covariances) decides g.cov3D and nothing else (carve_geom).
+ViewWs carve_view(size_t rows, int W, int H, bool mode_b, size_t R, const void* geom_ws, const void* img_ws, const void* bin_ws)
+{
+    ViewWs w;
+    w.gx = grid_x(W); w.gy = grid_x(H); w.T = w.gx * w.gy;
+    carve_geom(align_base(geom_ws), rows, mode_b, &w.g);
+    carve_img(align_base(img_ws), (size_t)W * H, (size_t)w.T, &w.im);
+    carve_bin(align_base(bin_ws), R, (size_t)w.T, &w.b);
+    return w;
+}
+
+// ---- the steps more than one entry point takes -------------------------------------------------------------------------
+// The per-tile counters before a pass's first projection: zero-filled, or -- a recycled workspace, whose counters k_tile_sort
+// left at zero -- taken on trust; under `debug` the promise is read back.  `not_zero`: the entry's words for a broken one.
+int zero_or_verify_counters(const ViewWs& w, int recycled, int debug, const char* not_zero, hipStream_t s)
+{
+    const size_t n = 2 * (size_t)w.T;
+    if (!recycled) GHR_HIP(hipMemsetAsync(w.im.tile_count, 0, sizeof(uint32_t) * n, s));
+    else if (debug) {
+        std::vector<uint32_t> h(n);
+        GHR_HIP(hipMemcpyAsync(h.data(), w.im.tile_count, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+        GHR_HIP(hipStreamSynchronize(s));
+        for (uint32_t v : h) if (v != 0) return fail(GHR_E_INVALID, "%s", not_zero);
+    }
+    return GHR_OK;
+}
+
+// k_tile_scan over the counters of `rows` projected rows; the instance count goes to *R_host (mapped_word)
+int tile_scan(const ViewWs& w, int rows, uint32_t* R_host, hipStream_t s)
+{
+    uint32_t* R_mapped = mapped_word(R_host);
+    hipLaunchKernelGGL(ghr::k_tile_scan, dim3(1), dim3(GHR_SCAN_BLOCK), 0, s, w.T, w.im.tile_count, w.im.small_cnt, w.im.tile_start,
+                       w.im.R_dev, w.g.slot_blk, n_blocks(rows), R_mapped, w.im.tile_order);
+    if (!R_mapped) GHR_HIP(hipMemcpyAsync(R_host, w.im.R_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    return GHR_OK;
+}
+
+// ghr_set_deterministic(1) is never dropped silently: the ordered walk exists in the cell-list form only (b3_fits)
+bool ordered_walk_refused(size_t rows, uint32_t R, int W, int H) { return g_deterministic && !ghr::b3_fits(rows, R, (size_t)W, (size_t)H); }
+
+// The pixel backward (K8) between the two profile events.  Nothing is launched at R == 0: ghr_render_backward does not
+// come here then, ghr_backward_ex does and goes on (k_geom_bwd writes the zero gradients).
+int pixel_backward(const ViewWs& w, size_t rows, int W, int H, uint32_t R, const float* bg, const float* dL_dpix, float* ginst,
+                   int prezeroed, hipStream_t s)
+{
+    if (g_ev[2]) GHR_HIP(hipEventRecord(g_ev[2], s));
+    if (R > 0) {
+        if (ordered_walk_refused(rows, R, W, H)) return fail(GHR_E_INVALID, GHR_E_DETERMINISTIC_MSG);
+        const dim3 grid(ghr::xcd_grid((uint32_t)w.T));
+        const uint32_t* order = order_ptr(w.im.tile_order, 2);
+        if ((g_deterministic || k8_variant() == 2) && ghr::b3_fits(rows, R, (size_t)W, (size_t)H))
+            hipLaunchKernelGGL(ghr::k_render_bwd_cells, grid, dim3(GHR_B3_THREADS), 0, s, W, H, w.gx, (uint32_t)w.T, w.im.tile_start,
+                               w.b.point_list, w.g.rec, bg, w.im.final_T, w.im.n_contrib, dL_dpix, w.g.rects, ginst, R, w.b.cell_mask,
+                               w.im.cell_last, g_deterministic, prezeroed ? 1 : 0, order);
+        else
+            hipLaunchKernelGGL(ghr::k_render_bwd, grid, dim3(GHR_BLOCK), 0, s, W, H, w.gx, (uint32_t)w.T, w.im.tile_start,
+                               w.b.point_list, w.g.rec, bg, w.im.final_T, w.im.n_contrib, dL_dpix, w.g.rects, ginst, R);
+    }
+    if (g_ev[3]) GHR_HIP(hipEventRecord(g_ev[3], s));
+    return GHR_OK;
+}
+
+void adam_fused_finish(const ghr_adam_fuse* af, hipStream_t s)
+{
+    hipLaunchKernelGGL(ghr::k_adam_fused_finish, dim3(1024), dim3(256), 0, s, (long long)af->n, af->p_in, af->m_in, af->v_in,
+                       af->p_out, af->m_out, af->v_out, af->state, (const int*)af->flag, af->flag_next);
+}
+
+// ---- rules more than one entry point states ------------------------------------------------------------------------------
+// The shape of SH features: a degree of 0 .. 3, K = sh_coeffs = (max_sh_degree + 1)^2 coefficients per channel (the kernels'
+// 16-B staging of features_rest counts on rows of >= 9 floats), and K covers the degree.
+inline bool sh_degree_ok(int degree) { return degree >= 0 && degree <= 3; }
+inline bool sh_coeffs_ok(int K) { return K == 1 || K == 4 || K == 9 || K == 16; }
+inline bool sh_covers(int degree, int K) { return (degree + 1) * (degree + 1) <= K; }
+
+// the cell masks' 32-bit byte offsets (stage 2)
+inline bool cell_masks_fit(uint32_t R, int W, int H) { return ghr::mask_groups(R, (size_t)grid_x(W) * grid_x(H)) * 128 < ((size_t)1 << 32); }
+// the densification statistics of the projection backward: all three buffers or none
+inline int n_dens(const ghr_model_args* m) { return (m->dens_grad_accum != nullptr) + (m->dens_denom != nullptr) + (m->dens_max_radii2D != nullptr); }
+inline bool dens_all_or_none(const ghr_model_args* m) { return n_dens(m) == 0 || n_dens(m) == 3; }
+// The projection backward stores nothing in d_features_dc / d_features_rest (they may be NULL) in the factored form -- the SH
+// gradients leave as d_rgb (ABI 19) -- and when the call carries the update (ghr_adam_fuse) without earlier views' gradients to add.
+inline bool sh_grads_unstored(const ghr_model_args* m, bool factored, int accumulate) { return factored || (m->adam_fuse && !accumulate); }
+// ghr_sh_grad_from_views: its sizes, and two views' tables [3 P] must not overlap
+inline bool sh_views_sizes_ok(int P, int degree, int K, int n_views, int64_t view_stride, int64_t campos_stride)
+{
+    return P >= 0 && n_views >= 0 && sh_degree_ok(degree) && sh_coeffs_ok(K) && sh_covers(degree, K) && view_stride >= 0 && campos_stride >= 0;
+}
+inline bool sh_views_overlap(int P, int n_views, int64_t view_stride) { return n_views > 1 && view_stride < 3 * (int64_t)P; }
 
 }  // namespace
 
@@ -247,64 +322,54 @@ int ghr_forward_stage1(void* stream, const ghr_view_args* a, void* geom_ws, void
     hipStream_t s = (hipStream_t)stream;
     if (a->P == 0) { *R_host = 0; return GHR_OK; }
     if (!geom_ws || !img_ws || !radii) return fail(GHR_E_INVALID, "workspace/radii is NULL");
-    const bool mode_b = a->conic_precomp == nullptr;
-    const int gx = grid_x(a->W), gy = grid_x(a->H);
-    const int T = gx * gy;
-    Geom g; Img im;
-    carve_geom(align_base(geom_ws), (size_t)a->P, mode_b, &g);
-    carve_img(align_base(img_ws), (size_t)a->W * a->H, (size_t)T, &im);
-
-    // (a recycled workspace -- ghr_view_args.img_ws_recycled -- has its counters at zero already: k_tile_sort left them there)
-    if (!a->img_ws_recycled) GHR_HIP(hipMemsetAsync(im.tile_count, 0, sizeof(uint32_t) * 2 * (size_t)T, s));
-    else if (a->debug) {
-        std::vector<uint32_t> h(2 * (size_t)T);
-        GHR_HIP(hipMemcpyAsync(h.data(), im.tile_count, sizeof(uint32_t) * h.size(), hipMemcpyDeviceToHost, s));
-        GHR_HIP(hipStreamSynchronize(s));
-        for (uint32_t v : h)
-            if (v != 0) return fail(GHR_E_INVALID, "ghr_view_args.img_ws_recycled is set but the workspace's per-tile counters are not zero");
-    }
+    const ViewWs w = carve_view((size_t)a->P, a->W, a->H, a->conic_precomp == nullptr, 0, geom_ws, img_ws, nullptr);
+    if (int rc = zero_or_verify_counters(w, a->img_ws_recycled, a->debug,
+                                         "ghr_view_args.img_ws_recycled is set but the workspace's per-tile counters are not zero", s))
+        return rc;
     ghr::PreArgs pa;
-    pa.P = a->P; pa.W = a->W; pa.H = a->H; pa.gx = gx; pa.gy = gy;
+    pa.P = a->P; pa.W = a->W; pa.H = a->H; pa.gx = w.gx; pa.gy = w.gy;
     pa.means3D = a->means3D; pa.colors = a->colors; pa.opacities = a->opacities;
     pa.scales = a->scales; pa.rotations = a->rotations;
     pa.cov3D_precomp = a->cov3D_precomp; pa.conic_precomp = a->conic_precomp;
     pa.view = a->viewmatrix; pa.proj = a->projmatrix;
     pa.scale_modifier = a->scale_modifier; pa.tan_fovx = a->tan_fovx; pa.tan_fovy = a->tan_fovy;
-    pa.focal_y = a->H / (2.0f * a->tan_fovy);  // rasterizer_impl.cu:224-225
-    pa.focal_x = a->W / (2.0f * a->tan_fovx);
-    pa.rec = g.rec; pa.depths = g.depths; pa.rects = g.rects; pa.cov3D = g.cov3D; pa.radii = radii;
-    pa.tile_count = im.tile_count; pa.slot_blk = g.slot_blk; pa.pos = g.pos;
-    hipLaunchKernelGGL(ghr::k_preprocess, dim3((a->P + GHR_BLOCK - 1) / GHR_BLOCK), dim3(GHR_BLOCK), 0, s, pa);
-    uint32_t* R_mapped = mapped_word(R_host);
-    hipLaunchKernelGGL(ghr::k_tile_scan, dim3(1), dim3(GHR_SCAN_BLOCK), 0, s, T, im.tile_count, im.small_cnt, im.tile_start, im.R_dev,
-                       g.slot_blk, (a->P + GHR_BLOCK - 1) / GHR_BLOCK, R_mapped, im.tile_order);
-    if (!R_mapped) GHR_HIP(hipMemcpyAsync(R_host, im.R_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    pa.focal_y = focal(a->H, a->tan_fovy); pa.focal_x = focal(a->W, a->tan_fovx);
+    pa.rec = w.g.rec; pa.depths = w.g.depths; pa.rects = w.g.rects; pa.cov3D = w.g.cov3D; pa.radii = radii;
+    pa.tile_count = w.im.tile_count; pa.slot_blk = w.g.slot_blk; pa.pos = w.g.pos;
+    hipLaunchKernelGGL(ghr::k_preprocess, dim3(n_blocks(a->P)), dim3(GHR_BLOCK), 0, s, pa);
+    if (int rc = tile_scan(w, a->P, R_host, s)) return rc;
     return finish(s, a->debug);
+}
+
+// Each call ghr_view_step composes is a check and a run.  The check launches nothing and touches neither device memory nor
+// the HIP runtime; it returns what the entry point refuses.  The run takes checked arguments.  ghr_view_step asks all the
+// checks before the first run: a struct that only the last call refuses must not leave five calls' kernels in the stream.
+static int check_forward_stage2(const ghr_view_args* a, uint32_t R, const void* geom_ws, const void* img_ws, const void* bin_ws,
+                                const float* out_color)
+{
+    if (int rc = check_dims(a)) return rc;  // stage 2 only reads P, W, H, C, background (+ debug)
+    if (!out_color) return fail(GHR_E_INVALID, "out_color is NULL");
+    if (a->P > 0 && !a->background) return fail(GHR_E_INVALID, "background is NULL");
+    if (a->P == 0) return GHR_OK;
+    if (!geom_ws || !img_ws || (R > 0 && !bin_ws)) return fail(GHR_E_INVALID, "workspace is NULL");
+    if (!cell_masks_fit(R, a->W, a->H)) return fail(GHR_E_INVALID, "too many instances for the 32-bit offsets of the cell masks");
+    return GHR_OK;
 }
 
 int ghr_forward_stage2(void* stream, const ghr_view_args* a, uint32_t R, void* geom_ws, void* img_ws, void* bin_ws,
                        float* out_color, float* grad_scratch)
 {
-    if (int rc = check_dims(a)) return rc;  // stage 2 only reads P, W, H, C, background (+ debug)
-    if (!out_color) return fail(GHR_E_INVALID, "out_color is NULL");
-    if (a->P > 0 && !a->background) return fail(GHR_E_INVALID, "background is NULL");
+    if (int rc = check_forward_stage2(a, R, geom_ws, img_ws, bin_ws, out_color)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int gx = grid_x(a->W), gy = grid_x(a->H);
-    const int T = gx * gy;
     if (a->P == 0) {
         // Nothing to splat: the reference skips the whole forward and returns the zero-filled image
         // (rasterize_points.cu:70,87); keep that.
         GHR_HIP(hipMemsetAsync(out_color, 0, sizeof(float) * (size_t)a->C * a->W * a->H, s));
         return finish(s, a->debug);
     }
-    if (!geom_ws || !img_ws || (R > 0 && !bin_ws)) return fail(GHR_E_INVALID, "workspace is NULL");
-    if (ghr::mask_groups((size_t)R, (size_t)T) * 128 >= ((size_t)1 << 32))
-        return fail(GHR_E_INVALID, "too many instances for the 32-bit offsets of the cell masks");
-    // the cov3D plane (mode B) lies behind everything stage 2 touches, so the carve is mode-independent here
-    Geom g; Img im; Bin b;
-    carve_geom(align_base(geom_ws), (size_t)a->P, false, &g);
-    carve_img(align_base(img_ws), (size_t)a->W * a->H, (size_t)T, &im);
-    carve_bin(bin_ws ? align_base(bin_ws) : nullptr, (size_t)R, (size_t)T, &b);
+    const ViewWs w = carve_view((size_t)a->P, a->W, a->H, false, R, geom_ws, img_ws, bin_ws);
+    const Geom& g = w.g; const Img& im = w.im; const Bin& b = w.b;
+    const int gx = w.gx, T = w.T;
     if (R > 0) {
         // append cursors are 0 on entry: k_tile_scan leaves them there and k_tile_sort resets them (replay-safe)
         const int scatter_blocks = (a->P + 127) / 128;  // a wave serves 32 Gaussians
@@ -378,31 +443,15 @@ int ghr_backward_ex(void* stream, const ghr_view_args* a, uint32_t R, const int3
     if (!radii || !geom_ws || !img_ws || (R > 0 && !bin_ws) || !dL_dpix || (R > 0 && !grad_scratch) || !dL_dmeans2D ||
         !dL_dconic || !dL_dopacity || !dL_dcolors || !dL_dmeans3D || !dL_dcov3D || !dL_dscales || !dL_drotations)
         return fail(GHR_E_INVALID, "ghr_backward: NULL buffer");
-    const bool mode_b = a->conic_precomp == nullptr;
-    const int gx = grid_x(a->W), gy = grid_x(a->H);
-    const int T = gx * gy;
-    Geom g; Img im; Bin b;
-    carve_geom(align_base(geom_ws), (size_t)a->P, mode_b, &g);
-    carve_img(align_base(img_ws), (size_t)a->W * a->H, (size_t)T, &im);
-    carve_bin(bin_ws ? align_base(bin_ws) : nullptr, (size_t)R, (size_t)T, &b);
-
-    if (g_ev[2]) GHR_HIP(hipEventRecord(g_ev[2], s));
-    if (R > 0 &&
-        launch_k8((size_t)a->P, (uint32_t)T, s, a->W, a->H, gx, (uint32_t)T, (const uint32_t*)im.tile_start,
-                  (const uint32_t*)b.point_list, (const ghr::f4*)g.rec, a->background, (const float*)im.final_T,
-                  (const uint32_t*)im.n_contrib, dL_dpix, (const ghr::rect4*)g.rects, grad_scratch, R,
-                  (const unsigned long long*)b.cell_mask, (const uint32_t*)im.cell_last, prezeroed != 0,
-                  order_ptr((const uint32_t*)im.tile_order, 2)))
-        return fail(GHR_E_INVALID, GHR_E_DETERMINISTIC_MSG);
-    if (g_ev[3]) GHR_HIP(hipEventRecord(g_ev[3], s));
+    const ViewWs w = carve_view((size_t)a->P, a->W, a->H, a->conic_precomp == nullptr, R, geom_ws, img_ws, bin_ws);
+    if (int rc = pixel_backward(w, (size_t)a->P, a->W, a->H, R, a->background, dL_dpix, grad_scratch, prezeroed, s)) return rc;
     ghr::GeomBwdArgs ga;
     ga.P = a->P; ga.means3D = a->means3D; ga.radii = radii; ga.scales = a->scales; ga.rotations = a->rotations;
-    ga.cov3D = g.cov3D; ga.conic_precomp = a->conic_precomp; ga.view = a->viewmatrix; ga.proj = a->projmatrix;
+    ga.cov3D = w.g.cov3D; ga.conic_precomp = a->conic_precomp; ga.view = a->viewmatrix; ga.proj = a->projmatrix;
     ga.scale_modifier = a->scale_modifier; ga.tan_fovx = a->tan_fovx; ga.tan_fovy = a->tan_fovy;
-    ga.focal_y = a->H / (2.0f * a->tan_fovy);
-    ga.focal_x = a->W / (2.0f * a->tan_fovx);
-    ga.ginst = grad_scratch; ga.inst_line = b.inst_line; ga.ginst_rows = R;
-    ga.rects = g.rects; ga.rec = g.rec; ga.half_w = 0.5f * a->W; ga.half_h = 0.5f * a->H;
+    ga.focal_y = focal(a->H, a->tan_fovy); ga.focal_x = focal(a->W, a->tan_fovx);
+    ga.ginst = grad_scratch; ga.inst_line = w.b.inst_line; ga.ginst_rows = R;
+    ga.rects = w.g.rects; ga.rec = w.g.rec; ga.half_w = 0.5f * a->W; ga.half_h = 0.5f * a->H;
     ga.dL_dmeans2D = dL_dmeans2D; ga.dL_dconic = dL_dconic; ga.dL_dconic3 = dL_dconic3; ga.dL_dopacity = dL_dopacity; ga.dL_dcolors = dL_dcolors;
     ga.dL_dmeans3D = dL_dmeans3D; ga.dL_dcov3D = dL_dcov3D; ga.dL_dscales = dL_dscales; ga.dL_drots = dL_drotations;
     hipLaunchKernelGGL(ghr::k_geom_bwd, dim3((a->P + GHR_BLOCK - 1) / GHR_BLOCK), dim3(GHR_BLOCK), 0, s, ga);
@@ -414,11 +463,9 @@ int fill_model(const ghr_model_args* m, ghr::ModelArgs* a)
 {
     if (!m) return fail(GHR_E_INVALID, "ghr_model_args is NULL");
     if (m->P < 0 || m->W <= 0 || m->H <= 0) return fail(GHR_E_INVALID, "bad P/W/H");
-    if (m->sh_degree < 0 || m->sh_degree > 3 || m->sh_coeffs < (m->sh_degree + 1) * (m->sh_degree + 1) ||
-        m->sh_coeffs > GHR_SH_MAX)
+    if (!sh_degree_ok(m->sh_degree) || !sh_covers(m->sh_degree, m->sh_coeffs) || m->sh_coeffs > GHR_SH_MAX)
         return fail(GHR_E_INVALID, "bad sh_degree / sh_coeffs");
-    // K = (max_sh_degree + 1)^2 (include/ghr.h): the kernels' 16-B staging of features_rest counts on rows of >= 9 floats
-    if (m->sh_coeffs != 1 && m->sh_coeffs != 4 && m->sh_coeffs != 9 && m->sh_coeffs != 16)
+    if (!sh_coeffs_ok(m->sh_coeffs))
         return fail(GHR_E_INVALID, "ghr_model_args: sh_coeffs must be (max_sh_degree + 1)^2, i.e. 1, 4, 9 or 16");
     if (m->mode != 0 && m->mode != 1) return fail(GHR_E_INVALID, "ghr_model_args: mode must be 0 or 1");
     if (m->row0 < 0 || (m->row0 & (GHR_BLOCK - 1))) return fail(GHR_E_INVALID, "ghr_model_args: row0 must be a multiple of 256");
@@ -437,8 +484,7 @@ int fill_model(const ghr_model_args* m, ghr::ModelArgs* a)
     a->features_dc = m->features_dc; a->features_rest = m->features_rest;
     a->view = m->viewmatrix; a->proj = m->projmatrix; a->campos = m->campos;
     a->scale_modifier = m->scale_modifier; a->tan_fovx = m->tan_fovx; a->tan_fovy = m->tan_fovy;
-    a->focal_y = m->H / (2.0f * m->tan_fovy);
-    a->focal_x = m->W / (2.0f * m->tan_fovx);
+    a->focal_y = focal(m->H, m->tan_fovy); a->focal_x = focal(m->W, m->tan_fovx);
     a->conic_eps = m->conic_eps;
     if ((m->fovx_dev != nullptr) != (m->fovy_dev != nullptr)) return fail(GHR_E_INVALID, "ghr_model_args: fovx_dev and fovy_dev: both or neither");
     a->fovx = m->fovx_dev; a->fovy = m->fovy_dev;
@@ -446,7 +492,6 @@ int fill_model(const ghr_model_args* m, ghr::ModelArgs* a)
     a->tile_count = nullptr; a->slot_blk = nullptr; a->pos = nullptr;
     return GHR_OK;
 }
-inline int n_blocks(int rows) { return (rows + GHR_BLOCK - 1) / GHR_BLOCK; }
 // The checks and the host-side table of a backward call that carries the optimizer update (ghr_adam_fuse): which group each
 // raw-parameter array of `a` lies in and its learning rate.  Launches nothing (ghr_view_step validates with it up front).
 int fill_adam_fuse(const ghr::ModelArgs& a, const ghr_adam_fuse* af, int32_t accumulate, const int32_t* nan_flag,
@@ -486,16 +531,15 @@ int fill_adam_fuse(const ghr::ModelArgs& a, const ghr_adam_fuse* af, int32_t acc
     mg->adam.on = 1;
     return GHR_OK;
 }
-}  // namespace
 
-namespace {
 // Everything a shared-feature segment call refuses, before anything else is looked at (and long before a launch).
+// (sh_degree is left to fill_model, which every such call goes through next)
 int check_shared(const char* who, const ghr_model_args* m, const ghr_shared_features* sf)
 {
     if (!m) return fail(GHR_E_INVALID, "ghr_model_args is NULL");
     if (!sf) return fail(GHR_E_INVALID, "%s: ghr_shared_features is NULL", who);
     if (m->mode != 1) return fail(GHR_E_INVALID, "%s: mode must be 1 (explicit Gaussians)", who);
-    if (m->sh_coeffs != 1 && m->sh_coeffs != 4 && m->sh_coeffs != 9 && m->sh_coeffs != 16)
+    if (!sh_coeffs_ok(m->sh_coeffs))
         return fail(GHR_E_INVALID, "%s: sh_coeffs must be 1, 4, 9 or 16", who);
     if (sf->rows_per_strand < 1) return fail(GHR_E_INVALID, "%s: rows_per_strand must be >= 1", who);
     if (sf->n_strands < 0 || (long long)sf->n_strands * sf->rows_per_strand != (long long)m->P)
@@ -506,9 +550,66 @@ int check_shared(const char* who, const ghr_model_args* m, const ghr_shared_feat
     return GHR_OK;
 }
 
+// ---- the projection forward of a segment ---------------------------------------------------------------------------------
+int check_forward_segment(const ghr_model_args* m, int32_t rows_total, const void* geom_ws, const void* img_ws,
+                          const int32_t* radii, ghr::ModelArgs* a)
+{
+    if (int rc = fill_model(m, a)) return rc;
+    if (rows_total < 0 || (long long)a->row0 + a->P > rows_total) return fail(GHR_E_INVALID, "segment exceeds rows_total");
+    if (rows_total == 0) return GHR_OK;
+    if (!geom_ws || !img_ws || !radii) return fail(GHR_E_INVALID, "workspace/radii is NULL");
+    return GHR_OK;
+}
+
 // sf != NULL: features_dc / features_rest of `m` are per strand (checked by check_shared)
+int run_forward_segment(ghr::ModelArgs& a, const ghr_model_args* m, const ghr_shared_features* sf, hipStream_t s,
+                        int32_t rows_total, int32_t first, void* geom_ws, void* img_ws, int32_t* radii, float* means2D_out)
+{
+    if (rows_total == 0) return GHR_OK;
+    const ViewWs w = carve_view((size_t)rows_total, a.W, a.H, false, 0, geom_ws, img_ws, nullptr);
+    if (first)
+        if (int rc = zero_or_verify_counters(w, m->img_ws_recycled, m->debug,
+                                             "ghr_model_args.img_ws_recycled is set but the workspace's per-tile counters are not zero "
+                                             "(was it through stage 1 AND stage 2 of a pass with P > 0 at the same W x H?)", s))
+            return rc;
+    // rows between the end of this segment and the next multiple of 256 are padding: culled, no gradient slots
+    const int end = a.row0 + a.P;
+    const int pad_end = (int)std::min<long long>((long long)n_blocks(end) * GHR_BLOCK, rows_total);
+    if (pad_end > end) {
+        GHR_HIP(hipMemsetAsync(w.g.rects + end, 0, sizeof(ghr::rect4) * (size_t)(pad_end - end), s));
+        GHR_HIP(hipMemsetAsync(radii + end, 0, sizeof(int32_t) * (size_t)(pad_end - end), s));
+    }
+    if (a.P == 0) return finish(s, m->debug);
+    a.rec = w.g.rec; a.depths = w.g.depths; a.rects = w.g.rects; a.radii = radii; a.means2D = means2D_out;
+    a.tile_count = w.im.tile_count; a.slot_blk = w.g.slot_blk; a.pos = w.g.pos;
+    if (sf) {
+        const ghr::SharedFeat k{sf->n_strands, sf->rows_per_strand, a.features_dc, a.features_rest};
+        a.features_dc = a.xyz;  // load_raw reads 3 floats per ROW there; the kernel replaces them by the strand's
+        a.features_rest = nullptr;
+        if (a.sh_coeffs > 1) hipLaunchKernelGGL(ghr::k_shared_proj_fwd<true>, dim3(n_blocks(a.P)), dim3(GHR_BLOCK), 0, s, a, k);
+        else hipLaunchKernelGGL(ghr::k_shared_proj_fwd<false>, dim3(n_blocks(a.P)), dim3(GHR_BLOCK), 0, s, a, k);
+    } else if (a.sh_coeffs > 1) hipLaunchKernelGGL(ghr::k_project<true>, dim3(n_blocks(a.P)), dim3(GHR_BLOCK), 0, s, a);
+    else hipLaunchKernelGGL(ghr::k_project<false>, dim3(n_blocks(a.P)), dim3(GHR_BLOCK), 0, s, a);
+    return finish(s, m->debug);
+}
+
 int forward_segment(const ghr_model_args* m, const ghr_shared_features* sf, void* stream, int32_t rows_total, int32_t first,
-                    void* geom_ws, void* img_ws, int32_t* radii, float* means2D_out);
+                    void* geom_ws, void* img_ws, int32_t* radii, float* means2D_out)
+{
+    ghr::ModelArgs a;
+    if (int rc = check_forward_segment(m, rows_total, geom_ws, img_ws, radii, &a)) return rc;
+    return run_forward_segment(a, m, sf, (hipStream_t)stream, rows_total, first, geom_ws, img_ws, radii, means2D_out);
+}
+
+int check_model_forward_stage1(const ghr_model_args* m, const void* geom_ws, const void* img_ws, const int32_t* radii,
+                               const uint32_t* R_host, ghr::ModelArgs* a)
+{
+    if (!m) return fail(GHR_E_INVALID, "ghr_model_args is NULL");
+    if (m->row0 != 0) return fail(GHR_E_INVALID, "ghr_model_forward_stage1: row0 must be 0 (use the segment calls)");
+    if (!R_host) return fail(GHR_E_INVALID, "R_host is NULL");
+    // (ghr_model_forward_finish has nothing to add: its sizes, R_host and workspaces are the ones checked here)
+    return check_forward_segment(m, m->P, geom_ws, img_ws, radii, a);
+}
 }  // namespace
 
 int ghr_model_forward_segment(void* stream, const ghr_model_args* m, int32_t rows_total, int32_t first, void* geom_ws,
@@ -528,54 +629,6 @@ int ghr_model_forward_segment_shared(void* stream, const ghr_model_args* m, cons
     return forward_segment(m, sf, stream, rows_total, first, geom_ws, img_ws, radii, means2D_out);
 }
 
-namespace {
-int forward_segment(const ghr_model_args* m, const ghr_shared_features* sf, void* stream, int32_t rows_total, int32_t first,
-                    void* geom_ws, void* img_ws, int32_t* radii, float* means2D_out)
-{
-    ghr::ModelArgs a;
-    if (int rc = fill_model(m, &a)) return rc;
-    if (rows_total < 0 || (long long)a.row0 + a.P > rows_total) return fail(GHR_E_INVALID, "segment exceeds rows_total");
-    hipStream_t s = (hipStream_t)stream;
-    if (rows_total == 0) return GHR_OK;
-    if (!geom_ws || !img_ws || !radii) return fail(GHR_E_INVALID, "workspace/radii is NULL");
-    const int T = a.gx * a.gy;
-    Geom g; Img im;
-    carve_geom(align_base(geom_ws), (size_t)rows_total, false, &g);
-    carve_img(align_base(img_ws), (size_t)a.W * a.H, (size_t)T, &im);
-    // (a recycled workspace -- ghr_model_args.img_ws_recycled -- has its counters at zero already: k_tile_sort left them there)
-    if (first && !m->img_ws_recycled) GHR_HIP(hipMemsetAsync(im.tile_count, 0, sizeof(uint32_t) * 2 * (size_t)T, s));
-    if (first && m->img_ws_recycled && m->debug) {
-        // the promise is otherwise taken on trust: under `debug` the counters are read back and must all be zero
-        std::vector<uint32_t> h(2 * (size_t)T);
-        GHR_HIP(hipMemcpyAsync(h.data(), im.tile_count, sizeof(uint32_t) * h.size(), hipMemcpyDeviceToHost, s));
-        GHR_HIP(hipStreamSynchronize(s));
-        for (uint32_t v : h)
-            if (v != 0)
-                return fail(GHR_E_INVALID, "ghr_model_args.img_ws_recycled is set but the workspace's per-tile counters are not zero "
-                                           "(was it through stage 1 AND stage 2 of a pass with P > 0 at the same W x H?)");
-    }
-    // rows between the end of this segment and the next multiple of 256 are padding: culled, no gradient slots
-    const int end = a.row0 + a.P;
-    const int pad_end = (int)std::min<long long>((long long)n_blocks(end) * GHR_BLOCK, rows_total);
-    if (pad_end > end) {
-        GHR_HIP(hipMemsetAsync(g.rects + end, 0, sizeof(ghr::rect4) * (size_t)(pad_end - end), s));
-        GHR_HIP(hipMemsetAsync(radii + end, 0, sizeof(int32_t) * (size_t)(pad_end - end), s));
-    }
-    if (a.P == 0) return finish(s, m->debug);
-    a.rec = g.rec; a.depths = g.depths; a.rects = g.rects; a.radii = radii; a.means2D = means2D_out;
-    a.tile_count = im.tile_count; a.slot_blk = g.slot_blk; a.pos = g.pos;
-    if (sf) {
-        const ghr::SharedFeat k{sf->n_strands, sf->rows_per_strand, a.features_dc, a.features_rest};
-        a.features_dc = a.xyz;  // load_raw reads 3 floats per ROW there; the kernel replaces them by the strand's
-        a.features_rest = nullptr;
-        if (a.sh_coeffs > 1) hipLaunchKernelGGL(ghr::k_shared_proj_fwd<true>, dim3(n_blocks(a.P)), dim3(GHR_BLOCK), 0, s, a, k);
-        else hipLaunchKernelGGL(ghr::k_shared_proj_fwd<false>, dim3(n_blocks(a.P)), dim3(GHR_BLOCK), 0, s, a, k);
-    } else if (a.sh_coeffs > 1) hipLaunchKernelGGL(ghr::k_project<true>, dim3(n_blocks(a.P)), dim3(GHR_BLOCK), 0, s, a);
-    else hipLaunchKernelGGL(ghr::k_project<false>, dim3(n_blocks(a.P)), dim3(GHR_BLOCK), 0, s, a);
-    return finish(s, m->debug);
-}
-}  // namespace
-
 int ghr_model_forward_finish(void* stream, int32_t rows_total, int32_t W, int32_t H, int32_t debug, void* geom_ws,
                              void* img_ws, uint32_t* R_host)
 {
@@ -584,60 +637,162 @@ int ghr_model_forward_finish(void* stream, int32_t rows_total, int32_t W, int32_
     hipStream_t s = (hipStream_t)stream;
     if (rows_total == 0) { *R_host = 0; return GHR_OK; }
     if (!geom_ws || !img_ws) return fail(GHR_E_INVALID, "workspace is NULL");
-    const int T = grid_x(W) * grid_x(H);
-    Geom g; Img im;
-    carve_geom(align_base(geom_ws), (size_t)rows_total, false, &g);
-    carve_img(align_base(img_ws), (size_t)W * H, (size_t)T, &im);
-    uint32_t* R_mapped = mapped_word(R_host);
-    hipLaunchKernelGGL(ghr::k_tile_scan, dim3(1), dim3(GHR_SCAN_BLOCK), 0, s, T, im.tile_count, im.small_cnt, im.tile_start, im.R_dev,
-                       g.slot_blk, n_blocks(rows_total), R_mapped, im.tile_order);
-    if (!R_mapped) GHR_HIP(hipMemcpyAsync(R_host, im.R_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    const ViewWs w = carve_view((size_t)rows_total, W, H, false, 0, geom_ws, img_ws, nullptr);
+    if (int rc = tile_scan(w, rows_total, R_host, s)) return rc;
     return finish(s, debug);
 }
 
 int ghr_model_forward_stage1(void* stream, const ghr_model_args* m, void* geom_ws, void* img_ws, int32_t* radii,
                              float* means2D_out, uint32_t* R_host)
 {
-    if (!m) return fail(GHR_E_INVALID, "ghr_model_args is NULL");
-    if (m->row0 != 0) return fail(GHR_E_INVALID, "ghr_model_forward_stage1: row0 must be 0 (use the segment calls)");
-    if (!R_host) return fail(GHR_E_INVALID, "R_host is NULL");
-    if (int rc = ghr_model_forward_segment(stream, m, m->P, 1, geom_ws, img_ws, radii, means2D_out)) return rc;
+    ghr::ModelArgs a;
+    if (int rc = check_model_forward_stage1(m, geom_ws, img_ws, radii, R_host, &a)) return rc;
+    if (int rc = run_forward_segment(a, m, nullptr, (hipStream_t)stream, m->P, 1, geom_ws, img_ws, radii, means2D_out)) return rc;
     return ghr_model_forward_finish(stream, m->P, m->W, m->H, m->debug, geom_ws, img_ws, R_host);
+}
+
+static int check_render_backward(int32_t rows_total, int32_t W, int32_t H, uint32_t R, const float* background, const void* geom_ws,
+                                 const void* img_ws, const void* bin_ws, const float* dL_dpix, const float* grad_scratch)
+{
+    if (rows_total < 0 || W <= 0 || H <= 0) return fail(GHR_E_INVALID, "bad rows_total/W/H");
+    if (rows_total == 0 || R == 0) return GHR_OK;
+    if (!background || !geom_ws || !img_ws || !bin_ws || !dL_dpix || !grad_scratch)
+        return fail(GHR_E_INVALID, "ghr_render_backward: NULL buffer");
+    if (ordered_walk_refused((size_t)rows_total, R, W, H)) return fail(GHR_E_INVALID, GHR_E_DETERMINISTIC_MSG);
+    return GHR_OK;
 }
 
 int ghr_render_backward(void* stream, int32_t rows_total, int32_t W, int32_t H, uint32_t R, const float* background,
                         const void* geom_ws, const void* img_ws, const void* bin_ws, const float* dL_dpix,
                         float* grad_scratch, int32_t prezeroed)
 {
-    if (rows_total < 0 || W <= 0 || H <= 0) return fail(GHR_E_INVALID, "bad rows_total/W/H");
-    hipStream_t s = (hipStream_t)stream;
+    if (int rc = check_render_backward(rows_total, W, H, R, background, geom_ws, img_ws, bin_ws, dL_dpix, grad_scratch)) return rc;
     if (rows_total == 0 || R == 0) return GHR_OK;
-    if (!background || !geom_ws || !img_ws || !bin_ws || !dL_dpix || !grad_scratch)
-        return fail(GHR_E_INVALID, "ghr_render_backward: NULL buffer");
-    const int gx = grid_x(W), T = gx * grid_x(H);
-    Geom g; Img im; Bin b;
-    carve_geom(align_base(geom_ws), (size_t)rows_total, false, &g);
-    carve_img(align_base(img_ws), (size_t)W * H, (size_t)T, &im);
-    carve_bin(align_base(bin_ws), (size_t)R, (size_t)T, &b);
-    if (g_ev[2]) GHR_HIP(hipEventRecord(g_ev[2], s));
-    if (launch_k8((size_t)rows_total, (uint32_t)T, s, W, H, gx, (uint32_t)T, (const uint32_t*)im.tile_start,
-                  (const uint32_t*)b.point_list, (const ghr::f4*)g.rec, background, (const float*)im.final_T,
-                  (const uint32_t*)im.n_contrib, dL_dpix, (const ghr::rect4*)g.rects, grad_scratch, R,
-                  (const unsigned long long*)b.cell_mask, (const uint32_t*)im.cell_last, prezeroed != 0,
-                  order_ptr((const uint32_t*)im.tile_order, 2)))
-        return fail(GHR_E_INVALID, GHR_E_DETERMINISTIC_MSG);
-    if (g_ev[3]) GHR_HIP(hipEventRecord(g_ev[3], s));
+    hipStream_t s = (hipStream_t)stream;
+    const ViewWs w = carve_view((size_t)rows_total, W, H, false, R, geom_ws, img_ws, bin_ws);
+    if (int rc = pixel_backward(w, (size_t)rows_total, W, H, R, background, dL_dpix, grad_scratch, prezeroed, s)) return rc;
+    return finish(s, 0);
+}
+
+int ghr_shared_sh_fold(void* stream, const ghr_shared_features* sf, int32_t sh_degree, int32_t sh_coeffs, const float* xyz,
+                       const float* campos, const float* d_rgb, float* d_features_dc, float* d_features_rest, int32_t* nan_flag)
+{
+    static const char* who = "ghr_shared_sh_fold";
+    if (!sf) return fail(GHR_E_INVALID, "%s: ghr_shared_features is NULL", who);
+    if (sf->rows_per_strand < 1 || sf->n_strands < 0 || (long long)sf->n_strands * sf->rows_per_strand > 0x7fffffffLL)
+        return fail(GHR_E_INVALID, "%s: bad n_strands / rows_per_strand", who);
+    if (!sh_coeffs_ok(sh_coeffs)) return fail(GHR_E_INVALID, "%s: sh_coeffs must be 1, 4, 9 or 16", who);
+    // (a degree above 3 is not covered by any such sh_coeffs)
+    if (sh_degree < 0 || !sh_covers(sh_degree, sh_coeffs)) return fail(GHR_E_INVALID, "%s: bad sh_degree", who);
+    if (sf->n_strands == 0) return GHR_OK;
+    if (!xyz || !campos || !d_rgb || !d_features_dc || (sh_coeffs > 1 && !d_features_rest))
+        return fail(GHR_E_INVALID, "%s: NULL buffer", who);
+    ghr::SharedFoldArgs fa;
+    fa.S = sf->n_strands; fa.n_seg = sf->rows_per_strand; fa.sh_degree = sh_degree; fa.sh_coeffs = sh_coeffs;
+    fa.xyz = xyz; fa.campos = campos; fa.d_rgb = d_rgb; fa.d_dc = d_features_dc; fa.d_rest = d_features_rest;
+    fa.nan_flag = nan_flag;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ghr::k_shared_sh_fold, dim3(fa.S), dim3(GHR_PBW_BLOCK), 0, s, fa);
     return finish(s, 0);
 }
 
 namespace {
+// where the projection backward of a segment leaves its gradients
+struct ProjGrads {
+    float *means2D, *xyz, *log_scales, *rotations, *opacity_logit, *label_logit, *orient_conf_log, *features_dc, *features_rest, *dir3d;
+};
+// Fills `a` and the optimizer table of `mg` (fill_adam_fuse).
+int check_backward_segment(const ghr_model_args* m, const ghr_shared_features* sf, int32_t rows_total, const int32_t* radii,
+                           const void* geom_ws, const ProjGrads& d, int32_t accumulate, const int32_t* nan_flag, const void* bin_ws,
+                           uint32_t R, ghr::ModelArgs* a, ghr::ModelGrads* mg)
+{
+    if (int rc = fill_model(m, a)) return rc;
+    if (rows_total < 0 || (long long)a->row0 + a->P > rows_total) return fail(GHR_E_INVALID, "segment exceeds rows_total");
+    if (!bin_ws && R > 0) return fail(GHR_E_INVALID, "ghr_model_backward_segment: bin_ws is NULL");
+    mg->adam.on = 0;
+    if (a->P == 0) return GHR_OK;
+    const bool need_act = a->mode == 0;
+    const bool cam_only = m->cam_only != 0;
+    if (cam_only && !m->cam_partial) return fail(GHR_E_INVALID, "ghr_model_backward_segment: cam_only without cam_partial");
+    if (m->cam_partial && (m->cam_slot0 < 0 || (long long)m->cam_slot0 + ghr_camera_slots(a->P) > m->cam_slots))
+        return fail(GHR_E_INVALID, "ghr_model_backward_segment: the segment's camera columns exceed cam_slots");
+    if (!radii || !geom_ws) return fail(GHR_E_INVALID, "ghr_model_backward_segment: NULL buffer");
+    const bool factored_sh = m->d_rgb != nullptr || sf != nullptr;
+    const bool sh_unstored = sh_grads_unstored(m, factored_sh, accumulate);
+    if (!cam_only && (!d.means2D || !d.xyz || !d.log_scales || !d.rotations || (!sh_unstored && !d.features_dc) ||
+        (need_act && (!d.opacity_logit || !d.label_logit || !d.orient_conf_log)) ||
+        (!sh_unstored && a->sh_coeffs > 1 && !d.features_rest)))
+        return fail(GHR_E_INVALID, "ghr_model_backward_segment: NULL buffer");
+    if (factored_sh && (cam_only || m->adam_fuse))
+        return fail(GHR_E_INVALID, "ghr_model_backward_segment: d_rgb with cam_only / adam_fuse");
+    if (!dens_all_or_none(m))
+        return fail(GHR_E_INVALID, "ghr_model_backward_segment: dens_grad_accum / dens_denom / dens_max_radii2D: all three or none");
+    if (m->adam_fuse) {
+        if (cam_only) return fail(GHR_E_INVALID, "ghr_adam_fuse: not with a cam_only segment");
+        if (int rc = fill_adam_fuse(*a, m->adam_fuse, accumulate, nan_flag, mg)) return rc;
+    }
+    return GHR_OK;
+}
+
 // sf != NULL (checked by check_shared): the projection backward in factored form into d_rgb_ws, then the per-strand fold into
-// d_features_dc [S,1,3] / d_features_rest [S,K-1,3]
+// d.features_dc [S,1,3] / d.features_rest [S,K-1,3]
+int run_backward_segment(ghr::ModelArgs& a, ghr::ModelGrads& mg, const ghr_model_args* m, const ghr_shared_features* sf,
+                         float* d_rgb_ws, void* stream, int32_t rows_total, const int32_t* radii, const void* geom_ws,
+                         const float* grad_scratch, const ProjGrads& d, int32_t accumulate, int32_t* nan_flag, uint32_t grad_rows,
+                         const void* bin_ws, uint32_t R)
+{
+    if (a.P == 0) return GHR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const bool cam_only = m->cam_only != 0;
+    const ghr_adam_fuse* af = m->adam_fuse;
+    // (of the image workspace only the instance count is read, and only where the densification statistics or the step's flag ask)
+    const ViewWs w = carve_view((size_t)rows_total, a.W, a.H, false, R, geom_ws, m->dens_img_ws, bin_ws);
+    // (rec: the gather unpacks the gradient lines with the pixel mean / conic / opacity k_project stored)
+    a.radii = const_cast<int*>(radii); a.rects = w.g.rects; a.rec = w.g.rec;
+    mg.inst_line = w.b.inst_line; mg.ginst = grad_scratch; mg.ginst_rows = grad_rows ? (grad_rows < R ? grad_rows : R) : R;
+    mg.d_means2D = d.means2D; mg.d_xyz = d.xyz; mg.d_log_scales = d.log_scales; mg.d_rotations = d.rotations;
+    mg.d_opacity_logit = d.opacity_logit; mg.d_label_logit = d.label_logit; mg.d_orient_conf_log = d.orient_conf_log;
+    mg.d_features_dc = d.features_dc; mg.d_features_rest = d.features_rest; mg.d_rgb = m->d_rgb;
+    if (sf) { mg.d_rgb = d_rgb_ws; mg.d_features_dc = mg.d_features_rest = nullptr; }
+    mg.d_dir3d = a.mode == 1 ? d.dir3d : nullptr;
+    mg.accumulate = accumulate; mg.nan_flag = cam_only ? nullptr : nan_flag;
+    mg.cam_partial = m->cam_partial; mg.cam_slot0 = (uint32_t)m->cam_slot0; mg.cam_stride = (uint32_t)m->cam_slots;
+    mg.cam_only = cam_only ? 1 : 0; mg.detach_means2D = m->detach_means2D != 0 ? 1 : 0;
+    mg.dens_grad_accum = m->dens_grad_accum; mg.dens_denom = m->dens_denom; mg.dens_max_radii = m->dens_max_radii2D;
+    // (steps with the fused optimizer update: EVERY view's backward checks its instance count and raises the step's flag)
+    const bool overflow_is_bad = m->dens_img_ws && (af || m->overflow_raises_flag);
+    mg.dens_count = (n_dens(m) == 3 || overflow_is_bad) ? w.im.R_dev : nullptr;  // (NULL without dens_img_ws)
+    mg.dens_cap = R; mg.overflow_is_bad = overflow_is_bad ? 1 : 0;
+    const dim3 grid((a.P + GHR_PBW_BLOCK - 1) / GHR_PBW_BLOCK), block(GHR_PBW_BLOCK);
+    if (sf) {
+        const ghr::SharedFeat k{sf->n_strands, sf->rows_per_strand, a.features_dc, a.features_rest};
+        const float *xyz = a.xyz, *campos = a.campos;
+        const int deg = a.sh_degree, K = a.sh_coeffs;
+        a.features_dc = a.xyz;  // (see forward_segment)
+        a.features_rest = nullptr;
+        if (mg.cam_partial) hipLaunchKernelGGL(ghr::k_shared_proj_bwd<true>, grid, block, 0, s, a, mg, k);
+        else hipLaunchKernelGGL(ghr::k_shared_proj_bwd<false>, grid, block, 0, s, a, mg, k);
+        if (int rc = ghr_shared_sh_fold(stream, sf, deg, K, xyz, campos, d_rgb_ws, d.features_dc, d.features_rest, nan_flag)) return rc;
+    } else if (af) {
+        if (mg.cam_partial) hipLaunchKernelGGL((ghr::k_project_bwd<true, true>), grid, block, 0, s, a, mg);
+        else hipLaunchKernelGGL((ghr::k_project_bwd<false, true>), grid, block, 0, s, a, mg);
+        // (a strand segment leaves the finish to the caller -- ghr_adam_fused_finish -- who first steps the groups whose
+        // gradients are still on their way through autograd and adds their non-finite mark to the step's flag)
+        if (a.mode == 0) adam_fused_finish(af, s);
+    } else if (mg.cam_partial) hipLaunchKernelGGL((ghr::k_project_bwd<true, false>), grid, block, 0, s, a, mg);
+    else hipLaunchKernelGGL((ghr::k_project_bwd<false, false>), grid, block, 0, s, a, mg);
+    return finish(s, m->debug);
+}
+
 int backward_segment(const ghr_model_args* m, const ghr_shared_features* sf, float* d_rgb_ws, void* stream, int32_t rows_total,
-                     const int32_t* radii, const void* geom_ws, const float* grad_scratch, float* d_means2D, float* d_xyz,
-                     float* d_log_scales, float* d_rotations, float* d_opacity_logit, float* d_label_logit,
-                     float* d_orient_conf_log, float* d_features_dc, float* d_features_rest, float* d_dir3d,
-                     int32_t accumulate, int32_t* nan_flag, uint32_t grad_rows, const void* bin_ws, uint32_t R);
+                     const int32_t* radii, const void* geom_ws, const float* grad_scratch, const ProjGrads& d, int32_t accumulate,
+                     int32_t* nan_flag, uint32_t grad_rows, const void* bin_ws, uint32_t R)
+{
+    ghr::ModelArgs a; ghr::ModelGrads mg;
+    if (int rc = check_backward_segment(m, sf, rows_total, radii, geom_ws, d, accumulate, nan_flag, bin_ws, R, &a, &mg)) return rc;
+    return run_backward_segment(a, mg, m, sf, d_rgb_ws, stream, rows_total, radii, geom_ws, grad_scratch, d, accumulate, nan_flag,
+                                grad_rows, bin_ws, R);
+}
 }  // namespace
 
 int ghr_model_backward_segment(void* stream, const ghr_model_args* m, int32_t rows_total, const int32_t* radii,
@@ -647,9 +802,10 @@ int ghr_model_backward_segment(void* stream, const ghr_model_args* m, int32_t ro
                                int32_t accumulate, int32_t* nan_flag, uint32_t grad_rows, const void* bin_ws,
                                uint32_t R)
 {
-    return backward_segment(m, nullptr, nullptr, stream, rows_total, radii, geom_ws, grad_scratch, d_means2D, d_xyz, d_log_scales,
-                            d_rotations, d_opacity_logit, d_label_logit, d_orient_conf_log, d_features_dc, d_features_rest,
-                            d_dir3d, accumulate, nan_flag, grad_rows, bin_ws, R);
+    const ProjGrads d{d_means2D, d_xyz, d_log_scales, d_rotations, d_opacity_logit, d_label_logit, d_orient_conf_log,
+                      d_features_dc, d_features_rest, d_dir3d};
+    return backward_segment(m, nullptr, nullptr, stream, rows_total, radii, geom_ws, grad_scratch, d, accumulate, nan_flag,
+                            grad_rows, bin_ws, R);
 }
 
 int ghr_model_backward_segment_shared(void* stream, const ghr_model_args* m, const ghr_shared_features* sf, int32_t rows_total,
@@ -664,137 +820,18 @@ int ghr_model_backward_segment_shared(void* stream, const ghr_model_args* m, con
     if (m->P > 0 && !d_rgb_ws) return fail(GHR_E_INVALID, "%s: d_rgb_ws is NULL", who);
     if (m->P > 0 && !d_features_dc) return fail(GHR_E_INVALID, "%s: d_features_dc is NULL", who);
     if (m->P > 0 && m->sh_coeffs > 1 && !d_features_rest) return fail(GHR_E_INVALID, "%s: d_features_rest is NULL", who);
-    return backward_segment(m, sf, d_rgb_ws, stream, rows_total, radii, geom_ws, grad_scratch, d_means2D, d_xyz, d_log_scales,
-                            d_rotations, d_opacity_logit, d_label_logit, d_orient_conf_log, d_features_dc, d_features_rest,
-                            d_dir3d, 0, nan_flag, grad_rows, bin_ws, R);
+    const ProjGrads d{d_means2D, d_xyz, d_log_scales, d_rotations, d_opacity_logit, d_label_logit, d_orient_conf_log,
+                      d_features_dc, d_features_rest, d_dir3d};
+    return backward_segment(m, sf, d_rgb_ws, stream, rows_total, radii, geom_ws, grad_scratch, d, 0, nan_flag, grad_rows, bin_ws, R);
 }
-
-int ghr_shared_sh_fold(void* stream, const ghr_shared_features* sf, int32_t sh_degree, int32_t sh_coeffs, const float* xyz,
-                       const float* campos, const float* d_rgb, float* d_features_dc, float* d_features_rest, int32_t* nan_flag)
-{
-    static const char* who = "ghr_shared_sh_fold";
-    if (!sf) return fail(GHR_E_INVALID, "%s: ghr_shared_features is NULL", who);
-    if (sf->rows_per_strand < 1 || sf->n_strands < 0 || (long long)sf->n_strands * sf->rows_per_strand > 0x7fffffffLL)
-        return fail(GHR_E_INVALID, "%s: bad n_strands / rows_per_strand", who);
-    if (sh_coeffs != 1 && sh_coeffs != 4 && sh_coeffs != 9 && sh_coeffs != 16)
-        return fail(GHR_E_INVALID, "%s: sh_coeffs must be 1, 4, 9 or 16", who);
-    if (sh_degree < 0 || (sh_degree + 1) * (sh_degree + 1) > sh_coeffs) return fail(GHR_E_INVALID, "%s: bad sh_degree", who);
-    if (sf->n_strands == 0) return GHR_OK;
-    if (!xyz || !campos || !d_rgb || !d_features_dc || (sh_coeffs > 1 && !d_features_rest))
-        return fail(GHR_E_INVALID, "%s: NULL buffer", who);
-    ghr::SharedFoldArgs fa;
-    fa.S = sf->n_strands; fa.n_seg = sf->rows_per_strand; fa.sh_degree = sh_degree; fa.sh_coeffs = sh_coeffs;
-    fa.xyz = xyz; fa.campos = campos; fa.d_rgb = d_rgb; fa.d_dc = d_features_dc; fa.d_rest = d_features_rest;
-    fa.nan_flag = nan_flag;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(ghr::k_shared_sh_fold, dim3(fa.S), dim3(GHR_PBW_BLOCK), 0, s, fa);
-    return finish(s, 0);
-}
-
-namespace {
-int backward_segment(const ghr_model_args* m, const ghr_shared_features* sf, float* d_rgb_ws, void* stream, int32_t rows_total,
-                     const int32_t* radii, const void* geom_ws, const float* grad_scratch, float* d_means2D, float* d_xyz,
-                     float* d_log_scales, float* d_rotations, float* d_opacity_logit, float* d_label_logit,
-                     float* d_orient_conf_log, float* d_features_dc, float* d_features_rest, float* d_dir3d,
-                     int32_t accumulate, int32_t* nan_flag, uint32_t grad_rows, const void* bin_ws, uint32_t R)
-{
-    ghr::ModelArgs a;
-    if (int rc = fill_model(m, &a)) return rc;
-    if (rows_total < 0 || (long long)a.row0 + a.P > rows_total) return fail(GHR_E_INVALID, "segment exceeds rows_total");
-    if (!bin_ws && R > 0) return fail(GHR_E_INVALID, "ghr_model_backward_segment: bin_ws is NULL");
-    hipStream_t s = (hipStream_t)stream;
-    if (a.P == 0) return GHR_OK;
-    const bool need_act = a.mode == 0;
-    const bool cam_only = m->cam_only != 0;
-    if (cam_only && !m->cam_partial) return fail(GHR_E_INVALID, "ghr_model_backward_segment: cam_only without cam_partial");
-    if (m->cam_partial && (m->cam_slot0 < 0 || (long long)m->cam_slot0 + ghr_camera_slots(a.P) > m->cam_slots))
-        return fail(GHR_E_INVALID, "ghr_model_backward_segment: the segment's camera columns exceed cam_slots");
-    if (!radii || !geom_ws)
-        return fail(GHR_E_INVALID, "ghr_model_backward_segment: NULL buffer");
-    const bool factored_sh = m->d_rgb != nullptr || sf != nullptr;  // ABI 19: the SH gradients leave as d_rgb, their own buffers may be NULL
-    // (the SH gradient buffers may be NULL when nothing is stored there: the factored form, or the update carried by this
-    // call -- ghr_adam_fuse -- without earlier views' gradients to add)
-    const bool sh_unstored = factored_sh || (m->adam_fuse != nullptr && !accumulate);
-    if (!cam_only && (!d_means2D || !d_xyz || !d_log_scales || !d_rotations || (!sh_unstored && !d_features_dc) ||
-        (need_act && (!d_opacity_logit || !d_label_logit || !d_orient_conf_log)) ||
-        (!sh_unstored && a.sh_coeffs > 1 && !d_features_rest)))
-        return fail(GHR_E_INVALID, "ghr_model_backward_segment: NULL buffer");
-    if (factored_sh && (cam_only || m->adam_fuse))
-        return fail(GHR_E_INVALID, "ghr_model_backward_segment: d_rgb with cam_only / adam_fuse");
-    Geom g;
-    carve_geom(align_base(geom_ws), (size_t)rows_total, false, &g);
-    a.radii = const_cast<int*>(radii);
-    a.rects = g.rects;
-    a.rec = g.rec;  // the gather unpacks the gradient lines with the pixel mean / conic / opacity k_project stored
-    Bin b;
-    carve_bin(bin_ws ? align_base(bin_ws) : nullptr, (size_t)R, (size_t)a.gx * a.gy, &b);
-    ghr::ModelGrads mg;
-    mg.inst_line = b.inst_line;
-    mg.ginst = grad_scratch; mg.ginst_rows = grad_rows ? (grad_rows < R ? grad_rows : R) : R; mg.d_means2D = d_means2D; mg.d_xyz = d_xyz; mg.d_log_scales = d_log_scales;
-    mg.d_rotations = d_rotations; mg.d_opacity_logit = d_opacity_logit; mg.d_label_logit = d_label_logit;
-    mg.d_orient_conf_log = d_orient_conf_log; mg.d_features_dc = d_features_dc; mg.d_features_rest = d_features_rest;
-    mg.d_rgb = m->d_rgb;
-    if (sf) { mg.d_rgb = d_rgb_ws; mg.d_features_dc = mg.d_features_rest = nullptr; }
-    mg.d_dir3d = a.mode == 1 ? d_dir3d : nullptr;
-    mg.accumulate = accumulate; mg.nan_flag = cam_only ? nullptr : nan_flag;
-    mg.cam_partial = m->cam_partial; mg.cam_slot0 = (uint32_t)m->cam_slot0; mg.cam_stride = (uint32_t)m->cam_slots;
-    mg.cam_only = cam_only ? 1 : 0; mg.detach_means2D = m->detach_means2D != 0 ? 1 : 0;
-    const int n_dens = (m->dens_grad_accum != nullptr) + (m->dens_denom != nullptr) + (m->dens_max_radii2D != nullptr);
-    if (n_dens != 0 && n_dens != 3)
-        return fail(GHR_E_INVALID, "ghr_model_backward_segment: dens_grad_accum / dens_denom / dens_max_radii2D: all three or none");
-    mg.dens_grad_accum = m->dens_grad_accum; mg.dens_denom = m->dens_denom; mg.dens_max_radii = m->dens_max_radii2D;
-    mg.dens_count = nullptr; mg.dens_cap = R;
-    if (n_dens == 3 && m->dens_img_ws) {
-        Img im;
-        carve_img(align_base(m->dens_img_ws), (size_t)a.W * a.H, (size_t)a.gx * a.gy, &im);
-        mg.dens_count = im.R_dev;
-    }
-    mg.overflow_is_bad = 0;
-    mg.adam.on = 0;
-    const ghr_adam_fuse* af = m->adam_fuse;
-    if (af) {
-        if (cam_only) return fail(GHR_E_INVALID, "ghr_adam_fuse: not with a cam_only segment");
-        if (int rc = fill_adam_fuse(a, af, accumulate, nan_flag, &mg)) return rc;
-    }
-    if (m->dens_img_ws && (af || m->overflow_raises_flag)) {
-        // (steps with the fused optimizer update: EVERY view's backward checks its instance count and raises the step's flag)
-        Img im;
-        carve_img(align_base(m->dens_img_ws), (size_t)a.W * a.H, (size_t)a.gx * a.gy, &im);
-        mg.dens_count = im.R_dev; mg.dens_cap = R; mg.overflow_is_bad = 1;
-    }
-    const dim3 grid((a.P + GHR_PBW_BLOCK - 1) / GHR_PBW_BLOCK), block(GHR_PBW_BLOCK);
-    if (sf) {
-        const ghr::SharedFeat k{sf->n_strands, sf->rows_per_strand, a.features_dc, a.features_rest};
-        const float *xyz = a.xyz, *campos = a.campos;
-        const int deg = a.sh_degree, K = a.sh_coeffs;
-        a.features_dc = a.xyz;  // (see forward_segment)
-        a.features_rest = nullptr;
-        if (mg.cam_partial) hipLaunchKernelGGL(ghr::k_shared_proj_bwd<true>, grid, block, 0, s, a, mg, k);
-        else hipLaunchKernelGGL(ghr::k_shared_proj_bwd<false>, grid, block, 0, s, a, mg, k);
-        if (int rc = ghr_shared_sh_fold(stream, sf, deg, K, xyz, campos, d_rgb_ws, d_features_dc, d_features_rest, nan_flag)) return rc;
-    } else if (af) {
-        if (mg.cam_partial) hipLaunchKernelGGL((ghr::k_project_bwd<true, true>), grid, block, 0, s, a, mg);
-        else hipLaunchKernelGGL((ghr::k_project_bwd<false, true>), grid, block, 0, s, a, mg);
-        // (a strand segment leaves the finish to the caller -- ghr_adam_fused_finish -- who first steps the groups whose
-        // gradients are still on their way through autograd and adds their non-finite mark to the step's flag)
-        if (a.mode == 0)
-            hipLaunchKernelGGL(ghr::k_adam_fused_finish, dim3(1024), dim3(256), 0, s, (long long)af->n, af->p_in, af->m_in,
-                               af->v_in, af->p_out, af->m_out, af->v_out, af->state, (const int*)af->flag, af->flag_next);
-    } else if (mg.cam_partial) hipLaunchKernelGGL((ghr::k_project_bwd<true, false>), grid, block, 0, s, a, mg);
-    else hipLaunchKernelGGL((ghr::k_project_bwd<false, false>), grid, block, 0, s, a, mg);
-    return finish(s, m->debug);
-}
-}  // namespace
 
 int ghr_adam_fused_finish(void* stream, const ghr_adam_fuse* af)
 {
     if (!af || af->n < 0 || !af->p_in || !af->m_in || !af->v_in || !af->p_out || !af->m_out || !af->v_out || !af->state ||
         !af->flag || !af->flag_next)
         return fail(GHR_E_INVALID, "ghr_adam_fused_finish: bad ghr_adam_fuse");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(ghr::k_adam_fused_finish, dim3(1024), dim3(256), 0, s, (long long)af->n, af->p_in, af->m_in, af->v_in,
-                       af->p_out, af->m_out, af->v_out, af->state, (const int*)af->flag, af->flag_next);
-    return finish(s, 0);
+    adam_fused_finish(af, (hipStream_t)stream);
+    return finish((hipStream_t)stream, 0);
 }
 
 int32_t ghr_camera_slots(int32_t P) { return P > 0 ? (P + GHR_PBW_BLOCK - 1) / GHR_PBW_BLOCK : 0; }
@@ -814,19 +851,29 @@ int ghr_camera_grad_fold(void* stream, const float* cam_partial, int32_t cam_slo
     return finish(s, 0);
 }
 
+static int check_sh_grad_from_views(int32_t P, int32_t sh_degree, int32_t sh_coeffs, const float* xyz, int32_t n_views,
+                                    const float* campos, int64_t campos_stride, const float* g_views, int64_t view_stride,
+                                    const float* d_features_dc, const float* d_features_rest, const int32_t* nan_flag, int64_t flag_offset)
+{
+    if (!sh_views_sizes_ok(P, sh_degree, sh_coeffs, n_views, view_stride, campos_stride) ||
+        (nan_flag != nullptr && (flag_offset < 0 || (n_views > 1 && flag_offset >= view_stride))))
+        return fail(GHR_E_INVALID, "ghr_sh_grad_from_views: bad sizes");
+    if (P == 0) return GHR_OK;
+    if (!xyz || !d_features_dc || (sh_coeffs > 1 && !d_features_rest) || (n_views > 0 && (!campos || !g_views)) ||
+        sh_views_overlap(P, n_views, view_stride))
+        return fail(GHR_E_INVALID, "ghr_sh_grad_from_views: NULL buffer / overlapping views");
+    return GHR_OK;
+}
+
 int ghr_sh_grad_from_views(void* stream, int32_t P, int32_t sh_degree, int32_t sh_coeffs, const float* xyz, int32_t n_views,
                            const float* campos, int64_t campos_stride, const float* g_views, int64_t view_stride,
                            float* d_features_dc, float* d_features_rest, int32_t accumulate, int32_t* nan_flag,
                            int64_t flag_offset)
 {
-    if (P < 0 || n_views < 0 || sh_degree < 0 || sh_degree > 3 || view_stride < 0 || campos_stride < 0 ||
-        (nan_flag != nullptr && (flag_offset < 0 || (n_views > 1 && flag_offset >= view_stride))) ||
-        !(sh_coeffs == 1 || sh_coeffs == 4 || sh_coeffs == 9 || sh_coeffs == 16) || (sh_degree + 1) * (sh_degree + 1) > sh_coeffs)
-        return fail(GHR_E_INVALID, "ghr_sh_grad_from_views: bad sizes");
+    if (int rc = check_sh_grad_from_views(P, sh_degree, sh_coeffs, xyz, n_views, campos, campos_stride, g_views, view_stride,
+                                          d_features_dc, d_features_rest, nan_flag, flag_offset))
+        return rc;
     if (P == 0) return GHR_OK;
-    if (!xyz || !d_features_dc || (sh_coeffs > 1 && !d_features_rest) || (n_views > 0 && (!campos || !g_views)) ||
-        (n_views > 1 && view_stride < 3 * (int64_t)P))
-        return fail(GHR_E_INVALID, "ghr_sh_grad_from_views: NULL buffer / overlapping views");
     hipStream_t s = (hipStream_t)stream;
     ghr::ShViewsArgs a;
     a.P = P; a.sh_degree = sh_degree; a.sh_coeffs = sh_coeffs; a.n_views = n_views; a.xyz = xyz; a.campos = campos;
@@ -896,61 +943,6 @@ int ghr_model_backward(void* stream, const ghr_model_args* m, uint32_t R, const 
                                       d_features_rest, nullptr, accumulate, nan_flag, R, bin_ws, R);
 }
 
-namespace ghr {
-// One 1024-thread workgroup folds the 5 x n_slots partial sums the forward kernel's workgroups stored (ghr_loss.h; laid out
-// [term][slot]): thread t takes the slots t, t + 1024, ... of every term (all of a round's loads in flight together), a DPP
-// sum inside each wave, and one thread per term adds the sixteen wave totals in double -- a fixed order, so the loss value
-// does not depend on how the forward kernel was scheduled.  (Built for latency: the kernel is a 5-us stop between the loss
-// forward and backward passes; a first form with double-precision butterflies took 12-17 us.)
-__global__ void __launch_bounds__(1024) k_loss_finalize(const float* slots, uint32_t n_slots, float w_l1, float w_ssim,
-                                                        float w_mask, float w_orient, float n_pix, float* aux, float* out)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    __shared__ float s_part[GHR_LOSS_TERMS][16];
-    __shared__ double s_tot[GHR_LOSS_TERMS];
-    float s[GHR_LOSS_TERMS] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    for (uint32_t base = 0; base < n_slots; base += 8u * 1024u) {
-        float v[GHR_LOSS_TERMS][8];
-#pragma unroll
-        for (int k = 0; k < GHR_LOSS_TERMS; k++)
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const uint32_t i = base + 1024u * u + threadIdx.x;
-                v[k][u] = i < n_slots ? slots[(size_t)k * n_slots + i] : 0.f;
-            }
-#pragma unroll
-        for (int k = 0; k < GHR_LOSS_TERMS; k++)
-            s[k] += ((v[k][0] + v[k][1]) + (v[k][2] + v[k][3])) + ((v[k][4] + v[k][5]) + (v[k][6] + v[k][7]));
-    }
-#pragma unroll
-    for (int k = 0; k < GHR_LOSS_TERMS; k++) {
-        const float w = wave_sum(s[k]);
-        if ((threadIdx.x & 63) == 0) s_part[k][threadIdx.x >> 6] = w;
-    }
-    __syncthreads();
-    if (threadIdx.x < GHR_LOSS_TERMS) {
-        double t = 0;
-#pragma unroll
-        for (int w = 0; w < 16; w++) t += (double)s_part[threadIdx.x][w];
-        s_tot[threadIdx.x] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double s0 = s_tot[0], s1 = s_tot[1], s2 = s_tot[2], s3 = s_tot[3], s4 = s_tot[4];
-        float lo = 0.f, bad = 0.f;
-        if (w_orient != 0.f) {
-            lo = (float)(s3 / s4);
-            if (lo != lo) { lo = 0.f; bad = 1.f; }  // train_gaussians.py:134: a NaN orientation loss is dropped
-        }
-        aux[0] = (float)s4;
-        aux[1] = bad;
-        out[0] = (float)(w_l1 * (s0 / (3.0 * n_pix)) + w_ssim * (1.0 - s1 / (3.0 * n_pix)) + w_mask * (s2 / (2.0 * n_pix))) +
-                 w_orient * lo;
-    }
-#endif
-}
-}  // namespace ghr
-
 #ifndef GHR_ADAM_BLOCKS
 #define GHR_ADAM_BLOCKS 65536
 #endif
@@ -988,13 +980,19 @@ size_t ghr_loss_sums_floats(int32_t W, int32_t H)
     return GHR_LOSS_AUX + GHR_LOSS_TERMS * n;
 }
 
-int ghr_loss_forward(void* stream, const ghr_loss_args* l, float* maps, float* sums, float* loss_out)
+static int check_loss_forward(const ghr_loss_args* l, const float* maps, const float* sums, const float* loss_out)
 {
     if (!l || l->W <= 0 || l->H <= 0 || !l->image || !l->mask || !l->gt_image || !l->gt_mask || !maps || !sums || !loss_out)
         return fail(GHR_E_INVALID, "ghr_loss_forward: bad args");
-    const bool orient = l->w_orient != 0.f;
-    if (orient && (!l->dir2d || !l->orient_conf || !l->gt_orient_angle || !l->gt_orient_conf))
+    if (l->w_orient != 0.f && (!l->dir2d || !l->orient_conf || !l->gt_orient_angle || !l->gt_orient_conf))
         return fail(GHR_E_INVALID, "ghr_loss_forward: w_orient != 0 needs dir2d / orient_conf / gt_orient_angle / gt_orient_conf");
+    return GHR_OK;
+}
+
+int ghr_loss_forward(void* stream, const ghr_loss_args* l, float* maps, float* sums, float* loss_out)
+{
+    if (int rc = check_loss_forward(l, maps, sums, loss_out)) return rc;
+    const bool orient = l->w_orient != 0.f;
     hipStream_t s = (hipStream_t)stream;
     // sums = {aux[GHR_LOSS_AUX] | one slot of five partial sums per workgroup of the forward kernel}: nothing to zero
     ghr::LossArgs a{l->W, l->H, l->image, l->mask, orient ? l->dir2d : nullptr, l->orient_conf, l->gt_image, l->gt_mask,
@@ -1030,16 +1028,23 @@ int ghr_loss_gt_stats(void* stream, const ghr_loss_args* l, float* stats_out)
     return finish(s, 0);
 }
 
-int ghr_loss_backward(void* stream, const ghr_loss_args* l, const float* maps, const float* sums,
-                      const float* grad_loss, float* d_image, float* d_mask, float* d_dir2d, float* d_orient_conf,
-                      float* zero_plane_a, float* zero_plane_b)
+static int check_loss_backward(const ghr_loss_args* l, const float* maps, const float* sums, const float* d_image,
+                               const float* d_mask, const float* d_dir2d, const float* d_orient_conf)
 {
     if (!l || l->W <= 0 || l->H <= 0 || !l->image || !l->mask || !l->gt_image || !l->gt_mask || !maps || !sums ||
         !d_image || !d_mask || ((d_dir2d == nullptr) != (d_orient_conf == nullptr)))
         return fail(GHR_E_INVALID, "ghr_loss_backward: bad args");
-    const bool orient = l->w_orient != 0.f;
-    if (orient && (!l->dir2d || !l->orient_conf || !l->gt_orient_angle || !l->gt_orient_conf || !d_dir2d))
+    if (l->w_orient != 0.f && (!l->dir2d || !l->orient_conf || !l->gt_orient_angle || !l->gt_orient_conf || !d_dir2d))
         return fail(GHR_E_INVALID, "ghr_loss_backward: w_orient != 0 needs the orientation inputs and d_dir2d / d_orient_conf");
+    return GHR_OK;
+}
+
+int ghr_loss_backward(void* stream, const ghr_loss_args* l, const float* maps, const float* sums,
+                      const float* grad_loss, float* d_image, float* d_mask, float* d_dir2d, float* d_orient_conf,
+                      float* zero_plane_a, float* zero_plane_b)
+{
+    if (int rc = check_loss_backward(l, maps, sums, d_image, d_mask, d_dir2d, d_orient_conf)) return rc;
+    const bool orient = l->w_orient != 0.f;
     hipStream_t s = (hipStream_t)stream;
     ghr::LossBwdArgs a{l->W, l->H, l->image, l->mask, orient ? l->dir2d : nullptr, l->orient_conf, l->gt_image,
                        l->gt_mask, l->gt_orient_angle, l->gt_orient_conf, l->unmasked_colours ? 0 : 1, maps,
@@ -1058,11 +1063,11 @@ int vs_bad(const char* what) { return fail(GHR_E_INVALID, "ghr_view_step: %s", w
 #define GHR_VS_PTR(p, name) \
     do { if (!(p)) return vs_bad(name " is NULL"); } while (0)
 
-// Everything the six calls below would refuse, asked up front (they check as they go: a struct that only the last of them
-// refuses would otherwise leave five calls' kernels in the stream).  Launches nothing, touches no device memory.
-int check_view_step(const ghr_view_step_args* v)
+// Everything ghr_view_step refuses, asked before the first launch.  First what the call itself does not cover, and the rules
+// of the six calls in its own words: a NULL buffer by the name of its field, the others with the predicate their owner asks
+// too.  Then the six calls' own checks, in call order: what they refuse is refused here, whether or not it has words above.
+int check_view_step(const ghr_view_step_args* v, const ghr_view_args* va, const ghr_loss_args* lr, const ProjGrads& pg)
 {
-    if (!v) return vs_bad("the argument struct is NULL");
     const ghr_model_args* m = &v->model;
     if (m->P <= 0) return vs_bad("model.P must be > 0");
     if (m->W <= 0 || m->H <= 0) return vs_bad("model.W / model.H must be > 0");
@@ -1073,9 +1078,8 @@ int check_view_step(const ghr_view_step_args* v)
     if (m->debug != 0) return vs_bad("model.debug must be 0 (the call never waits for the device)");
     if (m->cam_partial || m->cam_only || m->detach_means2D) return vs_bad("model.cam_partial / cam_only / detach_means2D: camera gradients are not part of the call");
     if (m->fovx_dev || m->fovy_dev) return vs_bad("model.fovx_dev / fovy_dev must be NULL");
-    if (m->sh_degree < 0 || m->sh_degree > 3) return vs_bad("model.sh_degree must be 0 .. 3");
-    if ((m->sh_coeffs != 1 && m->sh_coeffs != 4 && m->sh_coeffs != 9 && m->sh_coeffs != 16) ||
-        m->sh_coeffs < (m->sh_degree + 1) * (m->sh_degree + 1))
+    if (!sh_degree_ok(m->sh_degree)) return vs_bad("model.sh_degree must be 0 .. 3");
+    if (!sh_coeffs_ok(m->sh_coeffs) || !sh_covers(m->sh_degree, m->sh_coeffs))
         return vs_bad("model.sh_coeffs must be (max_sh_degree + 1)^2 and cover model.sh_degree");
     GHR_VS_PTR(m->xyz, "model.xyz"); GHR_VS_PTR(m->log_scales, "model.log_scales"); GHR_VS_PTR(m->rotations, "model.rotations");
     GHR_VS_PTR(m->opacity_logit, "model.opacity_logit"); GHR_VS_PTR(m->label_logit, "model.label_logit");
@@ -1085,11 +1089,8 @@ int check_view_step(const ghr_view_step_args* v)
     GHR_VS_PTR(m->campos, "model.campos"); GHR_VS_PTR(m->background, "model.background");
     GHR_VS_PTR(v->R_host, "R_host"); GHR_VS_PTR(v->geom_ws, "geom_ws"); GHR_VS_PTR(v->img_ws, "img_ws");
     if (v->R > 0) { GHR_VS_PTR(v->bin_ws, "bin_ws"); GHR_VS_PTR(v->grad_scratch, "grad_scratch"); }
-    const size_t T = (size_t)grid_x(m->W) * grid_x(m->H);
-    if (ghr::mask_groups((size_t)v->R, T) * 128 >= ((size_t)1 << 32))
-        return vs_bad("R: too many instances for the 32-bit offsets of the cell masks");
-    if (g_deterministic && !ghr::b3_fits((size_t)m->P, v->R, (size_t)m->W, (size_t)m->H))
-        return vs_bad("model.P / R: " GHR_E_DETERMINISTIC_MSG);
+    if (!cell_masks_fit(v->R, m->W, m->H)) return vs_bad("R: too many instances for the 32-bit offsets of the cell masks");
+    if (ordered_walk_refused((size_t)m->P, v->R, m->W, m->H)) return vs_bad("model.P / R: " GHR_E_DETERMINISTIC_MSG);
     GHR_VS_PTR(v->radii, "radii"); GHR_VS_PTR(v->render, "render");
     const ghr_loss_args* l = &v->loss;
     if (l->W != m->W || l->H != m->H) return vs_bad("loss.W / loss.H differ from model.W / model.H");
@@ -1101,56 +1102,66 @@ int check_view_step(const ghr_view_step_args* v)
     GHR_VS_PTR(v->d_label_logit, "d_label_logit"); GHR_VS_PTR(v->d_orient_conf_log, "d_orient_conf_log");
     const ghr_adam_fuse* af = m->adam_fuse;
     if (m->d_rgb && af) return vs_bad("model.d_rgb with model.adam_fuse (the view that carries the update stores no table)");
-    // (the SH gradient buffers may be NULL when nothing is stored there: ghr_model_backward_segment)
-    const bool sh_unstored = m->d_rgb != nullptr || (af != nullptr && !v->accumulate);
-    if (!sh_unstored && (!v->d_features_dc || (m->sh_coeffs > 1 && !v->d_features_rest)))
+    if (!sh_grads_unstored(m, m->d_rgb != nullptr, v->accumulate) && (!v->d_features_dc || (m->sh_coeffs > 1 && !v->d_features_rest)))
         return vs_bad(af ? "d_features_dc / d_features_rest is NULL: model.adam_fuse with accumulate != 0 adds the earlier views' "
                            "gradients from there"
                          : "d_features_dc / d_features_rest is NULL (without model.d_rgb)");
-    const int n_dens = (m->dens_grad_accum != nullptr) + (m->dens_denom != nullptr) + (m->dens_max_radii2D != nullptr);
-    if (n_dens != 0 && n_dens != 3) return vs_bad("model.dens_grad_accum / dens_denom / dens_max_radii2D: all three or none");
+    if (!dens_all_or_none(m)) return vs_bad("model.dens_grad_accum / dens_denom / dens_max_radii2D: all three or none");
     if (m->dens_img_ws && m->dens_img_ws != v->img_ws) return vs_bad("model.dens_img_ws must be img_ws");
     if (m->overflow_raises_flag && (!m->dens_img_ws || !v->nan_flag))
         return vs_bad("model.overflow_raises_flag needs model.dens_img_ws and nan_flag");
-    ghr::ModelArgs a;
-    if (int rc = fill_model(m, &a)) return rc;
-    if (af) {
-        if (!m->dens_img_ws) return vs_bad("model.adam_fuse needs model.dens_img_ws (an overflowed view must not reach the parameters)");
-        ghr::ModelGrads mg;
-        if (int rc = fill_adam_fuse(a, af, v->accumulate, v->nan_flag, &mg)) return rc;
-    }
-    if (const ghr_sh_fold_args* f = v->sh_fold) {
+    if (af && !m->dens_img_ws) return vs_bad("model.adam_fuse needs model.dens_img_ws (an overflowed view must not reach the parameters)");
+    const ghr_sh_fold_args* f = v->sh_fold;
+    if (f) {
         if (f->P != m->P || f->sh_coeffs != m->sh_coeffs) return vs_bad("sh_fold.P / sh_fold.sh_coeffs differ from the model's");
-        if (f->n_views < 0 || f->sh_degree < 0 || (f->sh_degree + 1) * (f->sh_degree + 1) > f->sh_coeffs || f->view_stride < 0 ||
-            f->campos_stride < 0 || (f->n_views > 1 && f->view_stride < 3 * (int64_t)f->P))
+        if (!sh_views_sizes_ok(f->P, f->sh_degree, f->sh_coeffs, f->n_views, f->view_stride, f->campos_stride) ||
+            sh_views_overlap(f->P, f->n_views, f->view_stride))
             return vs_bad("sh_fold: bad sizes / overlapping views");
         GHR_VS_PTR(f->xyz, "sh_fold.xyz"); GHR_VS_PTR(f->d_features_dc, "sh_fold.d_features_dc");
         if (f->sh_coeffs > 1) GHR_VS_PTR(f->d_features_rest, "sh_fold.d_features_rest");
         if (f->n_views > 0) { GHR_VS_PTR(f->campos, "sh_fold.campos"); GHR_VS_PTR(f->g_views, "sh_fold.g_views"); }
     }
-    return GHR_OK;
+    const float* d = v->d_pix;
+    const size_t n = (size_t)m->W * m->H;
+    ghr::ModelArgs a; ghr::ModelGrads mg;
+    if (int rc = check_model_forward_stage1(m, v->geom_ws, v->img_ws, v->radii, v->R_host, &a)) return rc;
+    if (int rc = check_forward_stage2(va, v->R, v->geom_ws, v->img_ws, v->bin_ws, v->render)) return rc;
+    if (int rc = check_loss_forward(lr, v->maps, v->sums, v->loss_out)) return rc;
+    if (int rc = check_loss_backward(lr, v->maps, v->sums, d, d + 3 * n, d + 5 * n, d + 8 * n)) return rc;
+    if (int rc = check_render_backward(m->P, m->W, m->H, v->R, m->background, v->geom_ws, v->img_ws, v->bin_ws, d, v->grad_scratch))
+        return rc;
+    if (f)
+        if (int rc = check_sh_grad_from_views(f->P, f->sh_degree, f->sh_coeffs, f->xyz, f->n_views, f->campos, f->campos_stride,
+                                              f->g_views, f->view_stride, f->d_features_dc, f->d_features_rest, nullptr, 0))
+            return rc;
+    return check_backward_segment(m, nullptr, m->P, v->radii, v->geom_ws, pg, v->accumulate, v->nan_flag, v->bin_ws, v->R, &a, &mg);
 }
 }  // namespace
 
 int ghr_view_step(void* stream, const ghr_view_step_args* v)
 {
-    if (int rc = check_view_step(v)) return rc;
-    hipStream_t s = (hipStream_t)stream;
+    if (!v) return vs_bad("the argument struct is NULL");
     const ghr_model_args* m = &v->model;
     const size_t n = (size_t)m->W * m->H;
-    if (int rc = ghr_model_forward_stage1(stream, m, v->geom_ws, v->img_ws, v->radii, v->means2D_out, v->R_host)) return rc;
-    if (v->count_event) GHR_HIP(hipEventRecord((hipEvent_t)v->count_event, s));
+    // what the six calls take that is no field of `v`: stage 2's view struct, the loss struct over the rendered planes of the
+    // packed output (include/ghr.h, ghr_loss_args), the gradient pointers
     ghr_view_args va;
     std::memset(&va, 0, sizeof(va));
     va.P = m->P; va.W = m->W; va.H = m->H; va.C = GHR_NUM_CHANNELS; va.background = m->background;
+    ghr_loss_args l = v->loss;
+    l.image = v->render; l.mask = v->render + 3 * n; l.dir2d = v->render + 5 * n; l.orient_conf = v->render + 8 * n;
+    const ProjGrads pg{v->d_means2D, v->d_xyz, v->d_log_scales, v->d_rotations, v->d_opacity_logit, v->d_label_logit,
+                       v->d_orient_conf_log, v->d_features_dc, v->d_features_rest, nullptr};
+    if (int rc = check_view_step(v, &va, &l, pg)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = ghr_model_forward_stage1(stream, m, v->geom_ws, v->img_ws, v->radii, v->means2D_out, v->R_host)) return rc;
+    if (v->count_event) GHR_HIP(hipEventRecord((hipEvent_t)v->count_event, s));
     if (int rc = ghr_forward_stage2(stream, &va, v->R, v->geom_ws, v->img_ws, v->bin_ws, v->render,
                                     v->prezero ? v->grad_scratch : nullptr))
         return rc;
-    ghr_loss_args l = v->loss;  // the rendered planes of the packed output (include/ghr.h, ghr_loss_args)
-    l.image = v->render; l.mask = v->render + 3 * n; l.dir2d = v->render + 5 * n; l.orient_conf = v->render + 8 * n;
     if (int rc = ghr_loss_forward(stream, &l, v->maps, v->sums, v->loss_out)) return rc;
     l.gt_stats = nullptr;  // (the backward pass reads no window moments)
-    float* d = v->d_pix;   // channels 7 and 9 carry no loss term: zero-filled by the loss backward
+    float* d = v->d_pix;     // channels 7 and 9 carry no loss term: zero-filled by the loss backward
     if (int rc = ghr_loss_backward(stream, &l, v->maps, v->sums, v->grad_loss, d, d + 3 * n, d + 5 * n, d + 8 * n, d + 7 * n,
                                    d + 9 * n))
         return rc;
@@ -1163,10 +1174,8 @@ int ghr_view_step(void* stream, const ghr_view_step_args* v)
                                             f->g_views, f->view_stride, f->d_features_dc, f->d_features_rest, f->accumulate,
                                             nullptr, 0))
             return rc;
-    if (int rc = ghr_model_backward_segment(stream, m, m->P, v->radii, v->geom_ws, v->grad_scratch, v->d_means2D, v->d_xyz,
-                                            v->d_log_scales, v->d_rotations, v->d_opacity_logit, v->d_label_logit,
-                                            v->d_orient_conf_log, v->d_features_dc, v->d_features_rest, nullptr, v->accumulate,
-                                            v->nan_flag, v->R, v->bin_ws, v->R))
+    if (int rc = backward_segment(m, nullptr, nullptr, stream, m->P, v->radii, v->geom_ws, v->grad_scratch, pg, v->accumulate,
+                                  v->nan_flag, v->R, v->bin_ws, v->R))
         return rc;
     if (v->acc_record_event) GHR_HIP(hipEventRecord((hipEvent_t)v->acc_record_event, s));
     return GHR_OK;
@@ -1422,36 +1431,6 @@ namespace {
 int adam_step_range(void* stream, int64_t n, int64_t begin, int64_t count, const float* p_in, const float* m_in,
                     const float* v_in, float* p, float* g, float* m, float* v, int32_t* state, int32_t* flag, int32_t nan_mark,
                     int32_t n_groups, const int64_t* group_end_host, const float* lr_host, double beta1, double beta2,
-                    float eps, int32_t nan_guard, int32_t zero_grad, int32_t last, uint32_t skip_mask);
-}
-
-int ghr_adam_step_range(void* stream, int64_t n, int64_t begin, int64_t count, float* p, float* g, float* m, float* v,
-                        int32_t* state, int32_t n_groups, const int64_t* group_end_host, const float* lr_host,
-                        double beta1, double beta2, float eps, int32_t nan_guard, int32_t zero_grad, int32_t last,
-                        uint32_t skip_mask)
-{
-    return adam_step_range(stream, n, begin, count, nullptr, nullptr, nullptr, p, g, m, v, state, nullptr, 0, n_groups,
-                           group_end_host, lr_host, beta1, beta2, eps, nan_guard, zero_grad, last, skip_mask);
-}
-
-int ghr_adam_step_range_to(void* stream, int64_t n, int64_t begin, int64_t count, const float* p_in, const float* m_in,
-                           const float* v_in, float* p_out, float* g, float* m_out, float* v_out, int32_t* state,
-                           int32_t* flag, int32_t nan_mark, int32_t n_groups, const int64_t* group_end_host,
-                           const float* lr_host, double beta1, double beta2, float eps, int32_t zero_grad, uint32_t skip_mask)
-{
-    if (!p_in || !m_in || !v_in) return fail(GHR_E_INVALID, "ghr_adam_step_range_to: NULL input buffer");
-    if (nan_mark && !flag) return fail(GHR_E_INVALID, "ghr_adam_step_range_to: nan_mark needs the flag word");
-    if (p_in == p_out || m_in == m_out || v_in == v_out)
-        return fail(GHR_E_INVALID, "ghr_adam_step_range_to: in and out buffers must differ (ghr_adam_step_range updates in place)");
-    // (nan_guard 2: whoever produced the gradients keeps the flag; last 0: the caller's own finish advances the counter)
-    return adam_step_range(stream, n, begin, count, p_in, m_in, v_in, p_out, g, m_out, v_out, state, flag, nan_mark, n_groups,
-                           group_end_host, lr_host, beta1, beta2, eps, 2, zero_grad, 0, skip_mask);
-}
-
-namespace {
-int adam_step_range(void* stream, int64_t n, int64_t begin, int64_t count, const float* p_in, const float* m_in,
-                    const float* v_in, float* p, float* g, float* m, float* v, int32_t* state, int32_t* flag, int32_t nan_mark,
-                    int32_t n_groups, const int64_t* group_end_host, const float* lr_host, double beta1, double beta2,
                     float eps, int32_t nan_guard, int32_t zero_grad, int32_t last, uint32_t skip_mask)
 {
     if (n < 0 || begin < 0 || count < 0 || begin + count > n || !p || !g || !m || !v || !state || n_groups <= 0 ||
@@ -1486,6 +1465,29 @@ int adam_step_range(void* stream, int64_t n, int64_t begin, int64_t count, const
     return finish(s, 0);
 }
 }  // namespace
+
+int ghr_adam_step_range(void* stream, int64_t n, int64_t begin, int64_t count, float* p, float* g, float* m, float* v,
+                        int32_t* state, int32_t n_groups, const int64_t* group_end_host, const float* lr_host,
+                        double beta1, double beta2, float eps, int32_t nan_guard, int32_t zero_grad, int32_t last,
+                        uint32_t skip_mask)
+{
+    return adam_step_range(stream, n, begin, count, nullptr, nullptr, nullptr, p, g, m, v, state, nullptr, 0, n_groups,
+                           group_end_host, lr_host, beta1, beta2, eps, nan_guard, zero_grad, last, skip_mask);
+}
+
+int ghr_adam_step_range_to(void* stream, int64_t n, int64_t begin, int64_t count, const float* p_in, const float* m_in,
+                           const float* v_in, float* p_out, float* g, float* m_out, float* v_out, int32_t* state,
+                           int32_t* flag, int32_t nan_mark, int32_t n_groups, const int64_t* group_end_host,
+                           const float* lr_host, double beta1, double beta2, float eps, int32_t zero_grad, uint32_t skip_mask)
+{
+    if (!p_in || !m_in || !v_in) return fail(GHR_E_INVALID, "ghr_adam_step_range_to: NULL input buffer");
+    if (nan_mark && !flag) return fail(GHR_E_INVALID, "ghr_adam_step_range_to: nan_mark needs the flag word");
+    if (p_in == p_out || m_in == m_out || v_in == v_out)
+        return fail(GHR_E_INVALID, "ghr_adam_step_range_to: in and out buffers must differ (ghr_adam_step_range updates in place)");
+    // (nan_guard 2: whoever produced the gradients keeps the flag; last 0: the caller's own finish advances the counter)
+    return adam_step_range(stream, n, begin, count, p_in, m_in, v_in, p_out, g, m_out, v_out, state, flag, nan_mark, n_groups,
+                           group_end_host, lr_host, beta1, beta2, eps, 2, zero_grad, 0, skip_mask);
+}
 
 int ghr_adam_step(void* stream, int64_t n, float* p, float* g, float* m, float* v, int32_t* state, int32_t n_groups,
                   const int64_t* group_end_host, const float* lr_host, double beta1, double beta2, float eps,
@@ -1707,20 +1709,16 @@ int ghr_ws_inspect(int32_t P, int32_t W, int32_t H, int32_t mode_b, uint32_t R, 
                    const void* img_ws, const void* bin_ws, ghr_ws_view* out)
 {
     if (!out || P < 0 || W <= 0 || H <= 0) return fail(GHR_E_INVALID, "ghr_ws_inspect: bad args");
-    const size_t T = (size_t)grid_x(W) * grid_x(H);
-    Geom g; Img im; Bin b;
-    carve_geom(align_base(geom_ws), (size_t)P, mode_b != 0, &g);
-    carve_img(align_base(img_ws), (size_t)W * H, T, &im);
-    carve_bin(bin_ws ? align_base(bin_ws) : nullptr, (size_t)R, (size_t)T, &b);
-    out->rec = (const float*)g.rec;
-    out->depths = g.depths;
-    out->rects = (const uint32_t*)g.rects;
-    out->cov3D = g.cov3D;
-    out->final_T = im.final_T;
-    out->n_contrib = im.n_contrib;
-    out->tile_start = im.tile_start;
-    out->keys = b.keys;
-    out->point_list = b.point_list;
+    const ViewWs w = carve_view((size_t)P, W, H, mode_b != 0, R, geom_ws, img_ws, bin_ws);
+    out->rec = (const float*)w.g.rec;
+    out->depths = w.g.depths;
+    out->rects = (const uint32_t*)w.g.rects;
+    out->cov3D = w.g.cov3D;
+    out->final_T = w.im.final_T;
+    out->n_contrib = w.im.n_contrib;
+    out->tile_start = w.im.tile_start;
+    out->keys = w.b.keys;
+    out->point_list = w.b.point_list;
     return GHR_OK;
 }
 

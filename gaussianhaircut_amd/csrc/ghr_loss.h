@@ -1028,4 +1028,57 @@ __global__ void __launch_bounds__(64) k_loss_bwd_v(LossBwdArgs a)
 #endif
 }
 
+// One 1024-thread workgroup folds the 5 x n_slots partial sums the forward kernel's workgroups stored (above; laid out
+// [term][slot]): thread t takes the slots t, t + 1024, ... of every term (all of a round's loads in flight together), a DPP
+// sum inside each wave, and one thread per term adds the sixteen wave totals in double -- a fixed order, so the loss value
+// does not depend on how the forward kernel was scheduled.  (Built for latency: the kernel is a 5-us stop between the loss
+// forward and backward passes; a first form with double-precision butterflies took 12-17 us.)
+__global__ void __launch_bounds__(1024) k_loss_finalize(const float* slots, uint32_t n_slots, float w_l1, float w_ssim,
+                                                        float w_mask, float w_orient, float n_pix, float* aux, float* out)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ float s_part[GHR_LOSS_TERMS][16];
+    __shared__ double s_tot[GHR_LOSS_TERMS];
+    float s[GHR_LOSS_TERMS] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    for (uint32_t base = 0; base < n_slots; base += 8u * 1024u) {
+        float v[GHR_LOSS_TERMS][8];
+#pragma unroll
+        for (int k = 0; k < GHR_LOSS_TERMS; k++)
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                const uint32_t i = base + 1024u * u + threadIdx.x;
+                v[k][u] = i < n_slots ? slots[(size_t)k * n_slots + i] : 0.f;
+            }
+#pragma unroll
+        for (int k = 0; k < GHR_LOSS_TERMS; k++)
+            s[k] += ((v[k][0] + v[k][1]) + (v[k][2] + v[k][3])) + ((v[k][4] + v[k][5]) + (v[k][6] + v[k][7]));
+    }
+#pragma unroll
+    for (int k = 0; k < GHR_LOSS_TERMS; k++) {
+        const float w = wave_sum(s[k]);
+        if ((threadIdx.x & 63) == 0) s_part[k][threadIdx.x >> 6] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x < GHR_LOSS_TERMS) {
+        double t = 0;
+#pragma unroll
+        for (int w = 0; w < 16; w++) t += (double)s_part[threadIdx.x][w];
+        s_tot[threadIdx.x] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double s0 = s_tot[0], s1 = s_tot[1], s2 = s_tot[2], s3 = s_tot[3], s4 = s_tot[4];
+        float lo = 0.f, bad = 0.f;
+        if (w_orient != 0.f) {
+            lo = (float)(s3 / s4);
+            if (lo != lo) { lo = 0.f; bad = 1.f; }  // train_gaussians.py:134: a NaN orientation loss is dropped
+        }
+        aux[0] = (float)s4;
+        aux[1] = bad;
+        out[0] = (float)(w_l1 * (s0 / (3.0 * n_pix)) + w_ssim * (1.0 - s1 / (3.0 * n_pix)) + w_mask * (s2 / (2.0 * n_pix))) +
+                 w_orient * lo;
+    }
+#endif
+}
+
 }  // namespace ghr

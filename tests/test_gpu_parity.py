@@ -478,3 +478,49 @@ def test_rasterizer_op_recycles_its_image_workspace_and_changes_nothing():
     dgr.RECYCLE_IMG_WS = True
     for a, b in zip(outs[False], outs[True]):
         assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and a[2] == b[2]
+
+
+@pytest.mark.gpu
+def test_stage1_under_debug_verifies_a_recycled_image_workspace(dev):
+    """ghr_view_args.img_ws_recycled with `debug` (the op never sets both: through the C ABI): stage 1 reads the workspace's
+    per-tile counters back instead of zero-filling them.  P = 257 (a full block of 256 and one row), 34 x 18 pixels (3 x 2
+    tiles, W no multiple of 4), 3D covariances from scales and rotations (the mode-B carve).  After a complete pass the counters
+    are zero: the recycled pass is accepted and gives the first pass's count and radii.  Over a workspace of other content the
+    call is refused, in its own words, before anything is projected.  A fresh complete pass gives the first image, bit for bit."""
+    import ctypes
+    import math
+    from gaussianhaircut_amd import _lib
+    from tests import gpu_helpers as gh
+    spec = syn.WorkloadSpec("recycle_257_34x18", 600, 34, 18, 3, "random", math.log(0.05))
+    ri = syn.raster_inputs(spec, "cpu", cam="front")
+    assert ri["P"] >= 257
+    rows = ("means3D", "means2D", "colors", "opacities", "cov3D", "conic", "scales", "rotations")
+    ri = {k: (v[:257].contiguous().to(dev) if k in rows else v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in ri.items()}
+    run = gh.GpuRun(ri, "B_sr", debug=True)
+    assert run.mode_b and run.R > 0
+    first = run.out.clone(), run.radii.clone()
+    L, pinned = run.L, gh._pinned(run.dev)
+
+    def stage1():
+        run.radii.fill_(-1)
+        rc = L.ghr_forward_stage1(gh._stream(), ctypes.byref(run.args), gh._ptr(run.geom), gh._ptr(run.img), gh._ptr(run.radii),
+                                  ctypes.c_void_p(pinned.data_ptr()))
+        torch.cuda.synchronize()
+        return rc
+    run.args.img_ws_recycled = 1
+    assert stage1() == _lib.GHR_OK and int(pinned[0].item()) == run.R and torch.equal(run.radii, first[1])
+    # a workspace whose counters are not zero is refused; radii untouched: nothing was projected
+    run.img.fill_(255)
+    assert stage1() == _lib.GHR_E_INVALID
+    assert b"img_ws_recycled is set but the workspace's per-tile counters are not zero" in L.ghr_last_error()
+    assert bool((run.radii == -1).all())
+    run.img.zero_()
+    run.args.img_ws_recycled = 0   # the zero-fill again: the pass completes and leaves the counters at zero
+    assert stage1() == _lib.GHR_OK and int(pinned[0].item()) == run.R
+    run.out.fill_(float("nan"))
+    _lib.check(L.ghr_forward_stage2(gh._stream(), ctypes.byref(run.args), run.R, gh._ptr(run.geom), gh._ptr(run.img),
+                                    gh._ptr(run.bin), gh._ptr(run.out), None))
+    torch.cuda.synchronize()
+    assert torch.equal(run.out, first[0]) and torch.equal(run.radii, first[1])
+    run.args.img_ws_recycled = 1
+    assert stage1() == _lib.GHR_OK and torch.equal(run.radii, first[1])   # and recyclable again
