@@ -8,7 +8,11 @@
 * ``prune_strands`` / ``export_strands``  -- src/preprocessing/export_strands.py:58-79: drop the strands of which less than half
   the points lie outside the head mesh, write ``<name>_strands.pkl`` and ``<name>_strands.ply``.
 
-All three are restated, none uses a learned model; the only arithmetic of substance is ``mesh.HeadMesh`` (HIP).
+* ``cut_scalp`` / ``scalp_uv_mask`` / ``write_scalp_data``  -- src/preprocessing/extract_non_visible_head_scalp.py:177-229: cut
+  the scalp mesh to the vertices the views do not see as bare head (``visibility.vertex_visibility``), write
+  ``scalp_data/`` (stage 2's strand generator starts from it).
+
+All are restated, none uses a learned model; the arithmetic of substance is ``mesh.HeadMesh`` and ``visibility`` (HIP).
 """
 from __future__ import annotations
 
@@ -19,6 +23,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from . import visibility
 from .mesh import HeadMesh
 from .scene import ply_io
 
@@ -114,3 +119,70 @@ def export_strands(points, directory: str, name) -> tuple:
     xyz = p.reshape(-1, 3)
     ply_io.write_ply_vertices(ply, ["x", "y", "z", "nx", "ny", "nz"], np.concatenate([xyz, np.zeros_like(xyz)], axis=1))
     return pkl, ply
+
+
+def load_seam_pairs(path: str) -> list:
+    """The seam groups of a scalp template from a JSON file ``{"groups": [[i, j, ...], ...]}``: scalp-vertex indices that lie on
+    the same seam of the UV map and must be kept or cut together."""
+    import json
+    with open(path, "r") as f:
+        d = json.load(f)
+    return [[int(i) for i in g] for g in (d["groups"] if isinstance(d, dict) else d)]
+
+
+def cut_scalp(vertex_mask, scalp_vert_idx, scalp_faces, seam_pairs=()):
+    """The script's lines 177-218.  ``vertex_mask`` bool [V_head] (``visibility.visible_vertex_mask``), ``scalp_vert_idx`` [S] the
+    head-mesh vertices that form the scalp, ``scalp_faces`` [F, 3] over 0 .. S - 1, ``seam_pairs`` groups of scalp indices: one
+    after the other, every member of a group gets the minimum over the group.  Returns (kept [n] int64: the surviving scalp
+    indices, ascending; faces [m, 3] int64: the faces whose three vertices survive, renumbered)."""
+    mask = np.asarray(torch.as_tensor(vertex_mask).cpu()).astype(bool)
+    idx = np.asarray(torch.as_tensor(scalp_vert_idx).cpu()).astype(np.int64).reshape(-1)
+    faces = np.asarray(torch.as_tensor(scalp_faces).cpu()).astype(np.int64).reshape(-1, 3)
+    m = mask[idx].copy()
+    for group in seam_pairs:
+        g = np.asarray(list(group), np.int64)
+        m[g] = m[g].min()
+    kept = np.nonzero(m)[0]
+    new_id = np.full(len(idx), -1, np.int64)
+    new_id[kept] = np.arange(len(kept))
+    alive = m[faces].all(axis=1)
+    return kept, new_id[faces[alive]]
+
+
+def scalp_uv_mask(uvs, faces, size: int = 256, fused: bool = True, device=None) -> np.ndarray:
+    """The script's ``create_scalp_mask``: uint8 [size, size, 1], 255 where a face of the UV map ``uvs`` [n, 2] (in [-1, 1]) covers.
+    Computed by the mesh rasterizer on the affine view x' = (size - 1) / 2 (u + 1) + 0.5, likewise y', w = 1 -- the script's
+    integer sample (r, c) = (size - 1) / 2 (uv + 1) is this view's pixel centre -- followed by the script's transpose and flip.
+    skimage's ``polygon`` decides pixels that lie exactly on a polygon's boundary by its own rule: such pixels may differ."""
+    uv = np.asarray(torch.as_tensor(uvs).cpu(), np.float32).reshape(-1, 2)
+    v = np.concatenate([uv, np.zeros((len(uv), 1), np.float32)], axis=1)
+    h = (size - 1) / 2.0
+    M = np.array([h, 0, 0, h + 0.5, 0, h, 0, h + 0.5, 0, 0, 0, 1], np.float32)
+    pix = visibility.rasterize_mesh((v, np.asarray(torch.as_tensor(faces).cpu())), M, size, size, fused=fused, device=device)
+    # ours[i][j] samples (r, c) = (j, i): the script's img transposed, which is what it then forms itself before flipping
+    return np.ascontiguousarray(np.flipud((pix >= 0).cpu().numpy()).astype(np.uint8) * 255)[:, :, None]
+
+
+def write_scalp_data(directory: str, scalp_vertices, kept, faces, vis_planes=None, dif_mask=None) -> str:
+    """``<directory>/scalp_data`` in the script's layout: ``scalp.obj`` (the kept scalp vertices and the renumbered faces),
+    ``cut_scalp_verts.pickle`` (the list of kept scalp indices), ``vis/<name>.jpg`` for every entry of the dict ``vis_planes``
+    (uint8 [H, W]) and ``dif_mask.png`` ([size, size, 1] or [size, size]).  Returns the path of ``scalp_data``."""
+    from PIL import Image
+    out = os.path.join(directory, "scalp_data")
+    os.makedirs(os.path.join(out, "vis"), exist_ok=True)
+    sv = np.asarray(torch.as_tensor(scalp_vertices).cpu(), np.float32).reshape(-1, 3)
+    kept, faces = np.asarray(kept, np.int64), np.asarray(faces, np.int64).reshape(-1, 3)
+    with open(os.path.join(out, "scalp.obj"), "w") as f:
+        for p in sv[kept]:
+            f.write("v %f %f %f\n" % (p[0], p[1], p[2]))
+        for t in faces:
+            f.write("f %d %d %d\n" % (t[0] + 1, t[1] + 1, t[2] + 1))
+    with open(os.path.join(out, "cut_scalp_verts.pickle"), "wb") as f:
+        pickle.dump(list(kept), f)
+    for name, plane in (vis_planes or {}).items():
+        p = plane.cpu().numpy() if isinstance(plane, torch.Tensor) else np.asarray(plane)
+        Image.fromarray(np.ascontiguousarray(p, np.uint8)).save(os.path.join(out, "vis", "%s.jpg" % name))
+    if dif_mask is not None:
+        d = np.asarray(dif_mask, np.uint8)
+        Image.fromarray(d[:, :, 0] if d.ndim == 3 else d).save(os.path.join(out, "dif_mask.png"))
+    return out

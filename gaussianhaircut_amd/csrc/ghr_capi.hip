@@ -32,6 +32,7 @@
 #include "ghr_latent.h"
 #include "ghr_shared.h"
 #include "ghr_mesh.h"
+#include "ghr_visibility.h"
 
 namespace {
 
@@ -1966,6 +1967,96 @@ int ghr_gaussian_probe_outside(void* stream, const ghr_mesh_grid* header, const 
     ghr::MeshProbeArgs a{ghr::mesh_view(*reinterpret_cast<const ghr::MeshGrid*>(header), grid_dev), P, probe, xyz, scaling, rotation,
                          outside};
     hipLaunchKernelGGL(ghr::k_gaussian_probe_outside, dim3((unsigned)blocks), dim3(GHR_MESH_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+}  // extern "C"
+
+// ---- head-mesh visibility (include/ghr.h; csrc/ghr_visibility.h) --------------------------------------------------------------
+namespace {
+inline unsigned vis_blocks(int64_t n) { return (unsigned)((n + GHR_VIS_BLOCK - 1) / GHR_VIS_BLOCK); }
+}  // namespace
+
+extern "C" {
+
+int ghr_vis_sizes(int32_t V, int32_t F, int32_t H, int32_t W, size_t* bytes)
+{
+    static const char* fn = "ghr_vis_sizes: %s";
+    if (!bytes) return lt_bad(fn, "bytes is NULL");
+    ghr::VisLayout L;
+    if (const char* why = ghr::vis_layout(V, F, H, W, &L)) return lt_bad(fn, why);
+    *bytes = (size_t)L.bytes;
+    return GHR_OK;
+}
+
+int ghr_vis_head_mask(void* stream, int32_t H, int32_t W, const uint8_t* body, const uint8_t* hair, uint8_t* head)
+{
+    static const char* fn = "ghr_vis_head_mask: %s";
+    ghr::VisLayout L;
+    if (const char* why = ghr::vis_layout(0, 0, H, W, &L)) return lt_bad(fn, why);
+    if ((int64_t)H * W == 0) return GHR_OK;
+    if (!body || !hair) return lt_bad(fn, "body or hair is NULL");
+    if (!head) return lt_bad(fn, "head is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ghr::k_vis_head_mask, dim3((unsigned)L.tiles_x, (unsigned)L.tiles_y), dim3(GHR_VIS_BLOCK), 0, s,
+                       ghr::VisHeadArgs{H, W, body, hair, head});
+    return finish(s, 0);
+}
+
+int ghr_vis_view(void* stream, int32_t V, const float* vertices, int32_t F, const int32_t* faces, const float* M, float near_w,
+                 int32_t H, int32_t W, const uint8_t* body, const uint8_t* hair, void* workspace, int32_t* pix_to_face,
+                 uint8_t* vis, int32_t* cnt, int32_t* cnt_head)
+{
+    static const char* fn = "ghr_vis_view: %s";
+    ghr::VisLayout L;
+    if (const char* why = ghr::vis_layout(V, F, H, W, &L)) return lt_bad(fn, why);
+    if (V && !vertices) return lt_bad(fn, "vertices is NULL");
+    if (F && !faces) return lt_bad(fn, "faces is NULL");
+    if (!M) return lt_bad(fn, "M is NULL");
+    if (!(near_w >= 0.f)) return lt_bad(fn, "near is negative or NaN");
+    if ((body == nullptr) != (hair == nullptr)) return lt_bad(fn, "body and hair must be given or NULL together");
+    if (!workspace) return lt_bad(fn, "workspace is NULL");
+    if (!al16(workspace)) return lt_bad(fn, "workspace is not 16-B aligned (the face records are read 16 B at a time)");
+    if ((cnt == nullptr) != (cnt_head == nullptr)) return lt_bad(fn, "cnt and cnt_head must be given or NULL together");
+    const bool pixels = (int64_t)H * W > 0;
+    if (pixels && !pix_to_face) return lt_bad(fn, "pix_to_face is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace);
+    ghr::VisArgs a{};
+    a.V = V; a.F = F; a.H = H; a.W = W; a.tiles_x = L.tiles_x; a.tiles_y = L.tiles_y;
+    a.near = near_w;
+    for (int k = 0; k < 12; k++) a.M[k] = M[k];
+    a.vertices = vertices; a.faces = faces;
+    a.proj = reinterpret_cast<float*>(ws + L.off_proj);
+    a.rec = reinterpret_cast<float*>(ws + L.off_rec);
+    a.start = reinterpret_cast<uint32_t*>(ws + L.off_start);
+    a.count = reinterpret_cast<uint32_t*>(ws + L.off_count);
+    a.nbig = reinterpret_cast<uint32_t*>(ws + L.off_nbig);
+    a.list = reinterpret_cast<uint32_t*>(ws + L.off_list);
+    a.big = reinterpret_cast<uint32_t*>(ws + L.off_big);
+    a.list_cap = (uint32_t)L.list_cap;
+    a.seen = reinterpret_cast<uint8_t*>(ws + L.off_seen);
+    a.seen_head = reinterpret_cast<uint8_t*>(ws + L.off_seen_head);
+    a.pix_to_face = pix_to_face; a.vis = vis; a.cnt = cnt; a.cnt_head = cnt_head;
+    // the tile counts, the big list's length and the vertex flags start every view at 0: one fill, so that a workspace needs no
+    // preparation by its owner and may change image size between views
+    GHR_HIP(hipMemsetAsync(ws + L.off_fill, 0, (size_t)L.fill_bytes, s));
+    if (pixels) {
+        if (F) {
+            if (V) hipLaunchKernelGGL(ghr::k_vis_project, dim3(vis_blocks(V)), dim3(GHR_VIS_BLOCK), 0, s, a);
+            hipLaunchKernelGGL(ghr::k_vis_setup, dim3(vis_blocks(F)), dim3(GHR_VIS_BLOCK), 0, s, a);
+        }
+        hipLaunchKernelGGL(ghr::k_vis_scan, dim3(1), dim3(GHR_VIS_BLOCK), 0, s, a);
+        if (F) hipLaunchKernelGGL(ghr::k_vis_scatter, dim3(vis_blocks(F)), dim3(GHR_VIS_BLOCK), 0, s, a);
+        if (body) {
+            uint8_t* head = reinterpret_cast<uint8_t*>(ws + L.off_head);
+            hipLaunchKernelGGL(ghr::k_vis_head_mask, dim3((unsigned)L.tiles_x, (unsigned)L.tiles_y), dim3(GHR_VIS_BLOCK), 0, s,
+                               ghr::VisHeadArgs{H, W, body, hair, head});
+            a.head = head;
+        }
+        hipLaunchKernelGGL(ghr::k_vis_raster, dim3((unsigned)L.tiles_x, (unsigned)L.tiles_y), dim3(GHR_VIS_BLOCK), 0, s, a);
+        if (V && F && cnt) hipLaunchKernelGGL(ghr::k_vis_accumulate, dim3(vis_blocks(V)), dim3(GHR_VIS_BLOCK), 0, s, a);
+    }
     return finish(s, 0);
 }
 

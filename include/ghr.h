@@ -802,6 +802,25 @@ int ghr_mesh_contains(void* stream, const ghr_mesh_grid* header, const void* gri
 int ghr_gaussian_probe_outside(void* stream, const ghr_mesh_grid* header, const void* grid_dev, int64_t P, const float* xyz,
                                const float* scaling, const float* rotation, int32_t probe, uint8_t* outside);
 
+/* ---- head-mesh visibility: a triangle rasterizer and the per-vertex view counts (csrc/ghr_visibility.h)
+ * Added without an ABI_VERSION bump: three new functions, no existing struct or signature changed.
+ * The definition of pix_to_face, of the head mask and of "seen" is the one at the top of csrc/ghr_visibility.h: pixel centres
+ * at +0.5, ghr_mesh.h's exact complementary edge predicates, the largest inverse depth wins, the lower face index among equals.
+ * ghr_vis_sizes: bytes of the workspace of one view of H x W pixels of a mesh of V vertices and F faces (device memory, 16-B
+ * aligned; it may be reused for any view of at most these sizes, one view at a time).
+ * ghr_vis_view: vertices [V][3], faces [F][3] (a face with an index outside 0 .. V - 1 never covers), M [12] on the HOST: the
+ * row-major 3 x 4 matrix to (x w, y w, w) in pixels; near: a vertex is valid iff its w is finite and > near.  body / hair: uint8
+ * [H][W] planes or both NULL (head then holds nowhere).  Writes pix_to_face [H][W] int32 (-1: nothing) and, unless NULL,
+ * vis [H][W] uint8 (255 where a face wins and head holds); unless both NULL, ADDS to cnt [V] / cnt_head [V] (int32) 1 for every
+ * vertex a winning face of this view has / has at a pixel where head holds.  V == 0, F == 0 and H * W == 0 are valid.
+ * ghr_vis_head_mask: head [H][W] bytes 0 / 1 = (max5x5(body) >= 128) and not (max5x5(hair) >= 128), windows clipped to the image.
+ * A refused call launches nothing and ghr_last_error() says why. */
+int ghr_vis_sizes(int32_t V, int32_t F, int32_t H, int32_t W, size_t* bytes);
+int ghr_vis_view(void* stream, int32_t V, const float* vertices, int32_t F, const int32_t* faces, const float* M, float near_w,
+                 int32_t H, int32_t W, const uint8_t* body, const uint8_t* hair, void* workspace, int32_t* pix_to_face,
+                 uint8_t* vis, int32_t* cnt, int32_t* cnt_head);
+int ghr_vis_head_mask(void* stream, int32_t H, int32_t W, const uint8_t* body, const uint8_t* hair, uint8_t* head);
+
 /* Introspection for tests (device pointers into the workspaces; layout is otherwise private). */
 typedef struct ghr_ws_view {
     const float* rec;          /* [P][16]: x, y, conic a, b, c, opacity, features[10] */

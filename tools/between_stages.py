@@ -1,4 +1,4 @@
-"""The three steps the reference's run.sh takes between its training stages, on the reference's directory layout:
+"""The steps the reference's run.sh takes between its training stages, on the reference's directory layout:
 
     python tools/between_stages.py crop   --model_path M --path_to_data D [--iter 30000]
         M/point_cloud/iteration_N/raw_point_cloud.ply -> M/point_cloud_cropped/iteration_N/point_cloud.ply (+ raw_), D/scale.pickle
@@ -6,9 +6,17 @@
         M/point_cloud_cropped/iteration_N/raw_point_cloud.ply -> M/point_cloud_filtered/iteration_N/point_cloud.ply (+ raw_)
     python tools/between_stages.py export --points P.npy|P.pkl --mesh HEAD.obj --out_dir DIR [--iter 30000]
         strand points [S, L, 3] -> DIR/N_strands.pkl, DIR/N_strands.ply
+    python tools/between_stages.py scalp  --mesh HEAD.obj --cams CAMS.pkl --path_to_data D --out_dir FLAME_DIR
+                                          --scalp_idx I --scalp_faces F --scalp_uvs UV [--seam_pairs SEAMS.json]
+        D/masks_2/{body,hair}/<view>.png -> FLAME_DIR/scalp_data/{scalp.obj, cut_scalp_verts.pickle, dif_mask.png, vis/<view>.jpg}
+        CAMS.pkl: the reference's cameras pickle (view -> 4 x 4 projection, stored transposed), or a pickle of a list of this
+        package's cameras (their image_name names the masks).  I, F, UV: the scalp template's vertex indices into the head mesh,
+        its faces and its UV map, each a .npy, .pkl or .pth file; SEAMS.json: {"groups": [[...], ...]}, scalp vertices kept or cut
+        together.
 
-(src/preprocessing/scale_scene_into_sphere.py, filter_flame_intersections.py, export_strands.py.)  The containment runs in HIP on
-cuda:0; --composed evaluates the PyTorch-composed form instead (any device, slow)."""
+(src/preprocessing/scale_scene_into_sphere.py, filter_flame_intersections.py, export_strands.py,
+extract_non_visible_head_scalp.py.)  Containment and visibility run in HIP on cuda:0; --composed evaluates the PyTorch-composed
+forms instead (any device, slow)."""
 import argparse
 import os
 import pickle
@@ -29,9 +37,47 @@ def _load(path, sh_degree, device):
     return m
 
 
+def _load_array(path):
+    if path.endswith(".npy"):
+        return np.load(path)
+    if path.endswith((".pth", ".pt")):
+        return torch.load(path, map_location="cpu").numpy()
+    with open(path, "rb") as f:
+        return np.asarray(pickle.load(f))
+
+
+def _scalp(a, fused, dev):
+    from PIL import Image
+    from gaussianhaircut_amd import visibility as vis
+    from gaussianhaircut_amd.mesh import read_obj
+    v, f = read_obj(a.mesh)
+    with open(a.cams, "rb") as fh:
+        cams = pickle.load(fh)
+    read = lambda kind, name: np.asarray(Image.open(os.path.join(a.path_to_data, "masks_2", kind, "%s.png" % name)).convert("L"))  # noqa: E731
+    if isinstance(cams, dict):
+        names = list(cams)
+        masks = [(read("body", n), read("hair", n)) for n in names]
+        P = {n: (cams[n].T if isinstance(cams[n], np.ndarray) else cams[n].transpose(0, 1)) for n in names}
+        by_name = vis.views_from_projections(P, {n: m[0].shape for n, m in zip(names, masks)})
+        views = [by_name[n] for n in names]
+    else:
+        names = [c.image_name for c in cams]
+        views = [vis.view_matrix_from_camera(c) for c in cams]
+        masks = [(read("body", n), read("hair", n)) for n in names]
+    cnt, cnt_head, planes = vis.vertex_visibility((v, f), views, masks, fused=fused, device=dev)
+    vertex_mask = vis.visible_vertex_mask(cnt, cnt_head, len(views), a.prob_thr, a.n_views_thr)
+    idx, sf, uv = _load_array(a.scalp_idx), _load_array(a.scalp_faces), _load_array(a.scalp_uvs)
+    seams = bs.load_seam_pairs(a.seam_pairs) if a.seam_pairs else []
+    kept, faces = bs.cut_scalp(vertex_mask, idx, sf, seams)
+    dif = bs.scalp_uv_mask(uv.reshape(-1, 2)[kept], faces, fused=fused, device=dev)
+    out = bs.write_scalp_data(a.out_dir, v[np.asarray(idx).reshape(-1)], kept, faces, dict(zip(names, planes)), dif)
+    print("scalp: %d views; %d of %d head vertices marked; kept %d of %d scalp vertices, %d of %d faces -> %s"
+          % (len(views), int(vertex_mask.sum()), len(v), len(kept), len(np.asarray(idx).reshape(-1)), len(faces), len(sf.reshape(-1, 3)), out))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("step", choices=["crop", "filter", "export"])
+    ap.add_argument("step", choices=["crop", "filter", "export", "scalp"])
     ap.add_argument("--model_path")
     ap.add_argument("--path_to_data")
     ap.add_argument("--mesh")
@@ -42,11 +88,20 @@ def main(argv=None):
     ap.add_argument("--probe", default="reference", choices=["reference", "ellipsoid", "axis_scaled"])
     ap.add_argument("--composed", action="store_true")
     ap.add_argument("--device", default=None)
+    ap.add_argument("--cams")
+    ap.add_argument("--scalp_idx")
+    ap.add_argument("--scalp_faces")
+    ap.add_argument("--scalp_uvs")
+    ap.add_argument("--seam_pairs")
+    ap.add_argument("--prob_thr", type=float, default=0.5)
+    ap.add_argument("--n_views_thr", type=float, default=0.1)
     a = ap.parse_args(argv)
     fused = not a.composed
     dev = torch.device(a.device or ("cuda:0" if fused else "cpu"))
     it = "iteration_%d" % a.iter
-    if a.step == "crop":
+    if a.step == "scalp":
+        _scalp(a, fused, dev)
+    elif a.step == "crop":
         m = _load(os.path.join(a.model_path, "point_cloud", it, "raw_point_cloud.ply"), a.sh_degree, dev)
         tr, s = bs.hair_sphere(m)
         keep = bs.crop_to_sphere(m, tr, s)
