@@ -11,6 +11,8 @@ One hot path of eth-ait/GaussianHaircut, rebuilt from scratch behind the referen
 * ``gaussianhaircut_amd.between_stages`` / ``mesh``   -- the steps between the training stages: hair sphere and crop, the head-mesh
   filter, strand pruning and export (reference: ``src/preprocessing/scale_scene_into_sphere.py``,
   ``filter_flame_intersections.py``, ``export_strands.py``); point-in-mesh containment in HIP
+* ``gaussianhaircut_amd.strand_prior``                 -- the strand stage's prior term between its two networks: guiding strands in
+  their local frames and the latent texture, in HIP (reference: ``src/scene/gaussian_model_strands.py:456-515``)
 * ``gaussianhaircut_amd.parallel``                     -- view-sharded data parallel step (RCCL all-reduce of Gaussian grads)
 
 The compute lives in ``csrc/`` (hand-written HIP, C ABI in ``include/ghr.h``).  No CPU fallback exists.

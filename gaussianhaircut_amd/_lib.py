@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GHR_LIB_PATH") or os.path.join(CSRC, "libghr_hip.so")  # override: kernel experiments
 SOURCES = ["ghr_capi.hip"]
 HEADERS = ["ghr_device.h", "ghr_preprocess.h", "ghr_binning.h", "ghr_render_fwd.h", "ghr_render_bwd.h", "ghr_render_bwd2.h", "ghr_render_bwd3.h",
-           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_visibility.h"]
+           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_visibility.h", "ghr_sds.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-fPIC",
                "-shared"]
 
@@ -211,7 +211,8 @@ EXPORTS = ["ghr_last_error", "ghr_abi_version", "ghr_forward_sizes", "ghr_binnin
            "ghr_latent_loss_sums_floats", "ghr_latent_loss_forward", "ghr_latent_loss_backward",
            "ghr_model_forward_segment_shared", "ghr_model_backward_segment_shared", "ghr_shared_sh_fold",
            "ghr_mesh_grid_sizes", "ghr_mesh_grid_build", "ghr_mesh_contains", "ghr_gaussian_probe_outside",
-           "ghr_vis_sizes", "ghr_vis_view", "ghr_vis_head_mask"]
+           "ghr_vis_sizes", "ghr_vis_view", "ghr_vis_head_mask",
+           "ghr_sds_local", "ghr_sds_local_backward", "ghr_sds_texture", "ghr_sds_texture_backward"]
 
 _lib = None
 
@@ -311,6 +312,10 @@ def lib() -> ctypes.CDLL:
     L.ghr_vis_sizes.argtypes = [i32, i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
     L.ghr_vis_view.argtypes = [vp, i32, vp, i32, vp, ctypes.POINTER(ctypes.c_float * 12), f32, i32, i32] + [vp] * 7
     L.ghr_vis_head_mask.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.ghr_sds_local.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, f32, vp, vp]
+    L.ghr_sds_local_backward.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, f32, vp, vp, vp]
+    L.ghr_sds_texture.argtypes = [vp, i32, i32, i32, i32] + [vp] * 13
+    L.ghr_sds_texture_backward.argtypes = [vp, i32, i32, i32, i32] + [vp] * 13
     L.ghr_ws_inspect.argtypes = [i32, i32, i32, i32, u32, vp, vp, vp, ctypes.POINTER(WsView)]
     for name in EXPORTS:
         fn = getattr(L, name)

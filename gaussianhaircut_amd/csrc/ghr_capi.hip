@@ -33,6 +33,7 @@
 #include "ghr_shared.h"
 #include "ghr_mesh.h"
 #include "ghr_visibility.h"
+#include "ghr_sds.h"
 
 namespace {
 
@@ -2057,6 +2058,111 @@ int ghr_vis_view(void* stream, int32_t V, const float* vertices, int32_t F, cons
         hipLaunchKernelGGL(ghr::k_vis_raster, dim3((unsigned)L.tiles_x, (unsigned)L.tiles_y), dim3(GHR_VIS_BLOCK), 0, s, a);
         if (V && F && cnt) hipLaunchKernelGGL(ghr::k_vis_accumulate, dim3(vis_blocks(V)), dim3(GHR_VIS_BLOCK), 0, s, a);
     }
+    return finish(s, 0);
+}
+
+}  // extern "C"
+
+// ---- the strand stage's prior term: guiding strands' local frames and the latent texture (include/ghr.h; csrc/ghr_sds.h) ------
+namespace {
+inline unsigned sds_blocks(int64_t waves) { return (unsigned)((waves + GHR_SDS_BLOCK / GHR_SDS_WAVE - 1) / (GHR_SDS_BLOCK / GHR_SDS_WAVE)); }
+
+// the sizes every entry shares, before anything touches the runtime; S < 0: not checked (the texture has no S)
+const char* sds_sizes(int64_t S, int64_t N, int64_t n, int64_t C, int64_t G)
+{
+    if (N < GHR_SDS_K) return "N < 4: a texel needs four guiding strands";
+    if (n < 1) return "n < 1";
+    if (S == 0) return "S < 1";
+    if (C < 1) return "C < 1";
+    if (G >= 0 && G * G < N) return "G * G < N: guiding strand g takes its coefficient from texel g";
+    if (G > 16384 || N > (1 << 24) || N * (n + 1) * 3 >= (1ll << 31) || N * C >= (1ll << 31) || (G >= 0 && C * G * G >= (1ll << 31)) ||
+        (S > 0 && S * n * 3 >= (1ll << 40)))
+        return "sizes exceed the kernels' 32-bit indexing";
+    return nullptr;
+}
+}  // namespace
+
+extern "C" {
+
+int ghr_sds_local(void* stream, int32_t S, int32_t N, int32_t n, const float* dirs, const float* frames, int32_t frames_are_inverse,
+                  const int64_t* idx, float scale, float* e, float* v)
+{
+    static const char* fn = "ghr_sds_local: %s";
+    if (S < 0) return lt_bad(fn, "S is negative");
+    if (const char* why = sds_sizes(S, N, n, 1, -1)) return lt_bad(fn, why);
+    if (!dirs || !frames || !idx) return lt_bad(fn, "dirs, frames or idx is NULL");
+    if (!e || !v) return lt_bad(fn, "e or v is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::SdsLocalArgs a{};
+    a.S = S; a.N = N; a.n = n; a.frames_are_inverse = frames_are_inverse; a.scale = scale;
+    a.dirs = dirs; a.frames = frames; a.idx = idx; a.e = e; a.v = v;
+    hipLaunchKernelGGL(ghr::k_sds_local, dim3(sds_blocks(N)), dim3(GHR_SDS_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+int ghr_sds_local_backward(void* stream, int32_t S, int32_t N, int32_t n, const float* frames, int32_t frames_are_inverse,
+                           const int64_t* sorted_idx, const int64_t* order, float scale, const float* d_e, const float* d_v,
+                           float* d_dirs)
+{
+    static const char* fn = "ghr_sds_local_backward: %s";
+    if (S < 0) return lt_bad(fn, "S is negative");
+    if (const char* why = sds_sizes(S, N, n, 1, -1)) return lt_bad(fn, why);
+    if (!frames || !sorted_idx || !order) return lt_bad(fn, "frames, sorted_idx or order is NULL");
+    if (!d_dirs) return lt_bad(fn, "d_dirs is NULL");
+    if (!d_e && !d_v) return GHR_OK;  // nothing arrives: the zero-filled d_dirs is the answer
+    hipStream_t s = (hipStream_t)stream;
+    ghr::SdsLocalArgs a{};
+    a.S = S; a.N = N; a.n = n; a.frames_are_inverse = frames_are_inverse; a.scale = scale;
+    a.frames = frames; a.idx = sorted_idx; a.order = order; a.d_e = d_e; a.d_v = d_v; a.d_dirs = d_dirs;
+    hipLaunchKernelGGL(ghr::k_sds_local_bwd, dim3(sds_blocks(N)), dim3(GHR_SDS_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+int ghr_sds_texture(void* stream, int32_t N, int32_t n, int32_t C, int32_t G, const float* uvg, const float* centres, const float* z,
+                    const float* v, int32_t* nbr, float* w, float* csim, float* alpha, float* alpha_q, int32_t* count,
+                    int32_t* start, int32_t* list, float* texture)
+{
+    static const char* fn = "ghr_sds_texture: %s";
+    if (G < 0) return lt_bad(fn, "G is negative");
+    if (const char* why = sds_sizes(-1, N, n, C, G)) return lt_bad(fn, why);
+    if (!uvg || !centres || !z || !v) return lt_bad(fn, "uvg, centres, z or v is NULL");
+    if (!nbr || !w || !csim || !alpha || !alpha_q || !count || !start || !list) return lt_bad(fn, "a saved-state buffer is NULL");
+    if (!texture) return lt_bad(fn, "texture is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::SdsTexArgs a{};
+    a.N = N; a.n = n; a.C = C; a.G = G; a.uvg = uvg; a.centres = centres; a.z = z; a.v = v;
+    a.nbr = nbr; a.w = w; a.csim = csim; a.alpha = alpha; a.alpha_q = alpha_q; a.count = count; a.start = start; a.list = list;
+    a.texture = texture;
+    const int64_t GG = (int64_t)G * G;
+    GHR_HIP(hipMemsetAsync(count, 0, sizeof(int32_t) * (size_t)N, s));
+    hipLaunchKernelGGL(ghr::k_sds_knn, dim3(sds_blocks(GG)), dim3(GHR_SDS_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_sds_lists, dim3(sds_blocks(N)), dim3(GHR_SDS_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_sds_blend, dim3(sds_blocks(GG)), dim3(GHR_SDS_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+int ghr_sds_texture_backward(void* stream, int32_t N, int32_t n, int32_t C, int32_t G, const float* z, const float* v,
+                             const int32_t* nbr, const float* w, const float* csim, const float* alpha_q, const int32_t* start,
+                             const int32_t* list, const float* d_texture, float* dalpha_q, float* d_csim, float* d_z, float* d_v)
+{
+    static const char* fn = "ghr_sds_texture_backward: %s";
+    if (G < 0) return lt_bad(fn, "G is negative");
+    if (const char* why = sds_sizes(-1, N, n, C, G)) return lt_bad(fn, why);
+    if (!z || !v) return lt_bad(fn, "z or v is NULL");
+    if (!nbr || !w || !csim || !alpha_q || !start || !list) return lt_bad(fn, "a saved-state buffer is NULL");
+    if (!d_texture) return lt_bad(fn, "d_texture is NULL");
+    if (!dalpha_q || !d_csim) return lt_bad(fn, "dalpha_q or d_csim is NULL");
+    if (!d_z) return lt_bad(fn, "d_z is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::SdsTexArgs a{};
+    a.N = N; a.n = n; a.C = C; a.G = G; a.z = z; a.v = v;
+    a.nbr = const_cast<int32_t*>(nbr); a.w = const_cast<float*>(w); a.csim = const_cast<float*>(csim);
+    a.alpha_q = const_cast<float*>(alpha_q); a.start = const_cast<int32_t*>(start); a.list = const_cast<int32_t*>(list);
+    a.d_texture = d_texture; a.dalpha_q = dalpha_q; a.d_csim = d_csim; a.d_z = d_z; a.d_v = d_v;
+    const int64_t GG = (int64_t)G * G;
+    hipLaunchKernelGGL(ghr::k_sds_bwd_texel, dim3(sds_blocks(GG)), dim3(GHR_SDS_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_sds_bwd_gather, dim3(sds_blocks(N)), dim3(GHR_SDS_BLOCK), 0, s, a);
+    if (d_v) hipLaunchKernelGGL(ghr::k_sds_bwd_v, dim3(sds_blocks(N)), dim3(GHR_SDS_BLOCK), 0, s, a);
     return finish(s, 0);
 }
 

@@ -68,6 +68,17 @@ class GaussianModelStrands(GaussianModel):
     def __init__(self, sh_degree: int, scale: float = 1e-3):
         super().__init__(sh_degree)
         self.scale = scale
+        self.use_sds = False  # the reference's constructor says True: its networks are built there; here a prior is attached
+        self.prior = None
+        self.Lsds = None
+
+    def attach_prior(self, prior):
+        """``prior``: a callable ``dirs -> Lsds`` (``strand_prior.StrandPrior``).  From now on ``initialize_gaussians_hair()`` sets
+        ``self.Lsds`` as the reference's method does (gaussian_model_strands.py:456-515); ``None`` detaches."""
+        self.prior = prior
+        self.use_sds = prior is not None
+        self.Lsds = None
+        return self
 
     def create_from_strands(self, origins, dirs, features, orient_conf_log=None, spatial_lr_scale: float = 1.0):
         """origins: (S,1,3) roots, dirs: (S,n_seg,3) segment vectors, features: (S*n_seg, K, 3)."""
@@ -83,9 +94,13 @@ class GaussianModelStrands(GaussianModel):
         self.initialize_gaussians_hair()
         return self
 
-    def initialize_gaussians_hair(self):
-        """gaussian_model_strands.py:435-452.  On a ROCm device one HIP kernel each way (``ghr_strand_build``, csrc/ghr_strands.h)
-        instead of ~55 PyTorch kernels per iteration; the polyline points ``_pts`` are then made on first use."""
+    def initialize_gaussians_hair(self, prior: bool = True):
+        """gaussian_model_strands.py:435-515.  On a ROCm device one HIP kernel each way (``ghr_strand_build``, csrc/ghr_strands.h)
+        instead of ~55 PyTorch kernels per iteration; the polyline points ``_pts`` are then made on first use.  With a prior
+        attached (``attach_prior``) and ``prior`` true, ``self.Lsds`` is computed from the strand directions (:456-515);
+        ``prior=False`` rebuilds the Gaussians only (a step's further views) and leaves ``Lsds`` as it is."""
+        if getattr(self, "use_sds", False) and prior:
+            self.Lsds = self.prior(self._dirs)
         self._dir = self._dirs.reshape(-1, 3)
         if FUSED_STRAND_BUILD and _strand_build_applies(self.pts_origins, self._dirs):
             self.__dict__.pop("_pts_value", None)

@@ -500,8 +500,10 @@ def densification_step(gaussians, render_pkg, opt, iteration: int, cameras_exten
 
 
 def strand_view_loss(render_pkg, cam, opt, fused=None, scale: float = 1.0):
-    """The strand-stage loss (src/train_strands.py:121-147 without the diffusion-prior term, whose networks are out of
-    scope): L1 and SSIM on the WHOLE image, mask L1, orientation loss weighted by the ground-truth confidence."""
+    """The image terms of the strand-stage loss (src/train_strands.py:121-138): L1 and SSIM on the WHOLE image, mask L1, the
+    orientation loss weighted by the ground-truth confidence.  The prior term ``Lsds * lambda_dsds`` (:139-147) does not depend
+    on the view: ``strand_training_step`` adds it once per step when the strand model has a prior attached
+    (``GaussianModelStrands.attach_prior``, strand_prior.py) -- its two networks are the prior's callables."""
     image, mask = render_pkg["render"], render_pkg["mask"]
     gt_image, gt_mask = cam.original_image, cam.original_mask
     if fused is None:
@@ -529,7 +531,11 @@ def strand_view_loss(render_pkg, cam, opt, fused=None, scale: float = 1.0):
 
 def strand_training_step(gaussians, gaussians_hair, cams: List, background, opt, iteration: int, pipe=PIPE):
     """One iteration of the strand stage (src/train_strands.py:98-160): rebuild the strand Gaussians from the strand
-    parameters, render head + hair, loss, backward, NaN guard on the strand parameters, Adam."""
+    parameters, render head + hair, loss, backward, NaN guard on the strand parameters, Adam.  With a prior attached to the
+    strand model the step's first rebuild computes ``Lsds`` and ``Lsds * opt.lambda_dsds`` joins the first view's loss, whole
+    (not divided by the number of views); the term has no NaN drop (the reference has none): a NaN reaches ``_dirs.grad`` and
+    the step is skipped by the guard below."""
+    use_sds = bool(getattr(gaussians_hair, "use_sds", False))
     gaussians_hair.initialize_gaussians_hair()
     gaussians_hair.update_learning_rate(iteration)
     V = len(cams)
@@ -550,13 +556,18 @@ def strand_training_step(gaussians, gaussians_hair, cams: List, background, opt,
         run_pipe = SimpleNamespace(**{**vars(pipe), "fuse_adam": True})
     fused_done = False
     try:
-        for cam in cams:
+        for view, cam in enumerate(cams):
             pkg = render_hair(cam, gaussians, gaussians_hair, run_pipe, background)
             loss = strand_view_loss(pkg, cam, opt, scale=1.0 / V)
+            if use_sds and view == 0:
+                loss = loss + gaussians_hair.Lsds.to(loss.dtype) * opt.lambda_dsds
             loss.backward(gradient=_one_like(loss))
             losses.append(loss.detach())
-            if cam is not cams[-1]:
-                gaussians_hair.initialize_gaussians_hair()  # a fresh graph for the next view
+            if cam is not cams[-1]:  # a fresh graph for the next view (the prior's term is in the first view's already)
+                if use_sds:
+                    gaussians_hair.initialize_gaussians_hair(prior=False)
+                else:
+                    gaussians_hair.initialize_gaussians_hair()
         if fuse and o.fused_update_launched:
             o.finish_fused_step_with_late_groups([g["name"] for g in o.param_groups if g["name"] not in ("f_dc", "f_rest")])
     finally:

@@ -821,6 +821,36 @@ int ghr_vis_view(void* stream, int32_t V, const float* vertices, int32_t F, cons
                  uint8_t* vis, int32_t* cnt, int32_t* cnt_head);
 int ghr_vis_head_mask(void* stream, int32_t H, int32_t W, const uint8_t* body, const uint8_t* hair, uint8_t* head);
 
+/* ---- the strand stage's prior term between its networks (csrc/ghr_sds.h)
+ * Added without an ABI_VERSION bump: four new functions, no existing struct or signature changed.
+ * ghr_sds_local: N guiding strands idx [N] (int64, drawn with replacement from 0 .. S - 1) of dirs [S][n][3] into their local
+ * frames: e [N][n + 1][3] = (M P) scale with P the running sum of the strand's segments from 0, v [N][n][3] = (M dir) scale.
+ * frames [S][3][3] row-major: local2world (M is its adjugate inverse, formed per strand) or, frames_are_inverse != 0, M itself.
+ * An index outside 0 .. S - 1 reads nothing and leaves NaN rows.
+ * ghr_sds_local_backward: d_dirs [S][n][3], ZERO-FILLED BY THE CALLER, += (M^T (d_v[g, i] + sum_{j > i} d_e[g, j])) scale for
+ * every guiding strand; sorted_idx / order [N] (int64) are a STABLE ascending sort of idx and its permutation: strands drawn
+ * more than once add in ascending g.  d_e or d_v may be NULL (both: nothing is launched).
+ * ghr_sds_texture: uvg [N][2] the guiding strands' UVs, centres [G] the texel centres of one axis (texel q = row G + col lies
+ * at (centres[col], centres[row])), z [N][C], v [N][n][3].  Writes nbr [G G][4] int32 (the four nearest under (d2, g)
+ * ascending), w [G G][4], csim / alpha [N] (of TEXEL q < N: alpha[g] is read by whoever chose guiding strand g), alpha_q [G G],
+ * the inverted lists start [N + 1] / list [4 G G] (entries 4 q + k, ascending within a strand; count [N] is their scratch) and
+ * texture [C][G][G].  Three kernels and one fill.
+ * ghr_sds_texture_backward: from the forward's buffers and d_texture [C][G][G]: d_z [N][C] and, unless NULL, d_v [N][n][3]
+ * (every element written); dalpha_q [G G] and d_csim [N] are scratch.  Sums run over the lists in their order: no atomics,
+ * the same bits every time.
+ * Refused before the runtime is touched: NULL pointers, N < 4, G G < N, C < 1, n < 1, S < 1. */
+int ghr_sds_local(void* stream, int32_t S, int32_t N, int32_t n, const float* dirs, const float* frames, int32_t frames_are_inverse,
+                  const int64_t* idx, float scale, float* e, float* v);
+int ghr_sds_local_backward(void* stream, int32_t S, int32_t N, int32_t n, const float* frames, int32_t frames_are_inverse,
+                           const int64_t* sorted_idx, const int64_t* order, float scale, const float* d_e, const float* d_v,
+                           float* d_dirs);
+int ghr_sds_texture(void* stream, int32_t N, int32_t n, int32_t C, int32_t G, const float* uvg, const float* centres, const float* z,
+                    const float* v, int32_t* nbr, float* w, float* csim, float* alpha, float* alpha_q, int32_t* count,
+                    int32_t* start, int32_t* list, float* texture);
+int ghr_sds_texture_backward(void* stream, int32_t N, int32_t n, int32_t C, int32_t G, const float* z, const float* v,
+                             const int32_t* nbr, const float* w, const float* csim, const float* alpha_q, const int32_t* start,
+                             const int32_t* list, const float* d_texture, float* dalpha_q, float* d_csim, float* d_z, float* d_v);
+
 /* Introspection for tests (device pointers into the workspaces; layout is otherwise private). */
 typedef struct ghr_ws_view {
     const float* rec;          /* [P][16]: x, y, conic a, b, c, opacity, features[10] */
