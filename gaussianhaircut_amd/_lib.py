@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GHR_LIB_PATH") or os.path.join(CSRC, "libghr_hip.so")  # override: kernel experiments
 SOURCES = ["ghr_capi.hip"]
 HEADERS = ["ghr_device.h", "ghr_preprocess.h", "ghr_binning.h", "ghr_render_fwd.h", "ghr_render_bwd.h", "ghr_render_bwd2.h", "ghr_render_bwd3.h",
-           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_visibility.h", "ghr_sds.h"]
+           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_visibility.h", "ghr_sds.h", "ghr_nn.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-fPIC",
                "-shared"]
 
@@ -212,7 +212,8 @@ EXPORTS = ["ghr_last_error", "ghr_abi_version", "ghr_forward_sizes", "ghr_binnin
            "ghr_model_forward_segment_shared", "ghr_model_backward_segment_shared", "ghr_shared_sh_fold",
            "ghr_mesh_grid_sizes", "ghr_mesh_grid_build", "ghr_mesh_contains", "ghr_gaussian_probe_outside",
            "ghr_vis_sizes", "ghr_vis_view", "ghr_vis_head_mask",
-           "ghr_sds_local", "ghr_sds_local_backward", "ghr_sds_texture", "ghr_sds_texture_backward"]
+           "ghr_sds_local", "ghr_sds_local_backward", "ghr_sds_texture", "ghr_sds_texture_backward",
+           "ghr_nn_workspace_size", "ghr_nn_search", "ghr_chamfer_point", "ghr_chamfer_point_backward"]
 
 _lib = None
 
@@ -316,6 +317,10 @@ def lib() -> ctypes.CDLL:
     L.ghr_sds_local_backward.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, f32, vp, vp, vp]
     L.ghr_sds_texture.argtypes = [vp, i32, i32, i32, i32] + [vp] * 13
     L.ghr_sds_texture_backward.argtypes = [vp, i32, i32, i32, i32] + [vp] * 13
+    L.ghr_nn_workspace_size.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]
+    L.ghr_nn_search.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int64, vp, vp, vp, i32, vp, vp, vp]
+    L.ghr_chamfer_point.argtypes = [vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp, i32, vp, vp, vp]
+    L.ghr_chamfer_point_backward.argtypes = [vp, ctypes.c_int64, ctypes.c_int64, i32] + [vp] * 8 + [i32] + [vp] * 5
     L.ghr_ws_inspect.argtypes = [i32, i32, i32, i32, u32, vp, vp, vp, ctypes.POINTER(WsView)]
     for name in EXPORTS:
         fn = getattr(L, name)
@@ -346,6 +351,12 @@ def forward_sizes(P: int, W: int, H: int, mode_b: bool):
 def knn_workspace_size(P: int) -> int:
     b = ctypes.c_size_t(0)
     check(lib().ghr_knn_workspace_size(P, ctypes.byref(b)))
+    return int(b.value)
+
+
+def nn_workspace_size(Px: int, Py: int) -> int:
+    b = ctypes.c_size_t(0)
+    check(lib().ghr_nn_workspace_size(Px, Py, ctypes.byref(b)))
     return int(b.value)
 
 

@@ -18,6 +18,7 @@
 #include "ghr_camera.h"
 #include "ghr_geom_bwd.h"
 #include "ghr_knn.h"
+#include "ghr_nn.h"
 #include "ghr_loss.h"
 #include "ghr_eval.h"
 #include "ghr_orient.h"
@@ -1588,6 +1589,130 @@ int ghr_knn_mean_dist2(void* stream, int64_t P, const float* points, const int64
                        (const long long*)order, sorted, bbox, sbox);
     hipLaunchKernelGGL(ghr::k_knn_search, dim3((unsigned)((nb + GHR_KNN_WAVES - 1) / GHR_KNN_WAVES)),
                        dim3(64 * GHR_KNN_WAVES), 0, s, (int)P, sorted, bbox, sbox, out);
+    return finish(s, 0);
+}
+
+// ---- cross-cloud nearest neighbour and the chamfer point terms (ghr_nn.h) ------------------------------------------------------
+static int nn_sizes(const char* fn, int64_t Px, int64_t Py)
+{
+    if (Px < 0 || Px >= ((int64_t)1 << 31)) return fail(GHR_E_INVALID, fn, "Px must be in [0, 2^31)");
+    if (Py < 0 || Py >= ((int64_t)1 << 31)) return fail(GHR_E_INVALID, fn, "Py must be in [0, 2^31)");
+    if (Py == 0) return fail(GHR_E_INVALID, fn, "Py == 0: there is no nearest neighbour in an empty cloud");
+    return GHR_OK;
+}
+
+static size_t nn_cloud_bytes(size_t P)
+{
+    const size_t nb = (P + GHR_KNN_BLOCK - 1) / GHR_KNN_BLOCK, ns = (nb + GHR_KNN_SUPER - 1) / GHR_KNN_SUPER;
+    return up(P * sizeof(float4)) + up(nb * 2 * sizeof(float4)) + up(ns * 2 * sizeof(float4));
+}
+
+int ghr_nn_workspace_size(int64_t Px, int64_t Py, size_t* bytes)
+{
+    static const char* fn = "ghr_nn_workspace_size: %s";
+    if (!bytes) return fail(GHR_E_INVALID, fn, "bytes is NULL");
+    if (int rc = nn_sizes(fn, Px, Py)) return rc;
+    *bytes = nn_cloud_bytes((size_t)Px) + nn_cloud_bytes((size_t)Py) + ALIGN;
+    return GHR_OK;
+}
+
+int ghr_nn_search(void* stream, int64_t Px, const float* x, const int64_t* order_x, const uint64_t* keys_x_sorted, int64_t Py,
+                  const float* y, const int64_t* order_y, const uint64_t* keys_y_sorted, int32_t norm, void* ws, float* dist,
+                  int32_t* idx)
+{
+    static const char* fn = "ghr_nn_search: %s";
+    if (int rc = nn_sizes(fn, Px, Py)) return rc;
+    if (norm != 1 && norm != 2) return fail(GHR_E_INVALID, fn, "norm must be 1 or 2");
+    if (Px == 0) return GHR_OK;
+    if (!x || !order_x || !keys_x_sorted) return fail(GHR_E_INVALID, fn, "x, order_x or keys_x_sorted is NULL");
+    if (!y || !order_y || !keys_y_sorted) return fail(GHR_E_INVALID, fn, "y, order_y or keys_y_sorted is NULL");
+    if (!ws || !dist || !idx) return fail(GHR_E_INVALID, fn, "ws, dist or idx is NULL");
+    const size_t nbx = ((size_t)Px + GHR_KNN_BLOCK - 1) / GHR_KNN_BLOCK, nsx = (nbx + GHR_KNN_SUPER - 1) / GHR_KNN_SUPER;
+    const size_t nby = ((size_t)Py + GHR_KNN_BLOCK - 1) / GHR_KNN_BLOCK, nsy = (nby + GHR_KNN_SUPER - 1) / GHR_KNN_SUPER;
+    char* base = align_base(ws);
+    float4* xs = (float4*)base;
+    float4* bbox_x = (float4*)(base + up((size_t)Px * sizeof(float4)));
+    float4* sbox_x = (float4*)((char*)bbox_x + up(nbx * 2 * sizeof(float4)));
+    base += nn_cloud_bytes((size_t)Px);
+    float4* ys = (float4*)base;
+    float4* bbox_y = (float4*)(base + up((size_t)Py * sizeof(float4)));
+    float4* sbox_y = (float4*)((char*)bbox_y + up(nby * 2 * sizeof(float4)));
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ghr::k_knn_boxes, dim3((unsigned)nsx), dim3(64 * GHR_KNN_WAVES), 0, s, (int)Px, x, (const long long*)order_x,
+                       xs, bbox_x, sbox_x);
+    hipLaunchKernelGGL(ghr::k_knn_boxes, dim3((unsigned)nsy), dim3(64 * GHR_KNN_WAVES), 0, s, (int)Py, y, (const long long*)order_y,
+                       ys, bbox_y, sbox_y);
+    const dim3 grid((unsigned)((nbx + GHR_NN_WAVES - 1) / GHR_NN_WAVES)), block(64 * GHR_NN_WAVES);
+    if (norm == 2)
+        hipLaunchKernelGGL(ghr::k_nn_search<2>, grid, block, 0, s, (int)Px, xs, (const unsigned long long*)keys_x_sorted, (int)Py, ys,
+                           bbox_y, sbox_y, (const unsigned long long*)keys_y_sorted, dist, idx);
+    else
+        hipLaunchKernelGGL(ghr::k_nn_search<1>, grid, block, 0, s, (int)Px, xs, (const unsigned long long*)keys_x_sorted, (int)Py, ys,
+                           bbox_y, sbox_y, (const unsigned long long*)keys_y_sorted, dist, idx);
+    return finish(s, 0);
+}
+
+#ifdef GHR_NN_COUNT_BLOCKS
+// measurement build only: reads {candidate blocks scanned, waves} since the last call and zeroes them (synchronises)
+int ghr_nn_read_counters(uint64_t* out2)
+{
+    unsigned long long h[2] = {0, 0}, z[2] = {0, 0};
+    GHR_HIP(hipDeviceSynchronize());
+    GHR_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(ghr::g_nn_count), sizeof(h)));
+    GHR_HIP(hipMemcpyToSymbol(HIP_SYMBOL(ghr::g_nn_count), z, sizeof(z)));
+    out2[0] = h[0]; out2[1] = h[1];
+    return GHR_OK;
+}
+#endif
+
+int ghr_chamfer_point(void* stream, int64_t Px, int64_t Py, const int32_t* idx, const float* x_normals, const float* y_normals,
+                      int32_t abs_cosine, const float* y_weights, float* term, float* weight)
+{
+    static const char* fn = "ghr_chamfer_point: %s";
+    if (int rc = nn_sizes(fn, Px, Py)) return rc;
+    if (Px == 0) return GHR_OK;
+    if (!idx) return fail(GHR_E_INVALID, fn, "idx is NULL");
+    if ((x_normals != nullptr) != (y_normals != nullptr) || (x_normals != nullptr) != (term != nullptr))
+        return fail(GHR_E_INVALID, fn, "x_normals, y_normals and term: all three or none");
+    if ((y_weights != nullptr) != (weight != nullptr)) return fail(GHR_E_INVALID, fn, "y_weights and weight: both or neither");
+    if (!term && !weight) return fail(GHR_E_INVALID, fn, "neither normals nor weights: nothing to compute");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ghr::k_chamfer_point, dim3((unsigned)((Px + GHR_NN_BLOCK - 1) / GHR_NN_BLOCK)), dim3(GHR_NN_BLOCK), 0, s,
+                       (int)Px, (int)Py, idx, x_normals, y_normals, abs_cosine, y_weights, term, weight);
+    return finish(s, 0);
+}
+
+int ghr_chamfer_point_backward(void* stream, int64_t Px, int64_t Py, int32_t norm, const float* x, const float* y, const int32_t* idx,
+                               const int64_t* start, const int64_t* members, const float* g_dist, const float* x_normals,
+                               const float* y_normals, int32_t abs_cosine, const float* g_cos, float* d_x, float* d_y,
+                               float* d_x_normals, float* d_y_normals)
+{
+    static const char* fn = "ghr_chamfer_point_backward: %s";
+    if (int rc = nn_sizes(fn, Px, Py)) return rc;
+    if (norm != 1 && norm != 2) return fail(GHR_E_INVALID, fn, "norm must be 1 or 2");
+    if (!idx || !start || !members) return fail(GHR_E_INVALID, fn, "idx, start or members is NULL");
+    const bool pts = g_dist != nullptr, nrm = g_cos != nullptr;
+    if (!pts && !nrm) return fail(GHR_E_INVALID, fn, "neither g_dist nor g_cos: nothing to compute");
+    if (pts && (!x || !y || !d_x || !d_y)) return fail(GHR_E_INVALID, fn, "g_dist needs x, y, d_x and d_y");
+    if (!pts && (d_x || d_y)) return fail(GHR_E_INVALID, fn, "d_x / d_y without g_dist");
+    if (nrm && (!x_normals || !y_normals || !d_x_normals || !d_y_normals))
+        return fail(GHR_E_INVALID, fn, "g_cos needs x_normals, y_normals, d_x_normals and d_y_normals");
+    if (!nrm && (d_x_normals || d_y_normals)) return fail(GHR_E_INVALID, fn, "d_x_normals / d_y_normals without g_cos");
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 gx((unsigned)((Px + GHR_NN_BLOCK - 1) / GHR_NN_BLOCK)), gy((unsigned)((Py + GHR_NN_BLOCK - 1) / GHR_NN_BLOCK));
+    if (norm == 2) {
+        if (Px > 0)
+            hipLaunchKernelGGL(ghr::k_chamfer_bwd_x<2>, gx, dim3(GHR_NN_BLOCK), 0, s, (int)Px, (int)Py, x, y, idx, g_dist, x_normals,
+                               y_normals, abs_cosine, g_cos, d_x, d_x_normals);
+        hipLaunchKernelGGL(ghr::k_chamfer_bwd_y<2>, gy, dim3(GHR_NN_BLOCK), 0, s, (int)Px, (int)Py, x, y, (const long long*)start,
+                           (const long long*)members, g_dist, x_normals, y_normals, abs_cosine, g_cos, d_y, d_y_normals);
+    } else {
+        if (Px > 0)
+            hipLaunchKernelGGL(ghr::k_chamfer_bwd_x<1>, gx, dim3(GHR_NN_BLOCK), 0, s, (int)Px, (int)Py, x, y, idx, g_dist, x_normals,
+                               y_normals, abs_cosine, g_cos, d_x, d_x_normals);
+        hipLaunchKernelGGL(ghr::k_chamfer_bwd_y<1>, gy, dim3(GHR_NN_BLOCK), 0, s, (int)Px, (int)Py, x, y, (const long long*)start,
+                           (const long long*)members, g_dist, x_normals, y_normals, abs_cosine, g_cos, d_y, d_y_normals);
+    }
     return finish(s, 0);
 }
 

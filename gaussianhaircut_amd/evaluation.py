@@ -305,3 +305,50 @@ def render_products(gaussians, cams: List, background, pipe=None, gaussians_hair
         pending = (s, cam, W, H)
     if pending is not None:
         yield finish(pending)
+
+
+# ---- strand geometry -----------------------------------------------------------------------------------------------------------
+
+def _segments(points: torch.Tensor):
+    """``[S, L, 3]`` strand points -> midpoints and directions of their ``S (L - 1)`` segments, ``[1, S (L - 1), 3]`` each."""
+    if points.dim() != 3 or points.shape[1] < 2 or points.shape[2] != 3:
+        raise ValueError("strand_geometry: strands must be [S, L >= 2, 3], got %s" % (tuple(points.shape),))
+    a, b = points[:, :-1], points[:, 1:]
+    return ((a + b) * 0.5).reshape(1, -1, 3).contiguous(), (b - a).reshape(1, -1, 3).contiguous()
+
+
+@torch.no_grad()
+def strand_geometry(pred_points: torch.Tensor, gt_points: torch.Tensor, dist_thresholds, angle_thresholds_deg,
+                    fused: Optional[bool] = None) -> dict:
+    """How far two grooms are from each other, on segment midpoints with the segment directions as normals (this package's own
+    definition; not the paper's evaluation script).  ``pred_points [S, L, 3]``, ``gt_points [S', L', 3]``.
+
+    Returns ``chamfer_pred_to_gt`` / ``chamfer_gt_to_pred`` (mean SQUARED distance of a midpoint to the nearest midpoint of the
+    other groom), ``direction_pred_to_gt`` / ``direction_gt_to_pred`` (mean ``1 - |cos|`` to that neighbour's direction) and, for
+    every pair of ``thresholds`` = ``dist_thresholds x angle_thresholds_deg``, ``precision`` (the share of predicted midpoints
+    whose neighbour lies within the distance -- a distance, not squared: ``d2 <= t_d^2`` -- AND at an unsigned angle below the
+    angle threshold: ``1 - |cos| < 1 - cos(t_a)``), ``recall`` (the same from the ground truth's side) and ``fscore``
+    (``2 P R / (P + R)``, 0 when both are 0).  Lists are in ``thresholds``' order.  One read-back at the end."""
+    from . import nearest
+    px, pn = _segments(pred_points)
+    gx, gn = _segments(gt_points)
+    sides = []
+    for (x, xn), (y, yn) in (((px, pn), (gx, gn)), ((gx, gn), (px, pn))):
+        nn = nearest.knn_points(x, y, norm=2, K=1, fused=fused)
+        term, _ = nearest.point_terms(nn.idx, xn, yn, abs_cosine=True, fused=fused)
+        sides.append((nn.dists[0, :, 0], term[0]))
+    thresholds = [(float(td), float(ta)) for td in dist_thresholds for ta in angle_thresholds_deg]
+    dev, dt = px.device, px.dtype
+    td2 = torch.tensor([td * td for td, _ in thresholds], dtype=dt, device=dev)
+    ta1 = torch.tensor([1.0 - float(np.cos(np.deg2rad(ta))) for _, ta in thresholds], dtype=dt, device=dev)
+    row = []
+    for d2, term in sides:
+        row += [d2.double().mean(), term.double().mean()]
+        hit = (d2[None, :] <= td2[:, None]) & (term[None, :] < ta1[:, None])
+        row.append(hit.sum(dim=1).double() / max(d2.shape[0], 1))
+    flat = torch.cat([t.reshape(-1) for t in row]).tolist()   # the one read-back
+    T = len(thresholds)
+    precision, recall = flat[2:2 + T], flat[4 + T:4 + 2 * T]
+    fscore = [2 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(precision, recall)]
+    return dict(chamfer_pred_to_gt=flat[0], direction_pred_to_gt=flat[1], chamfer_gt_to_pred=flat[2 + T],
+                direction_gt_to_pred=flat[3 + T], thresholds=thresholds, precision=precision, recall=recall, fscore=fscore)

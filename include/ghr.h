@@ -851,6 +851,34 @@ int ghr_sds_texture_backward(void* stream, int32_t N, int32_t n, int32_t C, int3
                              const int32_t* nbr, const float* w, const float* csim, const float* alpha_q, const int32_t* start,
                              const int32_t* list, const float* d_texture, float* dalpha_q, float* d_csim, float* d_z, float* d_v);
 
+/* ---- cross-cloud nearest neighbour and the point terms of a chamfer distance (csrc/ghr_nn.h)
+ * Added without an ABI_VERSION bump: four new functions, no existing struct or signature changed.
+ * For query x_i and every candidate y_j, j < Py: d = (dx*dx + dy*dy) + dz*dz (norm 2, the SQUARED distance) or
+ * d = (|dx| + |dy|) + |dz| (norm 1), dx = y_j.x - x_i.x, fp32 without contraction.  dist[i] is the smallest d and idx[i] the
+ * LOWEST original j among those that reach it: the same bits for any schedule and any permutation of either cloud; idx in
+ * [0, Py).  Finite coordinates are the caller's check: other bits give unspecified values, never an out-of-range access.
+ * Sequence: ghr_knn_keys on each cloud with bounds_dev = the bounds of their UNION; the caller sorts each cloud's keys (stable)
+ * and passes the permutations and the sorted keys; ghr_nn_search (two box passes and the search).
+ * ghr_chamfer_point: term[i] = 1 - cos or 1 - |cos| (abs_cosine != 0), cos = (a . b) / (max(|a|, 1e-6) max(|b|, 1e-6)),
+ * a = x_normals[i], b = y_normals[idx[i]]; weight[i] = y_weights[idx[i]].  Normals (with term) and weights (with weight) are
+ * each optional (NULL), not both.
+ * ghr_chamfer_point_backward: from g_dist [Px] (optional) d_x [Px][3] and d_y [Py][3], from g_cos [Px] (optional)
+ * d_x_normals / d_y_normals; every element written.  start [Py + 1] / members [Px] (int64): the queries that chose candidate j
+ * are members[start[j] .. start[j + 1]) in ASCENDING order (a stable sort of idx); d_y[j] adds their products in that order
+ * with one fp32 accumulator per component, no atomics: the same bits every time, +0 for a candidate nobody chose.
+ * Refused before the runtime is touched: sizes outside [0, 2^31), Py == 0, a norm other than 1 or 2, NULL pointers.
+ * Px == 0 does nothing in ghr_nn_search and ghr_chamfer_point. */
+int ghr_nn_workspace_size(int64_t Px, int64_t Py, size_t* bytes);
+int ghr_nn_search(void* stream, int64_t Px, const float* x, const int64_t* order_x, const uint64_t* keys_x_sorted, int64_t Py,
+                  const float* y, const int64_t* order_y, const uint64_t* keys_y_sorted, int32_t norm, void* ws, float* dist,
+                  int32_t* idx);
+int ghr_chamfer_point(void* stream, int64_t Px, int64_t Py, const int32_t* idx, const float* x_normals, const float* y_normals,
+                      int32_t abs_cosine, const float* y_weights, float* term, float* weight);
+int ghr_chamfer_point_backward(void* stream, int64_t Px, int64_t Py, int32_t norm, const float* x, const float* y, const int32_t* idx,
+                               const int64_t* start, const int64_t* members, const float* g_dist, const float* x_normals,
+                               const float* y_normals, int32_t abs_cosine, const float* g_cos, float* d_x, float* d_y,
+                               float* d_x_normals, float* d_y_normals);
+
 /* Introspection for tests (device pointers into the workspaces; layout is otherwise private). */
 typedef struct ghr_ws_view {
     const float* rec;          /* [P][16]: x, y, conic a, b, c, opacity, features[10] */
