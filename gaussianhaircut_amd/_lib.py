@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GHR_LIB_PATH") or os.path.join(CSRC, "libghr_hip.so")  # override: kernel experiments
 SOURCES = ["ghr_capi.hip"]
 HEADERS = ["ghr_device.h", "ghr_preprocess.h", "ghr_binning.h", "ghr_render_fwd.h", "ghr_render_bwd.h", "ghr_render_bwd2.h", "ghr_render_bwd3.h",
-           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_visibility.h", "ghr_sds.h", "ghr_nn.h"]
+           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_products.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_visibility.h", "ghr_sds.h", "ghr_nn.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-fPIC",
                "-shared"]
 
@@ -206,7 +206,7 @@ EXPORTS = ["ghr_last_error", "ghr_abi_version", "ghr_forward_sizes", "ghr_binnin
            "ghr_camera_compose", "ghr_camera_compose_backward", "ghr_camera_adam_step",
            "ghr_eval_scratch_floats", "ghr_eval_metrics", "ghr_eval_products",
            "ghr_orient_dog_scratch_bytes", "ghr_orient_dog", "ghr_orient_bank_floats", "ghr_orient_gabor",
-           "ghr_resample_scratch_bytes", "ghr_resample_u8", "ghr_gt_assemble", "ghr_gt_resize_variance",
+           "ghr_resample_scratch_bytes", "ghr_resample_u8", "ghr_gt_assemble", "ghr_gt_resize_variance", "ghr_gt_from_render",
            "ghr_strand_points_build", "ghr_strand_points_build_backward", "ghr_strand_rows_expand", "ghr_strand_rows_reduce",
            "ghr_latent_loss_sums_floats", "ghr_latent_loss_forward", "ghr_latent_loss_backward",
            "ghr_model_forward_segment_shared", "ghr_model_backward_segment_shared", "ghr_shared_sh_fold",
@@ -294,6 +294,7 @@ def lib() -> ctypes.CDLL:
     L.ghr_resample_u8.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp]
     L.ghr_gt_assemble.argtypes = [vp, i32, i32] + [vp] * 5 + [i32, i32, vp, vp, i32, i32, i32] + [vp] * 4
     L.ghr_gt_resize_variance.argtypes = [vp, i32, i32, vp, i32, i32, i32, vp]
+    L.ghr_gt_from_render.argtypes = [vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp]
     L.ghr_strand_points_build.argtypes = [vp, i32, i32, vp, f32, vp, vp, vp, vp]
     L.ghr_strand_points_build_backward.argtypes = [vp, i32, i32] + [vp] * 6
     L.ghr_strand_rows_expand.argtypes = [vp, i32, i32, i32, vp, vp]

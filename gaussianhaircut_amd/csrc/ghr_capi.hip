@@ -1430,6 +1430,24 @@ int ghr_gt_resize_variance(void* stream, int32_t W, int32_t H, const float* var,
     return finish(s, 0);
 }
 
+int ghr_gt_from_render(void* stream, int32_t W, int32_t H, const float* renders, const float* div255_table, int32_t white_background,
+                       int32_t binarize, float* out_image, float* out_mask, float* out_angle, float* out_conf)
+{
+    if (W < 1 || H < 1) return fail(GHR_E_INVALID, "ghr_gt_from_render: W and H must be >= 1");
+    if (!renders || !div255_table || !out_image || !out_mask || !out_angle || !out_conf)
+        return fail(GHR_E_INVALID, "ghr_gt_from_render: NULL buffer");
+    if (white_background != 0 && white_background != 1) return fail(GHR_E_INVALID, "ghr_gt_from_render: white_background must be 0 or 1");
+    const size_t N = (size_t)W * (size_t)H, quads = (N + 3) / 4, groups = (quads + 255) / 256;
+    if (groups > 0x7fffffffu) return fail(GHR_E_INVALID, "ghr_gt_from_render: image too large for the launch grid");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::GtFromRenderArgs a{W, H, renders, div255_table, white_background, binarize != 0, out_image, out_mask, out_angle, out_conf};
+    const dim3 grid((unsigned)groups);
+    const bool vec = (N & 3) == 0 && eval_aligned16({renders, out_image, out_mask, out_angle, out_conf});
+    if (vec) hipLaunchKernelGGL(ghr::k_gt_from_render<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(ghr::k_gt_from_render<false>, grid, dim3(256), 0, s, a);
+    return finish(s, 0);
+}
+
 namespace {
 int adam_step_range(void* stream, int64_t n, int64_t begin, int64_t count, const float* p_in, const float* m_in,
                     const float* v_in, float* p, float* g, float* m, float* v, int32_t* state, int32_t* flag, int32_t nan_mark,

@@ -12,33 +12,18 @@
 //   k_eval_ssim[_v]  the SSIM map's sum: the loss kernels' forward bodies (ghr_loss.h, EVAL) on the clamped images
 //   k_eval_finalize  folds both sets of slots in a fixed order in double into one row of GHR_EVAL_TERMS doubles
 //   k_eval_products  12 bytes + 1 float per pixel, ready for one device-to-host copy
+// The per-pixel functions of the products (orient_angle_of, quant8, vis_orient_pixel, product_pixel) are in ghr_products.h.
 // Every workgroup owns one slot and stores it: no atomics, nothing to zero, the same bits run after run.
 #pragma once
 #include "ghr_device.h"
 #include "ghr_loss.h"
+#include "ghr_products.h"
 
 namespace ghr {
 
 #define GHR_EVAL_TERMS 8        // doubles per view: {l1, ce, or_num, or_den, mse[3], ssim}
 #define GHR_EVAL_POINT_TERMS 7  // partial sums per slot of k_eval_points: the first seven of them
 #define GHR_EVAL_MAX_GROUPS 2048
-
-GHR_HD float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
-
-// Orientation angle / pi in (0, 1) of a rendered 2D strand direction (src/gaussian_renderer/__init__.py:100-105): the
-// normalise / mirror / clamp / acos chain of orient_pixel (ghr_loss.h), operation for operation.
-GHR_HD float orient_angle_of(float d0, float d1)
-{
-    const float INV_PI = 0.31830988618379067154f;
-    const float nrm = fast_sqrt(d0 * d0 + d1 * d1);
-    const float den = fmaxf(nrm, 1e-12f);  // F.normalize(dim=0), eps = 1e-12
-    const float iden = fast_rcp(den);
-    const float u0 = d0 * iden, u1 = d1 * iden;
-    const float mirror = u0 < 0.f ? -1.f : 1.f;
-    const float lo = -1.f + 1e-3f, hi = 1.f - 1e-3f;
-    const float uc = fminf(hi, fmaxf(lo, u1));
-    return acosf(uc * mirror) * INV_PI;
-}
 
 // One pixel of the packed render (rgb, hair label, foreground, dir2d x, dir2d y) and of the ground truth
 struct EvalIn {
@@ -70,46 +55,6 @@ GHR_HD EvalPix eval_pixel(const EvalIn& p, bool orient)
     return o;
 }
 
-// torchvision.utils.save_image: mul(255).add_(0.5).clamp_(0, 255).to(uint8)
-GHR_HD uint32_t quant8(float v) { return (uint32_t)fminf(fmaxf(v * 255.f + 0.5f, 0.f), 255.f); }
-
-// image_utils.py:22-37: the four colour ramps over the angle in degrees, BGR, swapped to RGB, times `mask`
-GHR_HD void vis_orient_pixel(float angle, float mask, float* rgb)
-{
-    const float deg = angle * 180.f;
-    const float red = clamp01(1.f - fabsf(deg - 0.f) / 45.f) + clamp01(1.f - fabsf(deg - 180.f) / 45.f);
-    const float green = clamp01(1.f - fabsf(deg - 90.f) / 45.f);
-    const float magenta = clamp01(1.f - fabsf(deg - 45.f) / 45.f);
-    const float teal = clamp01(1.f - fabsf(deg - 135.f) / 45.f);
-    rgb[0] = (red + magenta) * mask;  // bgr[2]
-    rgb[1] = (green + teal) * mask;   // bgr[1]
-    rgb[2] = (magenta + teal) * mask; // bgr[0]
-}
-
-struct ProductPix {
-    uint32_t render[3], hair, head, orient, orient_vis[3], conf_vis[3];  // 8-bit levels
-    float conf;                                                        // orient_conf * hair: the reference's .pth product
-};
-GHR_HD ProductPix product_pixel(const float* r, float m0, float m1, float d0, float d1, float conf)
-{
-    ProductPix o;
-#pragma unroll
-    for (int c = 0; c < 3; c++) o.render[c] = quant8(r[c]);
-    o.hair = quant8(m0);
-    o.head = quant8(m1);
-    const float angle = orient_angle_of(d0, d1);
-    o.orient = quant8(angle * m0);
-    float v[3];
-    vis_orient_pixel(angle, m0, v);
-#pragma unroll
-    for (int c = 0; c < 3; c++) o.orient_vis[c] = quant8(v[c]);
-    o.conf = conf * m0;
-    vis_orient_pixel(angle, 1.f - 1.f / (o.conf + 1.f), v);
-#pragma unroll
-    for (int c = 0; c < 3; c++) o.conf_vis[c] = quant8(v[c]);
-    return o;
-}
-
 struct EvalArgs {
     int W, H;
     const float* renders;   // [10,H,W] packed: rgb 0-2, mask 3-4, dir2d 5-6, orientation confidence 8
@@ -126,22 +71,6 @@ GHR_HD uint32_t eval_point_groups(int W, int H)
     const size_t quads = ((size_t)W * H + 3) / 4, g = (quads + 255) / 256;
     return (uint32_t)(g < GHR_EVAL_MAX_GROUPS ? g : GHR_EVAL_MAX_GROUPS);
 }
-
-#if defined(__HIP_DEVICE_COMPILE__)
-// Four consecutive pixels of a plane: one 16-B load (VEC: H*W % 4 == 0 and a 16-B aligned plane) or four 4-B loads with the
-// image's end checked (what lies past it reads 0 and is not summed)
-template <bool VEC>
-__device__ __forceinline__ void load_quad(const float* plane, size_t p0, size_t N, float* v)
-{
-    if (VEC) {
-        const f4 t = *reinterpret_cast<const f4*>(plane + p0);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; j++) v[j] = p0 + j < N ? plane[p0 + j] : 0.f;
-    }
-}
-#endif
 
 // grid eval_point_groups(W, H), block 256.  A thread takes the quads (four consecutive pixels) t, t + T, ... of the image and
 // adds their pixels' terms in pixel order, so the scalar form (any pointers, any size; it also takes the tail quad) and the

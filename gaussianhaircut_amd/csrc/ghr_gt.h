@@ -11,6 +11,9 @@
 //   k_gt_assemble     x / 255 and x / 180 through host-divided tables, the mask threshold, the white background, the bilinear
 //                     sample of the variance map and conf = 1 / ((v / pi^2)^2 + 1e-7) (orient_conf_of of ghr_orient.h)
 //   k_gt_resize_var   the bilinear sample alone (what the tests compare with F.interpolate)
+//   k_gt_from_render  load_synthetic_rgba + load_synthetic_geom at -r 1 (camera_utils.py:51-64): the four tensors straight from the
+//                     packed [10,H,W] render -- the levels render_set would have written as PNGs (product_core of ghr_products.h),
+//                     every one / 255 through the table, the same mask rule and composite, the masked confidence as it is
 // The host computes the coefficients in double exactly as Pillow's precompute_coeffs / normalize_coeffs_8bpc do; the kernels do
 // the integer part: 22 fractional bits, a 32-bit accumulator that starts at 1 << 21, an arithmetic shift and a clip to 0 ... 255.
 // The intermediate between the two passes is uint8, as Pillow's is.  No atomics, no float in the resize: the same bytes run
@@ -19,6 +22,7 @@
 #pragma once
 #include "ghr_device.h"
 #include "ghr_orient.h"
+#include "ghr_products.h"
 
 namespace ghr {
 
@@ -258,18 +262,29 @@ struct GtAssembleArgs {
     float* out_conf;           // [1][H][W] or NULL
 };
 
+// image, mask_hair, mask_body of one pixel from its five bytes: what k_gt_assemble and k_gt_from_render share
+struct GtPix { float image[3], hair, body; };
+GHR_HD GtPix gt_assemble_pixel(const uint8_t* rgb, uint8_t hair, uint8_t body, const float* div255, int binarize, float white)
+{
+    GtPix o;
+    o.hair = gt_mask_value(hair, div255, binarize);
+    o.body = gt_mask_value(body, div255, binarize);
+#pragma unroll
+    for (int c = 0; c < 3; c++) o.image[c] = gt_image_value(div255[rgb[c]], o.body, white);
+    return o;
+}
+
 __global__ __launch_bounds__(256) void k_gt_assemble(GtAssembleArgs a)
 {
     const size_t N = (size_t)a.W * a.H;
     const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= N) return;
-    const float hair = gt_mask_value(a.mask_hair[p], a.div255, a.binarize);
-    const float body = gt_mask_value(a.mask_body[p], a.div255, a.binarize);
-    const float white = a.white ? 1.f : 0.f;
+    const uint8_t rgb[3] = {a.image[3 * p], a.image[3 * p + 1], a.image[3 * p + 2]};
+    const GtPix o = gt_assemble_pixel(rgb, a.mask_hair[p], a.mask_body[p], a.div255, a.binarize, a.white ? 1.f : 0.f);
 #pragma unroll
-    for (int c = 0; c < 3; c++) a.out_image[c * N + p] = gt_image_value(a.div255[a.image[3 * p + c]], body, white);
-    a.out_mask[p] = hair;
-    a.out_mask[N + p] = body;
+    for (int c = 0; c < 3; c++) a.out_image[c * N + p] = o.image[c];
+    a.out_mask[p] = o.hair;
+    a.out_mask[N + p] = o.body;
     if (a.angle) a.out_angle[p] = gt_angle_value(a.angle[p], a.div180);
     if (a.var) {
         const int y = (int)(p / a.W), x = (int)(p - (size_t)y * a.W);
@@ -283,6 +298,78 @@ __global__ __launch_bounds__(256) void k_gt_resize_var(int W, int H, const float
     if (p >= (size_t)W * H) return;
     const int y = (int)(p / W), x = (int)(p - (size_t)y * W);
     out[p] = gt_var_sample(var, vw, vh, W, H, x, y, via_half);
+}
+
+// ---- synthetic ground truth --------------------------------------------------------------------------------------------------
+
+// One pixel of camera_utils.py:51-64 + cameras.py:51-64 at -r 1.  render_set quantises render, hair mask, head mask and
+// angle * hair to bytes (product_core) and saves orient_conf * hair as a float; loadCam reads every PNG back through PILtoTorch's
+// default max_value: byte / 255, the angle too (the clamp of cameras.py:55 holds for every table value); the confidence goes
+// through F.interpolate alone, which at equal size returns the plane's own (finite) values.
+struct GtSynthPix { GtPix v; float angle, conf; };
+GHR_HD GtSynthPix gt_from_render_pixel(const float* rgb, float m0, float m1, float d0, float d1, float conf, const float* div255,
+                                       int binarize, float white)
+{
+    const ProductCore k = product_core(rgb, m0, m1, d0, d1, conf);
+    const uint8_t b[3] = {(uint8_t)k.render[0], (uint8_t)k.render[1], (uint8_t)k.render[2]};
+    GtSynthPix o;
+    o.v = gt_assemble_pixel(b, (uint8_t)k.hair, (uint8_t)k.head, div255, binarize, white);
+    o.angle = div255[k.orient];
+    o.conf = k.conf;
+    return o;
+}
+
+struct GtFromRenderArgs {
+    int W, H;
+    const float* renders;  // [10,H,W] packed: rgb 0-2, hair 3, head 4, dir2d 5-6, orientation confidence 8
+    const float* div255;   // [256]
+    int white, binarize;
+    float* out_image;      // [3][H][W]
+    float* out_mask;       // [2][H][W]: hair, body
+    float* out_angle;      // [1][H][W]
+    float* out_conf;       // [1][H][W]
+};
+
+// grid ceil(ceil(H W / 4) / 256), block 256; a thread makes four consecutive pixels: eight planes in, seven out, 60 B a pixel.
+// VEC (H*W % 4 == 0, every pointer 16-B aligned): float4 loads and stores; otherwise single ones with the end checked.  The table
+// is staged in LDS: six look-ups per pixel at addresses the render decides.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_gt_from_render(GtFromRenderArgs a)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ float s_div255[256];
+    s_div255[threadIdx.x] = a.div255[threadIdx.x];
+    __syncthreads();
+    const size_t N = (size_t)a.W * a.H, quads = (N + 3) / 4;
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= quads) return;
+    const size_t p0 = 4 * q;
+    float r[8][4];
+#pragma unroll
+    for (int k = 0; k < 7; k++) load_quad<VEC>(a.renders + (size_t)k * N, p0, N, r[k]);
+    load_quad<VEC>(a.renders + (size_t)8 * N, p0, N, r[7]);
+    const float white = a.white ? 1.f : 0.f;
+    float o[7][4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const float rgb[3] = {r[0][j], r[1][j], r[2][j]};
+        const GtSynthPix g = gt_from_render_pixel(rgb, r[3][j], r[4][j], r[5][j], r[6][j], r[7][j], s_div255, a.binarize, white);
+        o[0][j] = g.v.image[0]; o[1][j] = g.v.image[1]; o[2][j] = g.v.image[2];
+        o[3][j] = g.v.hair; o[4][j] = g.v.body;
+        o[5][j] = g.angle; o[6][j] = g.conf;
+    }
+    float* dst[7] = {a.out_image, a.out_image + N, a.out_image + 2 * N, a.out_mask, a.out_mask + N, a.out_angle, a.out_conf};
+#pragma unroll
+    for (int k = 0; k < 7; k++) {
+        if (VEC) {
+            *reinterpret_cast<f4*>(dst[k] + p0) = f4{o[k][0], o[k][1], o[k][2], o[k][3]};
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (p0 + j < N) dst[k][p0 + j] = o[k][j];
+        }
+    }
+#endif
 }
 
 }  // namespace ghr

@@ -15,8 +15,14 @@ in float64 exactly as Pillow does, and the rest is integer work -- the kernels o
 (``fused=None`` / ``True``), or the same arithmetic composed from torch integer operations (``fused=False``, the comparator,
 CPU and device).  Both give Pillow's bytes.  numpy in, numpy out; tensor in, tensor out on the tensor's device.
 
-Not built: RGBA (Pillow premultiplies alpha), other dtypes, other filters, file formats, COLMAP, ``Scene``,
-``load_synthetic_*`` and depth.  The module needs no Pillow.
+Synthetic ground truth (``--load_synthetic_rgba --load_synthetic_geom``, ``camera_utils.py:51-64``): the strand stages train on
+what ``render_gaussians.py`` wrote from the stage-1 model, read back with everything ``/ 255`` and the confidence plane as it is.
+``synthetic_view_ground_truth`` is that reader on arrays; ``ground_truth_from_render`` is the whole chain -- render, quantise,
+write, read, divide, composite -- from the packed rasterizer output, one launch of ``k_gt_from_render`` at the render's size;
+``attach_synthetic_ground_truth`` fills cameras with it.
+
+Not built: RGBA (Pillow premultiplies alpha), other dtypes, other filters, file formats, COLMAP, ``Scene`` and depth.  The module
+needs no Pillow.
 """
 from __future__ import annotations
 
@@ -291,30 +297,38 @@ def assemble_fused(image, mask_hair, mask_body, angle=None, var=None, white_back
     """ONE launch of ``k_gt_assemble`` on the current stream from uint8 tensors at the training size (``var`` float32 at its
     own): ``(image [3,H,W], mask [2,H,W], angle [1,H,W] | None, conf [1,H,W] | None)``.  ``fill``: a byte the outputs are
     pre-filled with (tests)."""
+    return _assemble_launch(image, mask_hair, mask_body, angle, var, white_background, binarize_masks, via_float16, fill, 180)
+
+
+def _new_planes(c, H, W, dev, fill):
+    t = torch.empty((c, H, W), dtype=torch.float32, device=dev)
+    if fill is not None:
+        t.view(torch.uint8).fill_(fill)
+    return t
+
+
+def _assemble_launch(image, mask_hair, mask_body, angle, var, white_background, binarize_masks, via_float16, fill, angle_max):
+    """``assemble_fused`` with the angle's divisor chosen: 180 for the orientation files, 255 for a rendered ``orients`` image"""
     assert image.is_cuda, "the assembly kernel has no CPU path (fused=False is the torch form)"
     H, W = int(image.shape[0]), int(image.shape[1])
     dev = image.device
     t255, t180 = _tables(dev)
+    t_angle = t255 if angle_max == 255 else t180
     guard, _ptr, _stream = _launch_env(image)
     with guard:
-        def new(c):
-            t = torch.empty((c, H, W), dtype=torch.float32, device=dev)
-            if fill is not None:
-                t.view(torch.uint8).fill_(fill)
-            return t
-        o_img, o_mask = new(3), new(2)
-        o_ang = new(1) if angle is not None else None
-        o_conf = new(1) if var is not None else None
+        o_img, o_mask = _new_planes(3, H, W, dev, fill), _new_planes(2, H, W, dev, fill)
+        o_ang = _new_planes(1, H, W, dev, fill) if angle is not None else None
+        o_conf = _new_planes(1, H, W, dev, fill) if var is not None else None
         vw, vh = (int(var.shape[1]), int(var.shape[0])) if var is not None else (0, 0)
         _lib.check(_lib.lib().ghr_gt_assemble(_stream(), W, H, _ptr(image), _ptr(mask_hair), _ptr(mask_body),
                                               _ptr(angle) if angle is not None else None, _ptr(var) if var is not None else None, vw, vh,
-                                              _ptr(t255), _ptr(t180), int(bool(white_background)), int(bool(binarize_masks)),
+                                              _ptr(t255), _ptr(t_angle), int(bool(white_background)), int(bool(binarize_masks)),
                                               int(bool(via_float16)), _ptr(o_img), _ptr(o_mask),
                                               _ptr(o_ang) if angle is not None else None, _ptr(o_conf) if var is not None else None))
     return o_img, o_mask, o_ang, o_conf
 
 
-def _assemble_torch(image, mask_hair, mask_body, angle, var, white_background, binarize_masks, via_float16):
+def _assemble_torch(image, mask_hair, mask_body, angle, var, white_background, binarize_masks, via_float16, angle_max=180):
     """loadCam's tail and Camera.__init__ in the reference's order of operations"""
     dev = image.device
     t255, t180 = _tables(dev)
@@ -327,7 +341,7 @@ def _assemble_torch(image, mask_hair, mask_body, angle, var, white_background, b
     hair, body = mask(mask_hair), mask(mask_body)
     white = 1.0 if white_background else 0.0
     o_img = img.clamp(0.0, 1.0) * body.clamp(0.0, 1.0) + white * (1 - body.clamp(0.0, 1.0))
-    o_ang = t180[angle.long()][None].clamp(0.0, 1.0) if angle is not None else None
+    o_ang = (t255 if angle_max == 255 else t180)[angle.long()][None].clamp(0.0, 1.0) if angle is not None else None
     o_conf = None
     if var is not None:
         v = var.to(torch.float16).float() if via_float16 else var.float()
@@ -347,19 +361,43 @@ def _plane(t, what):
     return t.contiguous()
 
 
+def _conf_plane(c, dev, what):
+    """``orient_confs/*.pth``: float [H,W] or [1,H,W] -> float32 [H,W] on ``dev``"""
+    c = _as_tensor(c)[0].to(dev)
+    if c.dim() == 3 and c.shape[0] == 1:
+        c = c[0]
+    if c.dim() != 2 or not c.is_floating_point():
+        raise ValueError("%s: orient_conf must be a float [H,W] or [1,H,W], got %s %s" % (what, str(c.dtype).replace("torch.", ""), tuple(c.shape)))
+    return c.float().contiguous()
+
+
+def _fit_conf(conf, w, h, k):
+    """camera_utils.py:64: ``F.interpolate(conf, mode='bilinear')`` alone -- at equal size the plane's own values"""
+    if (int(conf.shape[1]), int(conf.shape[0])) == (w, h):
+        return conf.clone()[None]
+    return resize_variance(conf, (w, h), via_float16=False, fused=k)[None]
+
+
 def view_ground_truth(image, mask_hair, mask_body, angle=None, var=None, resolution=None, white_background: bool = False,
                       binarize_masks: bool = False, via_float16: bool = True, fused: Optional[bool] = None,
-                      resolution_scale: float = 1.0) -> ViewGroundTruth:
+                      resolution_scale: float = 1.0, *, orient=None, orient_conf=None) -> ViewGroundTruth:
     """One view's tensors as ``loadCam`` + ``Camera`` build them.  ``image`` uint8 [H,W,3]; ``mask_hair`` / ``mask_body`` uint8
     [H,W]; ``angle`` uint8 [H,W] (degrees 0 ... 179) and ``var`` [vh,vw] the two orientation files -- when either is absent both are
     computed from ``image`` at its own size (orientation.dog_fused / gabor_fused), then resized like files would be.
     ``resolution``: None (the image's size), ``(w, h)``, or loadCam's ``-r`` (1 | 2 | 4 | 8 | a width | -1).  Everything that
     differs from the training size is resized (Pillow's bicubic for the bytes, bilinear for the variance), then assembled: on a
-    ROCm tensor at most two launches per resized input and one for the assembly.  numpy in, numpy out."""
+    ROCm tensor at most two launches per resized input and one for the assembly.  numpy in, numpy out.
+    ``orient`` uint8 [H,W] and ``orient_conf`` float [H,W] instead of ``angle`` / ``var``: ``load_synthetic_geom`` on a
+    photograph -- the rendered ``orients`` image ``/ 255`` and the rendered confidence through the bilinear resize alone."""
     t, was_numpy = _as_tensor(image)
     t = _check_u8(t, "view_ground_truth")
     if t.dim() != 3 or t.shape[2] != 3:
         raise ValueError("view_ground_truth: image must be [H,W,3], got %s" % (tuple(t.shape),))
+    synth = orient is not None or orient_conf is not None
+    if synth and (orient is None or orient_conf is None):
+        raise ValueError("view_ground_truth: orient and orient_conf come together")
+    if synth and (angle is not None or var is not None):
+        raise ValueError("view_ground_truth: give angle / var (the orientation files) or orient / orient_conf (rendered), not both")
     dev = t.device
     H0, W0 = int(t.shape[0]), int(t.shape[1])
     if resolution is None:
@@ -372,7 +410,11 @@ def view_ground_truth(image, mask_hair, mask_body, angle=None, var=None, resolut
     planes = []
     for m, what in ((mask_hair, "mask_hair"), (mask_body, "mask_body")):
         planes.append(_plane(_check_u8(_as_tensor(m)[0].to(dev), "view_ground_truth"), what))
-    if angle is None or var is None:
+    conf_t = None
+    if synth:
+        ang_t = _plane(_check_u8(_as_tensor(orient)[0].to(dev), "view_ground_truth"), "orient")
+        conf_t, var_t = _conf_plane(orient_conf, dev, "view_ground_truth"), None
+    elif angle is None or var is None:
         if k:
             deg, v = ori.gabor_fused(ori.dog_fused(t))
         else:
@@ -392,9 +434,13 @@ def view_ground_truth(image, mask_hair, mask_body, angle=None, var=None, resolut
         return resize_u8_fused(x, w, h) if k else _resize_torch(x, w, h)
     img, hair, body, ang = fit(t), fit(planes[0]), fit(planes[1]), fit(ang_t)
     if k:
-        o_img, o_mask, o_ang, o_conf = assemble_fused(img, hair, body, ang, var_t, white_background, binarize_masks, via_float16)
+        o_img, o_mask, o_ang, o_conf = _assemble_launch(img, hair, body, ang, var_t, white_background, binarize_masks, via_float16, None,
+                                                        255 if synth else 180)
     else:
-        o_img, o_mask, o_ang, o_conf = _assemble_torch(img, hair, body, ang, var_t, white_background, binarize_masks, via_float16)
+        o_img, o_mask, o_ang, o_conf = _assemble_torch(img, hair, body, ang, var_t, white_background, binarize_masks, via_float16,
+                                                       255 if synth else 180)
+    if synth:
+        o_conf = _fit_conf(conf_t, w, h, k)
     res = (o_img, o_mask, o_ang, o_conf, o_mask[0:1], o_mask[1:2])
     return ViewGroundTruth(*(_out(x, was_numpy) for x in res))
 
@@ -418,4 +464,118 @@ def attach_ground_truth(cams: Sequence, views: Sequence, resolution=None, white_
         as_t = lambda x: torch.from_numpy(x) if isinstance(x, np.ndarray) else x   # noqa: E731
         cam.original_image, cam.original_mask = as_t(gt.original_image), as_t(gt.original_mask)
         cam.original_orient_angle, cam.original_orient_conf = as_t(gt.original_orient_angle), as_t(gt.original_orient_conf)
+    return list(cams)
+
+
+# ---- synthetic ground truth ------------------------------------------------------------------------------------------------------------
+
+def synthetic_view_ground_truth(render, head_mask, hair_mask, orient=None, orient_conf=None, angle=None, var=None, size=None,
+                                white_background: bool = False, binarize_masks: bool = False, fused: Optional[bool] = None) -> ViewGroundTruth:
+    """``loadCam`` with ``load_synthetic_rgba`` on the arrays of ``<model>/train_cropped/ours_<it>/``: ``render`` uint8 [H,W,3]
+    (``renders``), ``head_mask`` / ``hair_mask`` uint8 [H,W] or [H,W,3] (``head_masks``, ``hair_masks``; channel 0 is used).
+    With ``orient`` uint8 (``orients``) and ``orient_conf`` float [H,W] or [1,H,W] (``orient_confs``) it is ``load_synthetic_geom``
+    too: the angle is ``orient / 255`` and the confidence the plane itself, through ``F.interpolate(mode='bilinear')`` alone.  With
+    ``angle`` and ``var`` instead (the orientation files of the photograph) it is ``load_synthetic_rgba`` alone: ``/ 180``,
+    float16, ``1 / ((v / pi^2)^2 + 1e-7)``.  ``size``: None (the render's) or the ``(w, h)`` the caller got from
+    ``training_resolution`` on the ORIGINAL photograph's size, as loadCam does; everything else is resized.  numpy in, numpy out."""
+    geom, files = (orient is not None, orient_conf is not None), (angle is not None, var is not None)
+    if geom[0] != geom[1] or files[0] != files[1]:
+        raise ValueError("synthetic_view_ground_truth: orient comes with orient_conf, angle with var")
+    if geom[0] == files[0]:
+        raise ValueError("synthetic_view_ground_truth: give orient / orient_conf (load_synthetic_geom) or angle / var (the "
+                         "orientation files), one pair")
+    resolution = None if size is None else _size(size)
+    if geom[0]:
+        return view_ground_truth(render, hair_mask, head_mask, resolution=resolution, white_background=white_background,
+                                 binarize_masks=binarize_masks, fused=fused, orient=orient, orient_conf=orient_conf)
+    return view_ground_truth(render, hair_mask, head_mask, angle, var, resolution=resolution, white_background=white_background,
+                             binarize_masks=binarize_masks, via_float16=True, fused=fused)
+
+
+def _core_products_torch(packed):
+    """The five products the synthetic branch reads, as ``evaluation.products_torch`` forms and quantises them, kept on ``packed``'s
+    device: uint8 render [H,W,3], hair, head, orient [H,W] and float32 conf [H,W]"""
+    from .evaluation import quantise8
+    from .gaussian_renderer import orient_angle_from
+    image, hair, head, conf = packed[0:3], packed[3:4], packed[4:5], packed[8:9]
+    angle = orient_angle_from(packed[5:8])
+    return (quantise8(image).contiguous(), quantise8(hair)[:, :, 0].contiguous(), quantise8(head)[:, :, 0].contiguous(),
+            quantise8(angle * hair)[:, :, 0].contiguous(), (conf * hair)[0].float().contiguous())
+
+
+def core_products_fused(packed):
+    """``evaluation.products_fused`` and the five planes of its block the synthetic branch reads (views into the block)"""
+    from .evaluation import products_fused
+    _, H, W = packed.shape
+    n = H * W
+    block = products_fused(packed)
+    return (block[:3 * n].view(H, W, 3), block[3 * n:4 * n].view(H, W), block[4 * n:5 * n].view(H, W), block[5 * n:6 * n].view(H, W),
+            block[12 * n:16 * n].view(torch.float32).view(H, W))
+
+
+def from_render_fused(packed, white_background=False, binarize_masks=False, fill=None):
+    """ONE launch of ``k_gt_from_render`` on the current stream: ``(image [3,H,W], mask [2,H,W], angle [1,H,W], conf [1,H,W])`` from
+    the packed [10,H,W] render.  ``fill``: a byte the outputs are pre-filled with (tests)."""
+    assert packed.is_cuda, "the synthetic ground-truth kernel has no CPU path (fused=False is the torch form)"
+    C, H, W = (int(x) for x in packed.shape)
+    assert C == _lib.NUM_CHANNELS
+    r = packed.detach().float().contiguous()
+    dev = r.device
+    t255, _ = _tables(dev)
+    guard, _ptr, _stream = _launch_env(r)
+    with guard:
+        outs = tuple(_new_planes(c, H, W, dev, fill) for c in (3, 2, 1, 1))
+        _lib.check(_lib.lib().ghr_gt_from_render(_stream(), W, H, _ptr(r), _ptr(t255), int(bool(white_background)),
+                                                 int(bool(binarize_masks)), *(_ptr(o) for o in outs)))
+    return outs
+
+
+def ground_truth_from_render(packed, size=None, white_background: bool = False, binarize_masks: bool = False,
+                             fused: Optional[bool] = None) -> ViewGroundTruth:
+    """What ``loadCam`` builds with ``load_synthetic_rgba`` and ``load_synthetic_geom`` from the files ``render_gaussians.py`` would
+    write for this render, without the files: ``packed`` is the [10,H,W] rasterizer output (``render(...).renders_packed``), finite.
+    ``size`` None or ``(W, H)``: on a ROCm tensor ONE launch.  Another ``(w, h)`` (the caller's ``training_resolution`` of the
+    original photograph's size): the products on the device, the four byte planes through ``resize_u8``, the assembly with the
+    angle ``/ 255``, the confidence through the bilinear resize.  ``fused=False``: ``evaluation.products_torch``'s values and the
+    torch assembly, on CPU tensors too."""
+    t, was_numpy = _as_tensor(packed)
+    if t.dim() != 3 or t.shape[0] != _lib.NUM_CHANNELS or t.shape[1] < 1 or t.shape[2] < 1:
+        raise ValueError("ground_truth_from_render: packed must be [%d,H,W], got %s" % (_lib.NUM_CHANNELS, tuple(t.shape)))
+    H, W = int(t.shape[1]), int(t.shape[2])
+    w, h = (W, H) if size is None else _size(size)
+    k = _use_kernels(t, fused)
+    if k and (w, h) == (W, H):
+        o_img, o_mask, o_ang, o_conf = from_render_fused(t, white_background, binarize_masks)
+    else:
+        img, hair, head, orient, conf = core_products_fused(t) if k else _core_products_torch(t.float())
+        if (w, h) != (W, H):
+            img, hair, head, orient = ((resize_u8_fused(x, w, h) if k else _resize_torch(x, w, h)) for x in (img, hair, head, orient))
+        if k:
+            o_img, o_mask, o_ang, _ = _assemble_launch(img, hair, head, orient, None, white_background, binarize_masks, False, None, 255)
+        else:
+            o_img, o_mask, o_ang, _ = _assemble_torch(img, hair, head, orient, None, white_background, binarize_masks, False, 255)
+        o_conf = _fit_conf(conf, w, h, k)
+    res = (o_img, o_mask, o_ang, o_conf, o_mask[0:1], o_mask[1:2])
+    return ViewGroundTruth(*(_out(x, was_numpy) for x in res))
+
+
+@torch.no_grad()
+def attach_synthetic_ground_truth(cams: Sequence, gaussians, background, pipe=None, gaussians_hair=None, white_background: bool = False,
+                                  binarize_masks: bool = False, fused: Optional[bool] = None) -> List:
+    """The strand stages' ``--load_synthetic_rgba --load_synthetic_geom`` at ``-r 1``: renders every camera (``Camera``,
+    ``BankCamera``) with ``render``, or ``render_hair`` when ``gaussians_hair`` is given, and fills its ``original_image`` /
+    ``original_mask`` / ``original_orient_angle`` / ``original_orient_conf`` with ``ground_truth_from_render`` of that render:
+    28 B per pixel per view stay on the device, nothing goes through the host.  The tensors are new ones (the cameras' previous
+    ones are not written), so what is cached per ground-truth tensor (trainer._gt_stats) is recomputed."""
+    from .evaluation import _default_pipe, _render_view
+    pipe = _default_pipe() if pipe is None else pipe
+    for cam in cams:
+        pkg = _render_view(cam, gaussians, gaussians_hair, pipe, background)
+        gt = ground_truth_from_render(pkg.renders_packed, None, white_background, binarize_masks, fused)
+        got = tuple(gt.original_image.shape[1:])
+        if got != (cam.image_height, cam.image_width):
+            raise ValueError("attach_synthetic_ground_truth: a render of %d x %d (h x w) for a %d x %d camera"
+                             % (got + (cam.image_height, cam.image_width)))
+        cam.original_image, cam.original_mask = gt.original_image, gt.original_mask
+        cam.original_orient_angle, cam.original_orient_conf = gt.original_orient_angle, gt.original_orient_conf
     return list(cams)

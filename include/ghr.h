@@ -688,6 +688,20 @@ int ghr_gt_assemble(void* stream, int32_t W, int32_t H, const uint8_t* image, co
 int ghr_gt_resize_variance(void* stream, int32_t W, int32_t H, const float* var, int32_t var_w, int32_t var_h, int32_t via_half,
                            float* out);
 
+/* ---- synthetic ground truth (src/utils/camera_utils.py:51-64 with load_synthetic_rgba and load_synthetic_geom, at -r 1)
+ * Added without an ABI_VERSION bump: one new function, no existing struct or signature changed.
+ * ghr_gt_from_render: one launch from the packed render [10][H][W] (channels 0-6 and 8 are read) to the four tensors the
+ * reference builds by writing render_set's products to disk and reading them back.  Per pixel, with q(v) = the 8-bit level
+ * uint8(clamp(v * 255 + 0.5, 0, 255)) of torchvision's save_image and t = div255_table (256 device floats i / 255 divided on the
+ * host): hair = t[q(r3)], body = t[q(r4)], or (level >= 128) when binarize; out_image [3][H][W] = t[q(r_c)] * body +
+ * white_background * (1 - body); out_mask [2][H][W] = hair, body; out_angle [1][H][W] = t[q(angle * r3)], angle the orientation
+ * angle / pi of (r5, r6) as ghr_eval_products forms it; out_conf [1][H][W] = r8 * r3, not clamped.  The levels are those
+ * ghr_eval_products writes; image and masks are what ghr_gt_assemble makes of them.  Renders must be finite.  Four pixels per
+ * thread with 16-B accesses when H * W % 4 == 0 and all five buffers are 16-B aligned, single accesses otherwise: the same bits
+ * either way, run after run.  A refused call launches nothing. */
+int ghr_gt_from_render(void* stream, int32_t W, int32_t H, const float* renders, const float* div255_table, int32_t white_background,
+                       int32_t binarize, float* out_image, float* out_mask, float* out_angle, float* out_conf);
+
 /* ---- the latent-strand stage (src/train_latent_strands.py:103-164; src/scene/gaussian_model_latent_strands.py:451-499)
  * Added without an ABI_VERSION bump: seven new functions and one new struct, no existing struct or signature changed.
  * ghr_strand_points_build: strands given as POINTS p [S][L][3], L >= 2 (no upper bound), n_seg = L - 1; row s n_seg + k is
