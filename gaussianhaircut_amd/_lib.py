@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GHR_LIB_PATH") or os.path.join(CSRC, "libghr_hip.so")  # override: kernel experiments
 SOURCES = ["ghr_capi.hip"]
 HEADERS = ["ghr_device.h", "ghr_preprocess.h", "ghr_binning.h", "ghr_render_fwd.h", "ghr_render_bwd.h", "ghr_render_bwd2.h", "ghr_render_bwd3.h",
-           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_products.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_visibility.h", "ghr_sds.h", "ghr_nn.h"]
+           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_products.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_visibility.h", "ghr_strandview.h", "ghr_sds.h", "ghr_nn.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-fPIC",
                "-shared"]
 
@@ -178,6 +178,14 @@ class MeshGrid(ctypes.Structure):
 
 
 PROBE_REFERENCE, PROBE_AXIS_SCALED = 0, 1  # GHR_PROBE_*
+STRANDVIEW_KAJIYA, STRANDVIEW_TANGENT = 0, 1  # GHR_STRANDVIEW_*
+
+
+class StrandViewShading(ctypes.Structure):
+    """``ghr_strandview_shading`` (include/ghr.h)."""
+    _fields_ = [("eye", ctypes.c_float * 3), ("light", ctypes.c_float * 3), ("ambient", ctypes.c_float), ("kd", ctypes.c_float),
+                ("ks", ctypes.c_float), ("shininess_log2", ctypes.c_int32), ("base_rgb", ctypes.c_float * 3),
+                ("head_rgb", ctypes.c_float * 3), ("background_rgb", ctypes.c_float * 3)]
 
 
 def latent_loss_sums_floats(W: int, H: int) -> int:
@@ -212,6 +220,8 @@ EXPORTS = ["ghr_last_error", "ghr_abi_version", "ghr_forward_sizes", "ghr_binnin
            "ghr_model_forward_segment_shared", "ghr_model_backward_segment_shared", "ghr_shared_sh_fold",
            "ghr_mesh_grid_sizes", "ghr_mesh_grid_build", "ghr_mesh_contains", "ghr_gaussian_probe_outside",
            "ghr_vis_sizes", "ghr_vis_view", "ghr_vis_head_mask",
+           "ghr_strandview_sizes", "ghr_strandview_face_depth", "ghr_strandview_raster", "ghr_strandview_shade",
+           "ghr_strandview_resolve",
            "ghr_sds_local", "ghr_sds_local_backward", "ghr_sds_texture", "ghr_sds_texture_backward",
            "ghr_nn_workspace_size", "ghr_nn_search", "ghr_chamfer_point", "ghr_chamfer_point_backward"]
 
@@ -314,6 +324,12 @@ def lib() -> ctypes.CDLL:
     L.ghr_vis_sizes.argtypes = [i32, i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
     L.ghr_vis_view.argtypes = [vp, i32, vp, i32, vp, ctypes.POINTER(ctypes.c_float * 12), f32, i32, i32] + [vp] * 7
     L.ghr_vis_head_mask.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.ghr_strandview_sizes.argtypes = [i32, i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
+    L.ghr_strandview_face_depth.argtypes = [vp, i32, vp, i32, vp, ctypes.POINTER(ctypes.c_float * 12), f32, i32, i32, vp, vp]
+    L.ghr_strandview_raster.argtypes = [vp, i32, i32, vp, ctypes.POINTER(ctypes.c_float * 12), f32, i32, i32, f32, f32] + [vp] * 7
+    L.ghr_strandview_shade.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32,
+                                       ctypes.POINTER(StrandViewShading), vp, vp]
+    L.ghr_strandview_resolve.argtypes = [vp, i32, i32, i32, vp, vp]
     L.ghr_sds_local.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, f32, vp, vp]
     L.ghr_sds_local_backward.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, f32, vp, vp, vp]
     L.ghr_sds_texture.argtypes = [vp, i32, i32, i32, i32] + [vp] * 13

@@ -34,6 +34,7 @@
 #include "ghr_shared.h"
 #include "ghr_mesh.h"
 #include "ghr_visibility.h"
+#include "ghr_strandview.h"
 #include "ghr_sds.h"
 
 namespace {
@@ -2201,6 +2202,148 @@ int ghr_vis_view(void* stream, int32_t V, const float* vertices, int32_t F, cons
         hipLaunchKernelGGL(ghr::k_vis_raster, dim3((unsigned)L.tiles_x, (unsigned)L.tiles_y), dim3(GHR_VIS_BLOCK), 0, s, a);
         if (V && F && cnt) hipLaunchKernelGGL(ghr::k_vis_accumulate, dim3(vis_blocks(V)), dim3(GHR_VIS_BLOCK), 0, s, a);
     }
+    return finish(s, 0);
+}
+
+}  // extern "C"
+
+// ---- the strand preview (include/ghr.h; csrc/ghr_strandview.h) ---------------------------------------------------------------
+namespace {
+inline unsigned sv_blocks(uint64_t n) { return (unsigned)((n + GHR_SV_BLOCK - 1) / GHR_SV_BLOCK); }
+inline bool al4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
+static_assert(sizeof(ghr_strandview_shading) == sizeof(ghr::SvShading), "ghr_strandview_shading is ghr::SvShading");
+static_assert(GHR_STRANDVIEW_KAJIYA == GHR_SV_KAJIYA && GHR_STRANDVIEW_TANGENT == GHR_SV_TANGENT, "the modes of include/ghr.h");
+}  // namespace
+
+extern "C" {
+
+int ghr_strandview_sizes(int32_t S, int32_t L, int32_t H, int32_t W, size_t* bytes)
+{
+    static const char* fn = "ghr_strandview_sizes: %s";
+    if (!bytes) return lt_bad(fn, "bytes is NULL");
+    ghr::SvLayout Y;
+    if (const char* why = ghr::sv_layout(S, L, H, W, &Y)) return lt_bad(fn, why);
+    *bytes = (size_t)Y.bytes;
+    return GHR_OK;
+}
+
+int ghr_strandview_face_depth(void* stream, int32_t V, const float* vertices, int32_t F, const int32_t* faces, const float* M,
+                              float near_w, int32_t H, int32_t W, const int32_t* pix_to_face, float* qf)
+{
+    static const char* fn = "ghr_strandview_face_depth: %s";
+    ghr::VisLayout L;
+    if (const char* why = ghr::vis_layout(V, F, H, W, &L)) return lt_bad(fn, why);
+    if (V && !vertices) return lt_bad(fn, "vertices is NULL");
+    if (F && !faces) return lt_bad(fn, "faces is NULL");
+    if (!M) return lt_bad(fn, "M is NULL");
+    if (!(near_w >= 0.f)) return lt_bad(fn, "near is negative or NaN");
+    const uint64_t N = (uint64_t)H * (uint64_t)W;
+    if (N == 0) return GHR_OK;
+    if (!pix_to_face) return lt_bad(fn, "pix_to_face is NULL");
+    if (!qf) return lt_bad(fn, "qf is NULL");
+    if (!al4(vertices) || !al4(faces) || !al4(pix_to_face) || !al4(qf)) return lt_bad(fn, "a buffer is not 4-B aligned");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::SvFaceDepthArgs a{};
+    a.V = V; a.F = F; a.H = H; a.W = W; a.near = near_w;
+    for (int k = 0; k < 12; k++) a.M[k] = M[k];
+    a.vertices = vertices; a.faces = faces; a.pix_to_face = pix_to_face; a.qf = qf;
+    hipLaunchKernelGGL(ghr::k_sv_face_depth, dim3(sv_blocks(N)), dim3(GHR_SV_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+int ghr_strandview_raster(void* stream, int32_t S, int32_t L, const float* points, const float* M, float near_w, int32_t H,
+                          int32_t W, float half_width, float head_bias, const int32_t* pix_to_face, const float* qf,
+                          void* workspace, int32_t* pix_to_segment, float* t, int32_t* pix_to_face_out, float* inv_depth)
+{
+    static const char* fn = "ghr_strandview_raster: %s";
+    ghr::SvLayout Y;
+    if (const char* why = ghr::sv_layout(S, L, H, W, &Y)) return lt_bad(fn, why);
+    if (S && !points) return lt_bad(fn, "points is NULL");
+    if (!M) return lt_bad(fn, "M is NULL");
+    if (!(near_w >= 0.f)) return lt_bad(fn, "near is negative or NaN");
+    if (!(ghr::vis_finite(half_width) && half_width > 0.f)) return lt_bad(fn, "half_width is not finite and > 0");
+    if (!(ghr::vis_finite(head_bias) && head_bias >= 0.f)) return lt_bad(fn, "head_bias is negative or not finite");
+    if ((pix_to_face == nullptr) != (qf == nullptr)) return lt_bad(fn, "pix_to_face and qf must be given or NULL together");
+    if (!workspace) return lt_bad(fn, "workspace is NULL");
+    if (!al16(workspace)) return lt_bad(fn, "workspace is not 16-B aligned (the segment records are read 16 B at a time)");
+    const bool pixels = (int64_t)H * W > 0;
+    if (pixels && (!pix_to_segment || !t || !pix_to_face_out || !inv_depth)) return lt_bad(fn, "an output plane is NULL");
+    if (!al4(points) || !al4(pix_to_face) || !al4(qf) || !al4(pix_to_segment) || !al4(t) || !al4(pix_to_face_out) || !al4(inv_depth))
+        return lt_bad(fn, "a buffer is not 4-B aligned");
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace);
+    ghr::SvArgs a{};
+    a.S = S; a.L = L; a.H = H; a.W = W; a.tiles_x = Y.tiles_x; a.tiles_y = Y.tiles_y;
+    a.n_points = (uint32_t)Y.n_points; a.n_segments = (uint32_t)Y.n_segments;
+    a.near = near_w; a.r = half_width; a.head_bias = head_bias;
+    for (int k = 0; k < 12; k++) a.M[k] = M[k];
+    a.points = points; a.pix_to_face = pix_to_face; a.qf = qf;
+    a.proj = reinterpret_cast<float*>(ws + Y.off_proj);
+    a.rec = reinterpret_cast<float*>(ws + Y.off_rec);
+    a.start = reinterpret_cast<uint32_t*>(ws + Y.off_start);
+    a.count = reinterpret_cast<uint32_t*>(ws + Y.off_count);
+    a.nbig = reinterpret_cast<uint32_t*>(ws + Y.off_nbig);
+    a.list = reinterpret_cast<uint32_t*>(ws + Y.off_list);
+    a.big = reinterpret_cast<uint32_t*>(ws + Y.off_big);
+    a.list_cap = (uint32_t)Y.list_cap;
+    a.pix_to_segment = pix_to_segment; a.t = t; a.pix_to_face_out = pix_to_face_out; a.inv_depth = inv_depth;
+    if (!pixels) return GHR_OK;
+    // the tile counts and the big list's length start every frame at 0: one fill, so that a workspace needs no preparation by
+    // its owner and may change image size between frames
+    GHR_HIP(hipMemsetAsync(ws + Y.off_fill, 0, (size_t)Y.fill_bytes, s));
+    if (a.n_segments) {
+        hipLaunchKernelGGL(ghr::k_sv_project, dim3(sv_blocks(Y.n_points)), dim3(GHR_SV_BLOCK), 0, s, a);
+        hipLaunchKernelGGL(ghr::k_sv_setup, dim3(sv_blocks(Y.n_segments)), dim3(GHR_SV_BLOCK), 0, s, a);
+    }
+    hipLaunchKernelGGL(ghr::k_sv_scan, dim3(1), dim3(GHR_SV_BLOCK), 0, s, a);
+    if (a.n_segments) hipLaunchKernelGGL(ghr::k_sv_scatter, dim3(sv_blocks(Y.n_segments)), dim3(GHR_SV_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_sv_raster, dim3((unsigned)Y.tiles_x, (unsigned)Y.tiles_y), dim3(GHR_SV_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+int ghr_strandview_shade(void* stream, int32_t S, int32_t L, const float* points, int32_t V, const float* vertices, int32_t F,
+                         const int32_t* faces, int32_t H, int32_t W, const int32_t* pix_to_segment, const int32_t* pix_to_face_out,
+                         int32_t mode, const ghr_strandview_shading* shading, const float* base, uint8_t* rgb)
+{
+    static const char* fn = "ghr_strandview_shade: %s";
+    ghr::SvLayout Y;
+    if (const char* why = ghr::sv_layout(S, L, H, W, &Y)) return lt_bad(fn, why);
+    ghr::VisLayout VL;
+    if (const char* why = ghr::vis_layout(V, F, H, W, &VL)) return lt_bad(fn, why);
+    if (mode != GHR_SV_KAJIYA && mode != GHR_SV_TANGENT) return lt_bad(fn, "mode is neither GHR_STRANDVIEW_KAJIYA nor GHR_STRANDVIEW_TANGENT");
+    if (!shading) return lt_bad(fn, "shading is NULL");
+    if (shading->shininess_log2 < 0 || shading->shininess_log2 > GHR_SV_MAX_SHININESS_LOG2) return lt_bad(fn, "shininess_log2 is outside 0 .. 16");
+    if (S && !points) return lt_bad(fn, "points is NULL");
+    if (V && !vertices) return lt_bad(fn, "vertices is NULL");
+    if (F && !faces) return lt_bad(fn, "faces is NULL");
+    const uint64_t N = (uint64_t)H * (uint64_t)W;
+    if (N == 0) return GHR_OK;
+    if (!pix_to_segment || !pix_to_face_out) return lt_bad(fn, "pix_to_segment or pix_to_face_out is NULL");
+    if (!rgb) return lt_bad(fn, "rgb is NULL");
+    if (!al4(points) || !al4(vertices) || !al4(faces) || !al4(pix_to_segment) || !al4(pix_to_face_out) || !al4(base))
+        return lt_bad(fn, "a buffer is not 4-B aligned");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::SvShadeArgs a{};
+    a.S = S; a.L = L; a.V = V; a.F = F; a.H = H; a.W = W; a.mode = mode;
+    memcpy(&a.sh, shading, sizeof(a.sh));
+    a.points = points; a.vertices = vertices; a.faces = faces; a.base = base;
+    a.pix_to_segment = pix_to_segment; a.pix_to_face_out = pix_to_face_out; a.rgb = rgb;
+    hipLaunchKernelGGL(ghr::k_sv_shade, dim3(sv_blocks(N)), dim3(GHR_SV_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+int ghr_strandview_resolve(void* stream, int32_t H, int32_t W, int32_t supersample, const uint8_t* src, uint8_t* dst)
+{
+    static const char* fn = "ghr_strandview_resolve: %s";
+    if (supersample != 1 && supersample != 2 && supersample != 4) return lt_bad(fn, "supersample is not 1, 2 or 4");
+    if (H < 0 || W < 0) return lt_bad(fn, "negative size");
+    if ((uint64_t)H * supersample * (uint64_t)W * supersample > 0x7fffffffull) return lt_bad(fn, "H * W exceeds 32-bit offsets");
+    const uint64_t N = (uint64_t)H * (uint64_t)W;
+    if (N == 0) return GHR_OK;
+    if (!src) return lt_bad(fn, "src is NULL");
+    if (!dst) return lt_bad(fn, "dst is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ghr::k_sv_resolve, dim3(sv_blocks(N)), dim3(GHR_SV_BLOCK), 0, s, ghr::SvResolveArgs{H, W, supersample, src, dst});
     return finish(s, 0);
 }
 

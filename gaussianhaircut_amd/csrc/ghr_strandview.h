@@ -1,0 +1,513 @@
+// ghr_strandview.h -- a preview of the groom: S strands of L points drawn as depth-tested polylines over the head mesh
+// (DESIGN.md 8l).  It stands where the reference's run.sh ends, src/postprocessing/render_video.py: that script hands the strands,
+// the head mesh and a camera path to Blender's Cycles hair (render_color.py on main.blend, a file the reference does not ship).
+// Blender is not a dependency, so the picture is DEFINED here, exactly and independently of any traversal order, and every form
+// (these kernels, the host simulator, the PyTorch comparator, the numpy model of the tests) is held to it bit for bit.
+// Everything is float32 without contraction, in the operand order written; only + - x /, sqrtf, fminf / fmaxf, comparisons and
+// integer arithmetic are used (no powf / expf / rsqrt), so that no bit depends on a math library.
+//
+//   View: M[12], H, W, near exactly as in 8h (ghr_visibility.h).  A point is projected by ghr::vis_project_one to
+//       (sx, sy, q = 1 / w, valid).  Pixel (row i, column j) is sampled at its centre c = (j + 0.5, i + 0.5).
+//   Segments: segment k = s (L - 1) + i joins points i and i + 1 of strand s.  It EXISTS iff both end points are valid.  Nothing is
+//       clipped: a segment with an end behind `near`, or with a NaN coordinate, is dropped whole.
+//   Coverage: half-width r (pixels, finite, > 0), screen ends a, b.  d = b - a, len2 = dx dx + dy dy, and for a centre c
+//       t = ((cx - ax) dx + (cy - ay) dy) / len2, clamped to [0, 1] as fminf(fmaxf(t, 0), 1);  t = 0 when len2 == 0 or t is NaN;
+//       e = c - (a + t d), i.e. ex = cx - (ax + t dx);
+//       the segment COVERS the pixel iff  ex ex + ey ey <= r r  (a closed capsule; a disc when the ends coincide)
+//       and c lies in the closed box [fminf(ax, bx) - r, fmaxf(ax, bx) + r] x [fminf(ay, by) - r, fmaxf(ay, by) + r].
+//       The box is implied by the capsule in exact arithmetic (as the box rule of 8g and 8h is implied by their side rule);
+//       stating it with the very floats the binning uses makes the tile lists and the wave skip EXACT instead of nearly safe.
+//   Inverse depth: qs = qa + t (qb - qa) -- inverse depth is linear along the screen segment.
+//   Strand WINNER of a pixel: the covering segment with the largest qs, the lowest k among equals; a qs that is NaN or not > 0
+//       never wins.  A maximum under a total order: binning, chunking and traversal order cannot change a bit of it.
+//   Head: pix_to_face [H][W] is 8h's winner plane, an input (or none: no mesh).  qf is 8h's inverse-depth expression of that
+//       face at the centre (sv_face_depth_one: vis_covers of the face's own record).  An entry outside 0 .. F - 1, or a face
+//       that does not cover the centre with an inverse depth > 0, counts as no face (qf = 0).
+//       The strand winner is KEPT iff there is no face, or  qs (1 + head_bias) >= qf  (head_bias >= 0, default 0: roots sit on
+//       the scalp, a caller may lift them).  Otherwise the head owns the pixel.
+//   Outputs, all [H][W]:  pix_to_segment int32 (-1: none, or hidden by the head), t float (0 where -1), pix_to_face_out int32
+//       (-1 where a strand is kept or nothing is there), inv_depth float (qs, qf or 0).
+//   Shading, uint8 [H][W][3], modes GHR_SV_KAJIYA (0, default) and GHR_SV_TANGENT (1).  A, B: the winner's two WORLD points.
+//       T = (B - A) / |B - A|, |x| = sqrtf((x0 x0 + x1 x1) + x2 x2); T = (0, 0, 0) when the length is 0.
+//       Dot products are (a0 b0 + a1 b1) + a2 b2.
+//       tangent:  colour = 0.5 + 0.5 T.
+//       kajiya:   V = eye - 0.5 (A + B), normalised the same way; Lw a world-space unit vector towards the light;
+//                 cl = T.Lw, cv = T.V, sl = sqrtf(fmaxf(0, 1 - cl cl)), sv likewise; diffuse = sl;
+//                 spec = fmaxf(0, cl cv + sl sv), then squared shininess_log2 times (default 5: the power 32);
+//                 colour = base[s] (ambient + kd diffuse) + ks spec.
+//       head pixel: n = (v1 - v0) x (v2 - v0) of the face, normalised the same way; colour = head_rgb (ambient + kd |n.Lw|),
+//                 |x| = fmaxf(x, -x).
+//       elsewhere: background_rgb.
+//       byte = quant8(clamp01(colour)) -- torchvision's save_image rule, ghr_products.h.
+//       Defaults (this header's and the README's): ambient 0.25, kd 0.65, ks 0.35, shininess_log2 5, hair (0.45, 0.30, 0.18)
+//       (a warm brown), head (0.62, 0.62, 0.62), background (1, 1, 1); the light (0.45, -0.60, -0.66) in camera axes (x right,
+//       y down, z forward: above and to the right of the camera, on its side of the head), normalised and rotated to world;
+//       eye and Lw are formed on the host in double and rounded once.
+//   Supersampling s in {1, 2, 4}: rows 0 and 1 of M and r are multiplied by s (exact: a power of two), 8h's raster, this raster
+//       and the shade run at sH x sW, and sv_resolve_one writes (sum of the s x s bytes + s s / 2) / (s s) per channel, in integers.
+//
+// Per frame (ghr_strandview_raster): one fill of the tile counters, then
+//   k_sv_project   one thread per point: {sx, sy, q, valid}, 16 B
+//   k_sv_setup     one thread per segment: a 32-B record  ax ay bx by | qa qb xy bits  and its rectangle of 16 x 16 tiles.
+//                  The rectangle is vis_pixel_range of the box widened by r -- the same four floats the coverage rule compares
+//                  the centre with -- so it can never be too small: a centre inside the closed box satisfies j + 0.5 >= lo, and
+//                  vis_pixel_range's floor of the rounded lo - 0.5 is never above such a j (monotone rounding, j exact), likewise
+//                  at the upper end.  xy = first tile x | y << 16; bits = flags | (tiles across - 1) << 8 | (tiles down - 1) << 16.
+//                  A segment of more than GHR_SV_BIG_RECT tiles goes to the frame's one BIG list, which every tile walks after its
+//                  own: the lists hold at most GHR_SV_BIG_RECT entries per segment, so the workspace is sized from S, L, H, W
+//                  alone, with no read-back.
+//   k_sv_scan      one workgroup: exclusive scan of the tile counts; the counts become the fill cursors
+//   k_sv_scatter   one thread per segment: its id into the lists of its tiles (integer atomics; the order inside a list is free)
+//   k_sv_raster    one 256-thread workgroup per tile, one pixel per thread; records staged in LDS GHR_SV_CHUNK at a time; a wave
+//                  none of whose lanes is in a record's widened box skips it by ballot; pix_to_face / qf are read once.
+// and, on their own entries: k_sv_face_depth (one thread per pixel: qf), k_sv_shade (one thread per pixel: it gathers the winner's
+// two world points or the face's three vertices), k_sv_resolve (one thread per output pixel).  Integer atomics only.
+// Everything per element is GHR_HD so that tests/hostsim/ghr_hostsim_strandview.cpp runs the product's own arithmetic on the CPU.
+#pragma once
+#include "ghr_visibility.h"
+#if defined(__HIPCC__)
+#include "ghr_products.h"
+#endif
+
+#define GHR_SV_TILE 16
+#define GHR_SV_BLOCK 256
+#define GHR_SV_CHUNK 128     // records staged in LDS per round of k_sv_raster (two 16-B units each: one per thread)
+#define GHR_SV_REC_WORDS 8   // two 16-B units per segment
+#define GHR_SV_BIG_RECT 16   // a segment of more tiles than this goes to the big list
+#define GHR_SV_NEVER 1u
+#define GHR_SV_EMPTY 2u
+#define GHR_SV_BIG 4u
+#define GHR_SV_KAJIYA 0
+#define GHR_SV_TANGENT 1
+#define GHR_SV_MAX_SHININESS_LOG2 16
+
+namespace ghr {
+
+// == ghr_strandview_shading of include/ghr.h
+struct SvShading {
+    float eye[3], light[3];
+    float ambient, kd, ks;
+    int32_t shininess_log2;
+    float base_rgb[3], head_rgb[3], background_rgb[3];
+};
+
+// One segment: its record from the projected end points pa, pb = {sx, sy, q, valid}.
+GHR_HD void sv_setup_one(const float* pa, const float* pb, float r, int H, int W, float* rec)
+{
+    const bool never = pa[3] == 0.f || pb[3] == 0.f;
+    rec[0] = pa[0]; rec[1] = pa[1]; rec[2] = pb[0]; rec[3] = pb[1]; rec[4] = pa[2]; rec[5] = pb[2];
+    uint32_t bits = never ? GHR_SV_NEVER : 0u, xy = 0u;
+    int j0 = 0, j1 = -1, i0 = 0, i1 = -1;
+    const float ulo = fminf(pa[0], pb[0]) - r, uhi = fmaxf(pa[0], pb[0]) + r;
+    const float vlo = fminf(pa[1], pb[1]) - r, vhi = fmaxf(pa[1], pb[1]) + r;
+    if (!never && vis_pixel_range(ulo, uhi, W, &j0, &j1) && vis_pixel_range(vlo, vhi, H, &i0, &i1)) {
+        const uint32_t x0 = (uint32_t)j0 / GHR_SV_TILE, x1 = (uint32_t)j1 / GHR_SV_TILE;
+        const uint32_t y0 = (uint32_t)i0 / GHR_SV_TILE, y1 = (uint32_t)i1 / GHR_SV_TILE;
+        xy = x0 | (y0 << 16);
+        if ((uint64_t)(x1 - x0 + 1u) * (y1 - y0 + 1u) > GHR_SV_BIG_RECT) bits |= GHR_SV_BIG;
+        else bits |= ((x1 - x0) << 8) | ((y1 - y0) << 16);  // (each below GHR_SV_BIG_RECT)
+    } else {
+        bits |= GHR_SV_EMPTY;
+    }
+    memcpy(rec + 6, &xy, 4);
+    memcpy(rec + 7, &bits, 4);
+}
+
+GHR_HD bool sv_in_box(const float* rec, float r, float px, float py)
+{
+    const float ulo = fminf(rec[0], rec[2]) - r, uhi = fmaxf(rec[0], rec[2]) + r;
+    const float vlo = fminf(rec[1], rec[3]) - r, vhi = fmaxf(rec[1], rec[3]) + r;
+    return px >= ulo && px <= uhi && py >= vlo && py <= vhi;
+}
+
+// One record against one pixel centre: does the segment cover it, where along itself and with which inverse depth?
+GHR_HD bool sv_covers(const float* rec, float r, float px, float py, float* t_out, float* qs)
+{
+    uint32_t bits;
+    memcpy(&bits, rec + 7, 4);
+    if ((bits & GHR_SV_NEVER) || !sv_in_box(rec, r, px, py)) return false;
+    const float ax = rec[0], ay = rec[1], bx = rec[2], by = rec[3], qa = rec[4], qb = rec[5];
+    const float dx = bx - ax, dy = by - ay;
+    const float len2 = dx * dx + dy * dy;
+    float t = ((px - ax) * dx + (py - ay) * dy) / len2;
+    t = fminf(fmaxf(t, 0.f), 1.f);
+    if (len2 == 0.f || t != t) t = 0.f;
+    const float ex = px - (ax + t * dx), ey = py - (ay + t * dy);
+    if (!(ex * ex + ey * ey <= r * r)) return false;
+    *t_out = t;
+    *qs = qa + t * (qb - qa);
+    return true;
+}
+
+// The total order of the winner: (inverse depth, lower index).  best starts at (0, -1): only a qs > 0 gets in, a NaN never.
+GHR_HD void sv_take(float q, float t, int32_t k, float* best_q, float* best_t, int32_t* best_k)
+{
+    if (q > *best_q || (q == *best_q && k < *best_k)) { *best_q = q; *best_t = t; *best_k = k; }
+}
+
+// 8h's inverse depth of face f at a pixel centre, from the mesh itself; 0: no face there.
+GHR_HD float sv_face_depth_one(const float* M, float near, const float* vertices, int V, const int32_t* faces, int F, int32_t f,
+                               float px, float py)
+{
+    if (f < 0 || f >= F) return 0.f;
+    const int32_t t[3] = {faces[3 * (size_t)f], faces[3 * (size_t)f + 1], faces[3 * (size_t)f + 2]};
+    if (t[0] < 0 || t[0] >= V || t[1] < 0 || t[1] >= V || t[2] < 0 || t[2] >= V) return 0.f;
+    if (t[0] == t[1] || t[1] == t[2] || t[0] == t[2]) return 0.f;
+    float p[3][4];
+    for (int k = 0; k < 3; k++) vis_project_one(M, vertices + 3 * (size_t)t[k], near, p[k]);
+    if (p[0][3] == 0.f || p[1][3] == 0.f || p[2][3] == 0.f) return 0.f;
+    if (mesh_flat(p[0][0], p[0][1], p[1][0], p[1][1], p[2][0], p[2][1])) return 0.f;
+    float r[GHR_VIS_REC_WORDS] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < 3; k++) { r[2 * k] = p[k][0]; r[2 * k + 1] = p[k][1]; r[6 + k] = p[k][2]; }
+    const uint32_t bits = (t[0] > t[1] ? 1u : 0u) | (t[1] > t[2] ? 2u : 0u) | (t[2] > t[0] ? 4u : 0u);
+    memcpy(r + 9, &bits, 4);
+    float d;
+    if (!vis_covers(r, px, py, &d)) return 0.f;
+    return d > 0.f ? d : 0.f;  // (a NaN fails the comparison)
+}
+
+// Strand winner (best_k, best_t, best_q; best_k < 0: none) against the head (face, qf): the four planes' values at one pixel.
+GHR_HD void sv_resolve_head(int32_t best_k, float best_t, float best_q, int32_t face, float qf, float head_bias, int32_t* seg,
+                            float* t, int32_t* face_out, float* inv_depth)
+{
+    const bool has_face = qf > 0.f;
+    if (best_k >= 0 && (!has_face || best_q * (1.f + head_bias) >= qf)) {
+        *seg = best_k; *t = best_t; *face_out = -1; *inv_depth = best_q;
+    } else if (has_face) {
+        *seg = -1; *t = 0.f; *face_out = face; *inv_depth = qf;
+    } else {
+        *seg = -1; *t = 0.f; *face_out = -1; *inv_depth = 0.f;
+    }
+}
+
+GHR_HD float sv_dot(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+// x / |x|, (0, 0, 0) when the length is 0
+GHR_HD void sv_normalise(const float* x, float* out)
+{
+    const float len = sqrtf(sv_dot(x, x));
+    for (int c = 0; c < 3; c++) out[c] = len == 0.f ? 0.f : x[c] / len;
+}
+
+GHR_HD uint32_t sv_quant8(float v)
+{
+#if defined(__HIPCC__)
+    return quant8(clamp01(v));
+#else  // (ghr_products.h needs the HIP runtime; its two expressions, for the host simulator)
+    return (uint32_t)fminf(fmaxf(fminf(fmaxf(v, 0.f), 1.f) * 255.f + 0.5f, 0.f), 255.f);
+#endif
+}
+
+GHR_HD void sv_shade_strand(const float* A, const float* B, const float* base, int mode, const SvShading& sh, uint8_t* rgb)
+{
+    const float d[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
+    float T[3];
+    sv_normalise(d, T);
+    if (mode == GHR_SV_TANGENT) {
+        for (int c = 0; c < 3; c++) rgb[c] = (uint8_t)sv_quant8(0.5f + 0.5f * T[c]);
+        return;
+    }
+    const float v[3] = {sh.eye[0] - 0.5f * (A[0] + B[0]), sh.eye[1] - 0.5f * (A[1] + B[1]), sh.eye[2] - 0.5f * (A[2] + B[2])};
+    float Vn[3];
+    sv_normalise(v, Vn);
+    const float cl = sv_dot(T, sh.light), cv = sv_dot(T, Vn);
+    const float sl = sqrtf(fmaxf(0.f, 1.f - cl * cl)), sv = sqrtf(fmaxf(0.f, 1.f - cv * cv));
+    float spec = fmaxf(0.f, cl * cv + sl * sv);
+    for (int k = 0; k < sh.shininess_log2; k++) spec = spec * spec;
+    for (int c = 0; c < 3; c++) rgb[c] = (uint8_t)sv_quant8(base[c] * (sh.ambient + sh.kd * sl) + sh.ks * spec);
+}
+
+GHR_HD void sv_shade_head(const float* v0, const float* v1, const float* v2, const SvShading& sh, uint8_t* rgb)
+{
+    const float e1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]}, e2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
+    const float n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+    float nn[3];
+    sv_normalise(n, nn);
+    const float c = sv_dot(nn, sh.light);
+    const float lit = sh.ambient + sh.kd * fmaxf(c, -c);
+    for (int k = 0; k < 3; k++) rgb[k] = (uint8_t)sv_quant8(sh.head_rgb[k] * lit);
+}
+
+// One pixel of the picture.  An index that points outside its table shades as background (the planes are a caller's).
+GHR_HD void sv_shade_one(int32_t seg, int32_t face, int S, int L, const float* points, int V, const float* vertices, int F,
+                         const int32_t* faces, const float* base, int mode, const SvShading& sh, uint8_t* rgb)
+{
+    if (seg >= 0 && L >= 2 && (int64_t)seg < (int64_t)S * (L - 1)) {
+        const int s = seg / (L - 1), i = seg % (L - 1);
+        const float* A = points + 3 * ((size_t)s * L + i);
+        sv_shade_strand(A, A + 3, base ? base + 3 * (size_t)s : sh.base_rgb, mode, sh, rgb);
+        return;
+    }
+    if (face >= 0 && face < F) {
+        const int32_t* t = faces + 3 * (size_t)face;
+        if (t[0] >= 0 && t[0] < V && t[1] >= 0 && t[1] < V && t[2] >= 0 && t[2] < V) {
+            sv_shade_head(vertices + 3 * (size_t)t[0], vertices + 3 * (size_t)t[1], vertices + 3 * (size_t)t[2], sh, rgb);
+            return;
+        }
+    }
+    for (int c = 0; c < 3; c++) rgb[c] = (uint8_t)sv_quant8(sh.background_rgb[c]);
+}
+
+// One output pixel of the resolve: src is [s H][s W][3], dst [H][W][3].
+GHR_HD void sv_resolve_one(const uint8_t* src, int W, int s, int i, int j, uint8_t* dst)
+{
+    for (int c = 0; c < 3; c++) {
+        uint32_t sum = 0u;
+        for (int di = 0; di < s; di++)
+            for (int dj = 0; dj < s; dj++) sum += src[3 * (((size_t)i * s + di) * ((size_t)W * s) + (size_t)j * s + dj) + c];
+        dst[3 * ((size_t)i * W + j) + c] = (uint8_t)((sum + (uint32_t)(s * s) / 2u) / (uint32_t)(s * s));
+    }
+}
+
+// ---- the workspace ---------------------------------------------------------------------------------------------------------
+// Offsets in bytes, 16-B aligned.  [off_fill, off_fill + fill_bytes) is what a frame zeroes first: the tile counts and the length
+// of the big list.
+struct SvLayout {
+    uint64_t off_proj, off_rec, off_start, off_fill, off_count, off_nbig, fill_bytes, off_list, off_big, bytes;
+    uint64_t list_cap, n_points, n_segments;
+    int32_t tiles_x, tiles_y;
+};
+
+inline const char* sv_layout(int64_t S, int64_t L, int64_t H, int64_t W, SvLayout* Y)
+{
+    if (S < 0 || H < 0 || W < 0) return "negative size";
+    if (L < 2) return "L < 2: a strand needs two points";
+    if (S > 0x7fffffff || L > 0x7fffffff || H > 0x7fffffff || W > 0x7fffffff) return "a size exceeds 2^31 - 1";
+    if ((uint64_t)H * (uint64_t)W > 0x7fffffffull) return "H * W exceeds 32-bit offsets";
+    if ((uint64_t)S * (uint64_t)L > 0x7fffffffull / 3) return "S * L * 3 exceeds 32-bit offsets";
+    const uint64_t tx = ((uint64_t)W + GHR_SV_TILE - 1) / GHR_SV_TILE, ty = ((uint64_t)H + GHR_SV_TILE - 1) / GHR_SV_TILE;
+    if (tx > 65535 || ty > 65535) return "image too large for 16-bit tile coordinates";
+    const uint64_t T = tx * ty, N = (uint64_t)S * (uint64_t)L, K = (uint64_t)S * (uint64_t)(L - 1);
+    const uint64_t per_seg = T < GHR_SV_BIG_RECT ? T : GHR_SV_BIG_RECT;
+    const uint64_t cap = K * per_seg;
+    if (cap > 0x7fffffffull) return "the tile lists exceed 32-bit offsets";
+    Y->tiles_x = (int32_t)tx; Y->tiles_y = (int32_t)ty;
+    Y->list_cap = cap; Y->n_points = N; Y->n_segments = K;
+    uint64_t off = 0;
+    Y->off_proj = off; off = mesh_up16(off + 16ull * N);
+    Y->off_rec = off; off = mesh_up16(off + 4ull * GHR_SV_REC_WORDS * K);
+    Y->off_start = off; off = mesh_up16(off + 4ull * (T + 1));
+    Y->off_fill = off;
+    Y->off_count = off; off = mesh_up16(off + 4ull * T);
+    Y->off_nbig = off; off += 16;
+    Y->fill_bytes = off - Y->off_fill;
+    Y->off_list = off; off = mesh_up16(off + 4ull * cap);
+    Y->off_big = off; off = mesh_up16(off + 4ull * K);
+    Y->bytes = off + 16;  // (never 0: a caller's allocation of `bytes` has an address)
+    return nullptr;
+}
+
+// ---- kernels ---------------------------------------------------------------------------------------------------------------
+#if defined(__HIPCC__)
+struct SvArgs {
+    int32_t S, L, H, W, tiles_x, tiles_y;
+    uint32_t n_points, n_segments;
+    float near, r, head_bias;
+    float M[12];
+    const float* points;         // [S][L][3]
+    const int32_t* pix_to_face;  // [H][W] or NULL: no mesh
+    const float* qf;             // [H][W] or NULL with it
+    float* proj;                 // [S L][4]
+    float* rec;                  // [S (L - 1)][8]
+    uint32_t* start;             // [T + 1]
+    uint32_t* count;             // [T]: counts, then fill cursors
+    uint32_t* nbig;
+    uint32_t* list;              // [list_cap]
+    uint32_t* big;               // [S (L - 1)]
+    uint32_t list_cap;
+    int32_t* pix_to_segment;     // [H][W]
+    float* t;                    // [H][W]
+    int32_t* pix_to_face_out;    // [H][W]
+    float* inv_depth;            // [H][W]
+};
+
+__global__ void __launch_bounds__(GHR_SV_BLOCK) k_sv_project(SvArgs a)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t v = blockIdx.x * GHR_SV_BLOCK + threadIdx.x;
+    if (v >= a.n_points) return;
+    const float X[3] = {a.points[3 * (size_t)v], a.points[3 * (size_t)v + 1], a.points[3 * (size_t)v + 2]};
+    float o[4];
+    vis_project_one(a.M, X, a.near, o);
+    reinterpret_cast<f4*>(a.proj)[v] = f4{o[0], o[1], o[2], o[3]};
+#endif
+}
+
+__global__ void __launch_bounds__(GHR_SV_BLOCK) k_sv_setup(SvArgs a)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t k = blockIdx.x * GHR_SV_BLOCK + threadIdx.x;
+    if (k >= a.n_segments) return;
+    const uint32_t s = k / (uint32_t)(a.L - 1), i = k % (uint32_t)(a.L - 1);
+    const size_t p = (size_t)s * (uint32_t)a.L + i;  // (p + 1 < S L)
+    const f4 pa = reinterpret_cast<const f4*>(a.proj)[p], pb = reinterpret_cast<const f4*>(a.proj)[p + 1];
+    const float fa[4] = {pa.x, pa.y, pa.z, pa.w}, fb[4] = {pb.x, pb.y, pb.z, pb.w};
+    float r[GHR_SV_REC_WORDS];
+    sv_setup_one(fa, fb, a.r, a.H, a.W, r);
+    f4* out = reinterpret_cast<f4*>(a.rec) + 2 * (size_t)k;
+    out[0] = f4{r[0], r[1], r[2], r[3]};
+    out[1] = f4{r[4], r[5], r[6], r[7]};
+    uint32_t xy, bits;
+    memcpy(&xy, r + 6, 4); memcpy(&bits, r + 7, 4);
+    if (bits & GHR_SV_EMPTY) return;
+    if (bits & GHR_SV_BIG) {
+        const uint32_t pos = atomicAdd(a.nbig, 1u);
+        if (pos < a.n_segments) a.big[pos] = k;  // (one entry per segment at the most: always true)
+        return;
+    }
+    const uint32_t x0 = xy & 0xffffu, y0 = xy >> 16, nx = (bits >> 8) & 0xffu, ny = (bits >> 16) & 0xffu;
+    for (uint32_t y = y0; y <= y0 + ny; y++)
+        for (uint32_t x = x0; x <= x0 + nx; x++) atomicAdd(&a.count[y * (uint32_t)a.tiles_x + x], 1u);
+#endif
+}
+
+// One workgroup.  start[t] = the entries of the tiles before t; count[t] becomes the fill cursor of tile t (= start[t]).
+__global__ void __launch_bounds__(GHR_SV_BLOCK) k_sv_scan(SvArgs a)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ uint32_t s_tmp[4];
+    const uint32_t T = (uint32_t)a.tiles_x * (uint32_t)a.tiles_y;
+    uint32_t run = 0u;
+    for (uint32_t base = 0u; base < T; base += GHR_SV_BLOCK) {
+        const uint32_t t = base + threadIdx.x;
+        const uint32_t n = t < T ? a.count[t] : 0u;
+        uint32_t total;
+        const uint32_t before = block_excl_scan_256(n, s_tmp, &total);
+        if (t < T) { a.start[t] = run + before; a.count[t] = run + before; }
+        run += total;
+        __syncthreads();  // s_tmp is written again in the next round
+    }
+    if (threadIdx.x == 0) a.start[T] = run;
+#endif
+}
+
+__global__ void __launch_bounds__(GHR_SV_BLOCK) k_sv_scatter(SvArgs a)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t k = blockIdx.x * GHR_SV_BLOCK + threadIdx.x;
+    if (k >= a.n_segments) return;
+    const uint32_t* r = reinterpret_cast<const uint32_t*>(a.rec) + (size_t)GHR_SV_REC_WORDS * k;
+    const uint32_t xy = r[6], bits = r[7];
+    if (bits & (GHR_SV_EMPTY | GHR_SV_BIG)) return;
+    const uint32_t x0 = xy & 0xffffu, y0 = xy >> 16, nx = (bits >> 8) & 0xffu, ny = (bits >> 16) & 0xffu;
+    for (uint32_t y = y0; y <= y0 + ny; y++)
+        for (uint32_t x = x0; x <= x0 + nx; x++) {
+            const uint32_t pos = atomicAdd(&a.count[y * (uint32_t)a.tiles_x + x], 1u);
+            if (pos < a.list_cap) a.list[pos] = k;  // (at most GHR_SV_BIG_RECT entries per segment: always true)
+        }
+#endif
+}
+
+// One tile per workgroup, one pixel per thread (a wave holds 4 rows of 16 pixels).
+__global__ void __launch_bounds__(GHR_SV_BLOCK) k_sv_raster(SvArgs a)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ f4 s_rec[2 * GHR_SV_CHUNK];
+    __shared__ uint32_t s_id[GHR_SV_CHUNK];
+    const uint32_t tile = blockIdx.y * (uint32_t)a.tiles_x + blockIdx.x;
+    const int i = (int)blockIdx.y * GHR_SV_TILE + (int)threadIdx.x / GHR_SV_TILE;
+    const int j = (int)blockIdx.x * GHR_SV_TILE + (int)threadIdx.x % GHR_SV_TILE;
+    const bool in_image = i < a.H && j < a.W;
+    const float px = (float)j + 0.5f, py = (float)i + 0.5f;
+    const uint32_t beg = a.start[tile], n_own = a.start[tile + 1] - beg;
+    const uint32_t n_big = a.n_segments > 0u ? min(*a.nbig, a.n_segments) : 0u;
+    const uint32_t n = n_own + n_big;  // (workgroup-uniform)
+    float best_q = 0.f, best_t = 0.f;
+    int32_t best_k = -1;
+    for (uint32_t c0 = 0u; c0 < n; c0 += GHR_SV_CHUNK) {
+        const uint32_t m = min((uint32_t)GHR_SV_CHUNK, n - c0);
+        if (threadIdx.x < 2u * m) {
+            const uint32_t k = threadIdx.x / 2u, part = threadIdx.x % 2u, e = c0 + k;
+            // (beg + e < start[T] <= list_cap and every id < S (L - 1); the clamps keep a workspace that two streams were wrongly
+            // given at once from ever indexing outside it)
+            uint32_t id = e < n_own ? a.list[min(beg + e, a.list_cap - 1u)] : a.big[e - n_own];
+            id = min(id, a.n_segments - 1u);
+            s_rec[2u * k + part] = reinterpret_cast<const f4*>(a.rec)[2 * (size_t)id + part];
+            if (part == 0u) s_id[k] = id;
+        }
+        __syncthreads();
+        for (uint32_t k = 0u; k < m; k++) {
+            const f4 r0 = s_rec[2u * k], r1 = s_rec[2u * k + 1u];  // (one address per wave: broadcast)
+            const float r[GHR_SV_REC_WORDS] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+            const bool box = in_image && sv_in_box(r, a.r, px, py);
+            if (__builtin_amdgcn_ballot_w64(box) == 0ull) continue;  // nobody in this wave is inside the widened box
+            float t, q;
+            if (box && sv_covers(r, a.r, px, py, &t, &q)) sv_take(q, t, (int32_t)s_id[k], &best_q, &best_t, &best_k);
+        }
+        __syncthreads();
+    }
+    if (!in_image) return;
+    const size_t o = (size_t)i * a.W + j;
+    const int32_t face = a.pix_to_face ? a.pix_to_face[o] : -1;
+    const float qf = a.pix_to_face ? a.qf[o] : 0.f;
+    int32_t seg, face_out;
+    float t, d;
+    sv_resolve_head(best_k, best_t, best_q, face, qf, a.head_bias, &seg, &t, &face_out, &d);
+    a.pix_to_segment[o] = seg;
+    a.t[o] = t;
+    a.pix_to_face_out[o] = face_out;
+    a.inv_depth[o] = d;
+#endif
+}
+
+struct SvFaceDepthArgs {
+    int32_t V, F, H, W;
+    float near;
+    float M[12];
+    const float* vertices;
+    const int32_t* faces;
+    const int32_t* pix_to_face;
+    float* qf;
+};
+
+__global__ void __launch_bounds__(GHR_SV_BLOCK) k_sv_face_depth(SvFaceDepthArgs a)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t o = blockIdx.x * GHR_SV_BLOCK + threadIdx.x;
+    if (o >= (uint32_t)a.H * (uint32_t)a.W) return;
+    const int i = (int)(o / (uint32_t)a.W), j = (int)(o % (uint32_t)a.W);
+    a.qf[o] = sv_face_depth_one(a.M, a.near, a.vertices, a.V, a.faces, a.F, a.pix_to_face[o], (float)j + 0.5f, (float)i + 0.5f);
+#endif
+}
+
+struct SvShadeArgs {
+    int32_t S, L, V, F, H, W, mode;
+    SvShading sh;
+    const float* points;
+    const float* vertices;
+    const int32_t* faces;
+    const float* base;  // [S][3] or NULL: sh.base_rgb
+    const int32_t* pix_to_segment;
+    const int32_t* pix_to_face_out;
+    uint8_t* rgb;       // [H][W][3]
+};
+
+__global__ void __launch_bounds__(GHR_SV_BLOCK) k_sv_shade(SvShadeArgs a)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t o = blockIdx.x * GHR_SV_BLOCK + threadIdx.x;
+    if (o >= (uint32_t)a.H * (uint32_t)a.W) return;
+    uint8_t rgb[3];
+    sv_shade_one(a.pix_to_segment[o], a.pix_to_face_out[o], a.S, a.L, a.points, a.V, a.vertices, a.F, a.faces, a.base, a.mode, a.sh,
+                 rgb);
+    a.rgb[3 * (size_t)o] = rgb[0]; a.rgb[3 * (size_t)o + 1] = rgb[1]; a.rgb[3 * (size_t)o + 2] = rgb[2];
+#endif
+}
+
+struct SvResolveArgs {
+    int32_t H, W, s;
+    const uint8_t* src;
+    uint8_t* dst;
+};
+
+__global__ void __launch_bounds__(GHR_SV_BLOCK) k_sv_resolve(SvResolveArgs a)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t o = blockIdx.x * GHR_SV_BLOCK + threadIdx.x;
+    if (o >= (uint32_t)a.H * (uint32_t)a.W) return;
+    sv_resolve_one(a.src, a.W, a.s, (int)(o / (uint32_t)a.W), (int)(o % (uint32_t)a.W), a.dst);
+#endif
+}
+#endif  // __HIPCC__
+
+}  // namespace ghr

@@ -893,6 +893,43 @@ int ghr_chamfer_point_backward(void* stream, int64_t Px, int64_t Py, int32_t nor
                                const float* y_normals, int32_t abs_cosine, const float* g_cos, float* d_x, float* d_y,
                                float* d_x_normals, float* d_y_normals);
 
+/* ---- the strand preview: depth-tested polylines over the head mesh, shaded (csrc/ghr_strandview.h)
+ * Added without an ABI_VERSION bump: five new functions and one new struct, no existing struct or signature changed.
+ * The definition of coverage (a closed capsule of half-width r pixels around every segment of S strands of L points), of the
+ * winner (largest inverse depth, lowest segment index among equals), of the head test and of the shading is the one at the top of
+ * csrc/ghr_strandview.h.  M [12] is on the HOST, as for ghr_vis_view; every other pointer is device memory.
+ * ghr_strandview_sizes: bytes of the workspace of one frame (16-B aligned; reusable for any frame of at most these sizes).
+ * ghr_strandview_face_depth: qf [H][W] = 8h's inverse depth of face pix_to_face[pixel] at the pixel's centre, 0 where the entry
+ * is outside 0 .. F - 1 or the face does not cover the centre.
+ * ghr_strandview_raster: points [S][L][3]; pix_to_face / qf are given or NULL together (NULL: no mesh).  Writes the four planes
+ * pix_to_segment (int32, -1: none or hidden by the head), t, pix_to_face_out (int32) and inv_depth.
+ * ghr_strandview_shade: rgb [H][W][3] bytes from the two index planes; mode GHR_STRANDVIEW_KAJIYA or GHR_STRANDVIEW_TANGENT;
+ * base [S][3] per-strand colours or NULL (shading->base_rgb for every strand).  An index outside its table shades as background.
+ * ghr_strandview_resolve: dst [H][W][3] from src [s H][s W][3], s = supersample in {1, 2, 4}: (sum + s s / 2) / (s s).
+ * S == 0, F == 0 and H * W == 0 are valid.  Refused: L < 2, a half_width that is not finite and > 0, a negative (or NaN)
+ * head_bias, an unknown mode, a shininess_log2 outside 0 .. 16, supersample outside {1, 2, 4}, a NULL required buffer, a
+ * workspace that is not 16-B aligned or a plane that is not 4-B aligned.  A refused call launches nothing and ghr_last_error()
+ * says why. */
+#define GHR_STRANDVIEW_KAJIYA 0
+#define GHR_STRANDVIEW_TANGENT 1
+typedef struct ghr_strandview_shading {
+    float eye[3];             /* the camera centre, world space */
+    float light[3];           /* a unit vector towards the light, world space */
+    float ambient, kd, ks;
+    int32_t shininess_log2;   /* the specular term is squared this many times */
+    float base_rgb[3], head_rgb[3], background_rgb[3];
+} ghr_strandview_shading;
+int ghr_strandview_sizes(int32_t S, int32_t L, int32_t H, int32_t W, size_t* bytes);
+int ghr_strandview_face_depth(void* stream, int32_t V, const float* vertices, int32_t F, const int32_t* faces, const float* M,
+                              float near_w, int32_t H, int32_t W, const int32_t* pix_to_face, float* qf);
+int ghr_strandview_raster(void* stream, int32_t S, int32_t L, const float* points, const float* M, float near_w, int32_t H,
+                          int32_t W, float half_width, float head_bias, const int32_t* pix_to_face, const float* qf,
+                          void* workspace, int32_t* pix_to_segment, float* t, int32_t* pix_to_face_out, float* inv_depth);
+int ghr_strandview_shade(void* stream, int32_t S, int32_t L, const float* points, int32_t V, const float* vertices, int32_t F,
+                         const int32_t* faces, int32_t H, int32_t W, const int32_t* pix_to_segment, const int32_t* pix_to_face_out,
+                         int32_t mode, const ghr_strandview_shading* shading, const float* base, uint8_t* rgb);
+int ghr_strandview_resolve(void* stream, int32_t H, int32_t W, int32_t supersample, const uint8_t* src, uint8_t* dst);
+
 /* Introspection for tests (device pointers into the workspaces; layout is otherwise private). */
 typedef struct ghr_ws_view {
     const float* rec;          /* [P][16]: x, y, conic a, b, c, opacity, features[10] */
