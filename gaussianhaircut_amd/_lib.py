@@ -188,6 +188,13 @@ class StrandViewShading(ctypes.Structure):
                 ("head_rgb", ctypes.c_float * 3), ("background_rgb", ctypes.c_float * 3)]
 
 
+class StrandViewShadow(ctypes.Structure):
+    """``ghr_strandview_shadow`` (include/ghr.h)."""
+    _fields_ = [("Ml", ctypes.c_float * 12), ("near_w", ctypes.c_float), ("Hl", ctypes.c_int32), ("Wl", ctypes.c_int32),
+                ("layer", ctypes.c_float), ("kappa", ctypes.c_float), ("bias", ctypes.c_float), ("q0", ctypes.c_void_p),
+                ("layers", ctypes.c_void_p), ("qfl", ctypes.c_void_p)]
+
+
 def latent_loss_sums_floats(W: int, H: int) -> int:
     """floats of the latent-stage loss kernels' ``sums`` for a W x H image (``ghr_latent_loss_sums_floats``)."""
     return int(lib().ghr_latent_loss_sums_floats(int(W), int(H)))
@@ -221,7 +228,7 @@ EXPORTS = ["ghr_last_error", "ghr_abi_version", "ghr_forward_sizes", "ghr_binnin
            "ghr_mesh_grid_sizes", "ghr_mesh_grid_build", "ghr_mesh_contains", "ghr_gaussian_probe_outside",
            "ghr_vis_sizes", "ghr_vis_view", "ghr_vis_head_mask",
            "ghr_strandview_sizes", "ghr_strandview_face_depth", "ghr_strandview_raster", "ghr_strandview_shade",
-           "ghr_strandview_resolve",
+           "ghr_strandview_resolve", "ghr_strandview_opacity", "ghr_strandview_shade_shadowed",
            "ghr_sds_local", "ghr_sds_local_backward", "ghr_sds_texture", "ghr_sds_texture_backward",
            "ghr_nn_workspace_size", "ghr_nn_search", "ghr_chamfer_point", "ghr_chamfer_point_backward"]
 
@@ -330,6 +337,10 @@ def lib() -> ctypes.CDLL:
     L.ghr_strandview_shade.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32,
                                        ctypes.POINTER(StrandViewShading), vp, vp]
     L.ghr_strandview_resolve.argtypes = [vp, i32, i32, i32, vp, vp]
+    L.ghr_strandview_opacity.argtypes = [vp, i32, i32, vp, ctypes.POINTER(ctypes.c_float * 12), f32, i32, i32, f32, f32, vp,
+                                         ctypes.c_size_t, vp, vp]
+    L.ghr_strandview_shade_shadowed.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, i32,
+                                                ctypes.POINTER(StrandViewShading), vp, ctypes.POINTER(StrandViewShadow), vp]
     L.ghr_sds_local.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, f32, vp, vp]
     L.ghr_sds_local_backward.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, f32, vp, vp, vp]
     L.ghr_sds_texture.argtypes = [vp, i32, i32, i32, i32] + [vp] * 13

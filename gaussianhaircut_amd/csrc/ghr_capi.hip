@@ -2347,6 +2347,105 @@ int ghr_strandview_resolve(void* stream, int32_t H, int32_t W, int32_t supersamp
     return finish(s, 0);
 }
 
+// -- self-shadowing: the light pass and the shadowed shade
+static_assert(sizeof(ghr_strandview_shadow) == sizeof(ghr::SvShadow), "ghr_strandview_shadow is ghr::SvShadow");
+
+int ghr_strandview_opacity(void* stream, int32_t S, int32_t L, const float* points, const float* Ml, float near_w, int32_t Hl,
+                           int32_t Wl, float half_width, float layer, void* workspace, size_t workspace_bytes, float* q0,
+                           uint32_t* layers)
+{
+    static const char* fn = "ghr_strandview_opacity: %s";
+    ghr::SvLayout Y;
+    if (const char* why = ghr::sv_layout(S, L, Hl, Wl, &Y)) return lt_bad(fn, why);
+    if (S && !points) return lt_bad(fn, "points is NULL");
+    if (!Ml) return lt_bad(fn, "Ml is NULL");
+    if (!(near_w >= 0.f)) return lt_bad(fn, "near is negative or NaN");
+    if (!(ghr::vis_finite(half_width) && half_width > 0.f)) return lt_bad(fn, "half_width is not finite and > 0");
+    if (!(ghr::vis_finite(layer) && layer > 0.f)) return lt_bad(fn, "layer is not finite and > 0");
+    if (!workspace) return lt_bad(fn, "workspace is NULL");
+    if (!al16(workspace)) return lt_bad(fn, "workspace is not 16-B aligned (the segment records are read 16 B at a time)");
+    if ((uint64_t)workspace_bytes < Y.bytes) return lt_bad(fn, "workspace is too small: ghr_strandview_sizes(S, L, Hl, Wl) sizes it");
+    const bool texels = (int64_t)Hl * Wl > 0;
+    if (texels && (!q0 || !layers)) return lt_bad(fn, "an output plane is NULL");
+    if (!al4(points) || !al4(q0)) return lt_bad(fn, "a buffer is not 4-B aligned");
+    if (!al16(layers)) return lt_bad(fn, "layers is not 16-B aligned (a texel's four counts are one store)");
+    if (!texels) return GHR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace);
+    ghr::SvLayersArgs la{};
+    ghr::SvArgs& a = la.a;
+    a.S = S; a.L = L; a.H = Hl; a.W = Wl; a.tiles_x = Y.tiles_x; a.tiles_y = Y.tiles_y;
+    a.n_points = (uint32_t)Y.n_points; a.n_segments = (uint32_t)Y.n_segments;
+    a.near = near_w; a.r = half_width;
+    for (int k = 0; k < 12; k++) a.M[k] = Ml[k];
+    a.points = points;
+    a.proj = reinterpret_cast<float*>(ws + Y.off_proj);
+    a.rec = reinterpret_cast<float*>(ws + Y.off_rec);
+    a.start = reinterpret_cast<uint32_t*>(ws + Y.off_start);
+    a.count = reinterpret_cast<uint32_t*>(ws + Y.off_count);
+    a.nbig = reinterpret_cast<uint32_t*>(ws + Y.off_nbig);
+    a.list = reinterpret_cast<uint32_t*>(ws + Y.off_list);
+    a.big = reinterpret_cast<uint32_t*>(ws + Y.off_big);
+    a.list_cap = (uint32_t)Y.list_cap;
+    la.layer = layer; la.q0 = q0; la.layers = layers;
+    GHR_HIP(hipMemsetAsync(ws + Y.off_fill, 0, (size_t)Y.fill_bytes, s));
+    if (a.n_segments) {
+        hipLaunchKernelGGL(ghr::k_sv_project, dim3(sv_blocks(Y.n_points)), dim3(GHR_SV_BLOCK), 0, s, a);
+        hipLaunchKernelGGL(ghr::k_sv_setup, dim3(sv_blocks(Y.n_segments)), dim3(GHR_SV_BLOCK), 0, s, a);
+    }
+    hipLaunchKernelGGL(ghr::k_sv_scan, dim3(1), dim3(GHR_SV_BLOCK), 0, s, a);
+    if (a.n_segments) hipLaunchKernelGGL(ghr::k_sv_scatter, dim3(sv_blocks(Y.n_segments)), dim3(GHR_SV_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_sv_layers, dim3((unsigned)Y.tiles_x, (unsigned)Y.tiles_y), dim3(GHR_SV_BLOCK), 0, s, la);
+    return finish(s, 0);
+}
+
+int ghr_strandview_shade_shadowed(void* stream, int32_t S, int32_t L, const float* points, int32_t V, const float* vertices, int32_t F,
+                                  const int32_t* faces, int32_t H, int32_t W, const int32_t* pix_to_segment,
+                                  const int32_t* pix_to_face_out, const float* t, int32_t mode, const ghr_strandview_shading* shading,
+                                  const float* base, const ghr_strandview_shadow* shadow, uint8_t* rgb)
+{
+    static const char* fn = "ghr_strandview_shade_shadowed: %s";
+    ghr::SvLayout Y;
+    if (const char* why = ghr::sv_layout(S, L, H, W, &Y)) return lt_bad(fn, why);
+    ghr::VisLayout VL;
+    if (const char* why = ghr::vis_layout(V, F, H, W, &VL)) return lt_bad(fn, why);
+    if (mode != GHR_SV_KAJIYA && mode != GHR_SV_TANGENT) return lt_bad(fn, "mode is neither GHR_STRANDVIEW_KAJIYA nor GHR_STRANDVIEW_TANGENT");
+    if (!shading) return lt_bad(fn, "shading is NULL");
+    if (shading->shininess_log2 < 0 || shading->shininess_log2 > GHR_SV_MAX_SHININESS_LOG2) return lt_bad(fn, "shininess_log2 is outside 0 .. 16");
+    if (!shadow) return lt_bad(fn, "shadow is NULL");
+    if (shadow->Hl < 0 || shadow->Wl < 0) return lt_bad(fn, "negative size of the light map");
+    if ((uint64_t)shadow->Hl * (uint64_t)shadow->Wl > 0x7fffffffull) return lt_bad(fn, "Hl * Wl exceeds 32-bit offsets");
+    if (!(shadow->near_w >= 0.f)) return lt_bad(fn, "near of the light view is negative or NaN");
+    if (!(ghr::vis_finite(shadow->layer) && shadow->layer > 0.f)) return lt_bad(fn, "layer is not finite and > 0");
+    if (!(ghr::vis_finite(shadow->kappa) && shadow->kappa >= 0.f)) return lt_bad(fn, "kappa is negative or not finite");
+    if (!(ghr::vis_finite(shadow->bias) && shadow->bias >= 0.f)) return lt_bad(fn, "shadow bias is negative or not finite");
+    const bool texels = (int64_t)shadow->Hl * shadow->Wl > 0;
+    if (texels && (!shadow->q0 || !shadow->layers)) return lt_bad(fn, "q0 or layers of the light map is NULL");
+    if (!al4(shadow->q0) || !al4(shadow->qfl)) return lt_bad(fn, "a buffer is not 4-B aligned");
+    if (!al16(shadow->layers)) return lt_bad(fn, "layers is not 16-B aligned");
+    if (S && !points) return lt_bad(fn, "points is NULL");
+    if (V && !vertices) return lt_bad(fn, "vertices is NULL");
+    if (F && !faces) return lt_bad(fn, "faces is NULL");
+    const uint64_t N = (uint64_t)H * (uint64_t)W;
+    if (N == 0) return GHR_OK;
+    if (!pix_to_segment || !pix_to_face_out) return lt_bad(fn, "pix_to_segment or pix_to_face_out is NULL");
+    if (!t) return lt_bad(fn, "t is NULL");
+    if (!rgb) return lt_bad(fn, "rgb is NULL");
+    if (!al4(points) || !al4(vertices) || !al4(faces) || !al4(pix_to_segment) || !al4(pix_to_face_out) || !al4(t) || !al4(base))
+        return lt_bad(fn, "a buffer is not 4-B aligned");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::SvShadeShadowedArgs sa{};
+    ghr::SvShadeArgs& a = sa.a;
+    a.S = S; a.L = L; a.V = V; a.F = F; a.H = H; a.W = W; a.mode = mode;
+    memcpy(&a.sh, shading, sizeof(a.sh));
+    a.points = points; a.vertices = vertices; a.faces = faces; a.base = base;
+    a.pix_to_segment = pix_to_segment; a.pix_to_face_out = pix_to_face_out; a.rgb = rgb;
+    sa.t = t;
+    memcpy(&sa.sd, shadow, sizeof(sa.sd));
+    hipLaunchKernelGGL(ghr::k_sv_shade_shadowed, dim3(sv_blocks(N)), dim3(GHR_SV_BLOCK), 0, s, sa);
+    return finish(s, 0);
+}
+
 }  // extern "C"
 
 // ---- the strand stage's prior term: guiding strands' local frames and the latent texture (include/ghr.h; csrc/ghr_sds.h) ------

@@ -45,6 +45,36 @@
 //       eye and Lw are formed on the host in double and rounded once.
 //   Supersampling s in {1, 2, 4}: rows 0 and 1 of M and r are multiplied by s (exact: a power of two), 8h's raster, this raster
 //       and the shade run at sH x sW, and sv_resolve_one writes (sum of the s x s bytes + s s / 2) / (s s) per channel, in integers.
+//   Self-shadowing: a deep opacity map (Yuksel & Keyser 2008) -- per texel of a LIGHT view, the strands in front of a
+//       point counted in four layers behind the first one.  Integer counts and float32 + - x / only; 1 / x is the IEEE division.
+//       Light view: (Ml[12], Hl, Wl, near), a view as above (perspective: q = 1 / w orders depth), texel centres at + 0.5.
+//       Front plane q0 [Hl][Wl]: the largest qs over the segments that COVER the texel's centre (the coverage rule above with the
+//           light half-width rl, in texels); a qs that is NaN or not > 0 never counts; 0 where there is none.
+//       Layer counts, layers [Hl][Wl][4] uint32: every segment that covers the centre with a counted qs has
+//           u = 1 / qs - 1 / q0  (>= 0: division is monotone)  and adds 1 to layer 0 if u < d, else to layer 1 if u < 3 d, else to
+//           layer 2 if u < 7 d, else to layer 3 (sv_layer_of); d = `layer`, a depth in the light's w units, finite and > 0; 3 d and
+//           7 d are 3.f * d and 7.f * d.  Integer sums of a set: chunking, binning and traversal order cannot change a bit;
+//           duplicated segments each count.
+//       Lookup of a world point P (the occluders in front of it, sv_occluders): P is projected by Ml to (lx, ly, ql, valid).
+//           n = 0 when P is not valid, when  lx >= 0 && lx < (float)Wl && ly >= 0 && ly < (float)Hl  is false, when q0 == 0 at
+//           texel (i, j) = ((int)ly, (int)lx), or when  u = 1 / ql - 1 / q0  is not > 0.  Otherwise, with c0 = n0, c1 = c0 + n1,
+//           c2 = c1 + n2 as integers, every count clamped to 2^24 and converted to float:
+//               u < d:    n = c0 (u / d)
+//               u < 3 d:  n = c0 + n1 ((u - d) / (2.f d))
+//               u < 7 d:  n = c1 + n2 ((u - 3.f d) / (4.f d))
+//               else:     n = c2 + n3 fminf((u - 7.f d) / (8.f d), 1.f)
+//           A point's own segment is in the counts; at u ~ 0 its share is ~ 0: the method's answer to self-shadowing acne.
+//       Head as an occluder: qfl [Hl][Wl] is 8h's pix_to_face of the mesh in the light view put through the face depth above (or
+//           absent: no mesh).  P is BEHIND THE HEAD iff qfl > 0 at its texel and  ql (1.f + shadow_bias) < qfl.
+//       Transmittance: Tr = 0 behind the head, else Tr = 1.f / (1.f + kappa n); Tr == 1 exactly where n == 0.
+//       Shading with shadows (kajiya only; tangent mode and the background are untouched):
+//           strand pixel (winner k, t from the t plane): P = A + t (B - A) per component;
+//               colour = base (ambient + kd (Tr diffuse)) + ks (Tr spec);
+//           head pixel: P = ((v0 + v1) + v2) / 3.f per component (flat shading: the shadow is per face);
+//               colour = head_rgb (ambient + kd (Tr |n.Lw|)).
+//           With Tr == 1 these are the unshadowed bytes: 1.f x == x.
+//       Look constants (defaults of the keywords, CHOSEN here like ambient and kd, not measured): light map 1024 x 1024, rl 1.0 texel,
+//           kappa 0.2, shadow_bias 0.02, d = rho / 32 with rho the radius of the bounding sphere the light camera is fitted to.
 //
 // Per frame (ghr_strandview_raster): one fill of the tile counters, then
 //   k_sv_project   one thread per point: {sx, sy, q, valid}, 16 B
@@ -62,6 +92,11 @@
 //                  none of whose lanes is in a record's widened box skips it by ballot; pix_to_face / qf are read once.
 // and, on their own entries: k_sv_face_depth (one thread per pixel: qf), k_sv_shade (one thread per pixel: it gathers the winner's
 // two world points or the face's three vertices), k_sv_resolve (one thread per output pixel).  Integer atomics only.
+// The light pass (ghr_strandview_opacity) is the same fill, k_sv_project, k_sv_setup, k_sv_scan and k_sv_scatter in the light view, then
+//   k_sv_layers    k_sv_raster's shape, but the lists are walked TWICE in one launch: walk 1 keeps the largest qs in a register,
+//                  walk 2 re-tests coverage and classifies every covering segment against that register into four counters in
+//                  registers; the epilogue writes q0 (4 B) and the four counts as one 16-B store.  No atomics, no pix_to_face.
+// and k_sv_shade_shadowed (one thread per camera pixel, behind ghr_strandview_shade_shadowed) is k_sv_shade with the lookup.
 // Everything per element is GHR_HD so that tests/hostsim/ghr_hostsim_strandview.cpp runs the product's own arithmetic on the CPU.
 #pragma once
 #include "ghr_visibility.h"
@@ -246,6 +281,114 @@ GHR_HD void sv_shade_one(int32_t seg, int32_t face, int S, int L, const float* p
         }
     }
     for (int c = 0; c < 3; c++) rgb[c] = (uint8_t)sv_quant8(sh.background_rgb[c]);
+}
+
+// ---- self-shadowing: the deep opacity map of the light view -------------------------------------------------------------------
+// == ghr_strandview_shadow of include/ghr.h
+struct SvShadow {
+    float Ml[12];
+    float near_w;
+    int32_t Hl, Wl;
+    float layer, kappa, bias;
+    const float* q0;         // [Hl][Wl]
+    const uint32_t* layers;  // [Hl][Wl][4]
+    const float* qfl;        // [Hl][Wl] or NULL: no mesh
+};
+
+// The layer of a covering segment u = 1 / qs - 1 / q0 behind the front plane.
+GHR_HD int sv_layer_of(float u, float d)
+{
+    if (u < d) return 0;
+    if (u < 3.f * d) return 1;
+    if (u < 7.f * d) return 2;
+    return 3;
+}
+
+GHR_HD float sv_count_float(uint32_t c) { return (float)(c < (1u << 24) ? c : (1u << 24)); }
+
+// The occluders in front of a point of inverse depth ql at a texel with front plane q0 and the four counts n4.
+GHR_HD float sv_occluders(float ql, float q0, const uint32_t* n4, float d)
+{
+    if (q0 == 0.f) return 0.f;
+    const float u = 1.f / ql - 1.f / q0;
+    if (!(u > 0.f)) return 0.f;
+    const uint32_t i0 = n4[0], i1 = i0 + n4[1], i2 = i1 + n4[2];
+    const float c0 = sv_count_float(i0), c1 = sv_count_float(i1), c2 = sv_count_float(i2);
+    if (u < d) return c0 * (u / d);
+    if (u < 3.f * d) return c0 + sv_count_float(n4[1]) * ((u - d) / (2.f * d));
+    if (u < 7.f * d) return c1 + sv_count_float(n4[2]) * ((u - 3.f * d) / (4.f * d));
+    return c2 + sv_count_float(n4[3]) * fminf((u - 7.f * d) / (8.f * d), 1.f);
+}
+
+GHR_HD float sv_transmittance(float n, float kappa, bool behind_head) { return behind_head ? 0.f : 1.f / (1.f + kappa * n); }
+
+// Tr of a world point P; *n_out (may be NULL) gets the occluders in front of it (0 where the point has no texel).
+GHR_HD float sv_shadow_at(const SvShadow& sd, const float* P, float* n_out)
+{
+    float o[4], n = 0.f;
+    bool behind = false;
+    vis_project_one(sd.Ml, P, sd.near_w, o);
+    if (o[3] != 0.f && o[0] >= 0.f && o[0] < (float)sd.Wl && o[1] >= 0.f && o[1] < (float)sd.Hl) {
+        const size_t e = (size_t)(int)o[1] * (size_t)sd.Wl + (size_t)(int)o[0];  // (0 <= (int)x < the size: x is in [0, size))
+        const float qfl = sd.qfl ? sd.qfl[e] : 0.f;
+        behind = qfl > 0.f && o[2] * (1.f + sd.bias) < qfl;
+        const float q0 = sd.q0[e];
+        if (q0 != 0.f) n = sv_occluders(o[2], q0, sd.layers + 4 * e, sd.layer);
+    }
+    if (n_out) *n_out = n;
+    return sv_transmittance(n, sd.kappa, behind);
+}
+
+// sv_shade_strand's kajiya branch with the transmittance on the two light terms
+GHR_HD void sv_shade_strand_shadowed(const float* A, const float* B, const float* base, const SvShading& sh, float Tr, uint8_t* rgb)
+{
+    const float d[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
+    float T[3];
+    sv_normalise(d, T);
+    const float v[3] = {sh.eye[0] - 0.5f * (A[0] + B[0]), sh.eye[1] - 0.5f * (A[1] + B[1]), sh.eye[2] - 0.5f * (A[2] + B[2])};
+    float Vn[3];
+    sv_normalise(v, Vn);
+    const float cl = sv_dot(T, sh.light), cv = sv_dot(T, Vn);
+    const float sl = sqrtf(fmaxf(0.f, 1.f - cl * cl)), sv = sqrtf(fmaxf(0.f, 1.f - cv * cv));
+    float spec = fmaxf(0.f, cl * cv + sl * sv);
+    for (int k = 0; k < sh.shininess_log2; k++) spec = spec * spec;
+    for (int c = 0; c < 3; c++) rgb[c] = (uint8_t)sv_quant8(base[c] * (sh.ambient + sh.kd * (Tr * sl)) + sh.ks * (Tr * spec));
+}
+
+GHR_HD void sv_shade_head_shadowed(const float* v0, const float* v1, const float* v2, const SvShading& sh, float Tr, uint8_t* rgb)
+{
+    const float e1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]}, e2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
+    const float n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+    float nn[3];
+    sv_normalise(n, nn);
+    const float c = sv_dot(nn, sh.light);
+    const float lit = sh.ambient + sh.kd * (Tr * fmaxf(c, -c));
+    for (int k = 0; k < 3; k++) rgb[k] = (uint8_t)sv_quant8(sh.head_rgb[k] * lit);
+}
+
+// One pixel of the shadowed picture: sv_shade_one with the lookup at the strand point A + t (B - A) or at the face's centroid.
+GHR_HD void sv_shade_one_shadowed(int32_t seg, int32_t face, float t, int S, int L, const float* points, int V, const float* vertices,
+                                  int F, const int32_t* faces, const float* base, int mode, const SvShading& sh, const SvShadow& sd,
+                                  uint8_t* rgb)
+{
+    if (mode == GHR_SV_KAJIYA && seg >= 0 && L >= 2 && (int64_t)seg < (int64_t)S * (L - 1)) {
+        const int s = seg / (L - 1), i = seg % (L - 1);
+        const float* A = points + 3 * ((size_t)s * L + i);
+        const float* B = A + 3;
+        const float P[3] = {A[0] + t * (B[0] - A[0]), A[1] + t * (B[1] - A[1]), A[2] + t * (B[2] - A[2])};
+        sv_shade_strand_shadowed(A, B, base ? base + 3 * (size_t)s : sh.base_rgb, sh, sv_shadow_at(sd, P, nullptr), rgb);
+        return;
+    }
+    if (mode == GHR_SV_KAJIYA && face >= 0 && face < F) {  // (no strand here: the branch above returned)
+        const int32_t* tr = faces + 3 * (size_t)face;
+        if (tr[0] >= 0 && tr[0] < V && tr[1] >= 0 && tr[1] < V && tr[2] >= 0 && tr[2] < V) {
+            const float *v0 = vertices + 3 * (size_t)tr[0], *v1 = vertices + 3 * (size_t)tr[1], *v2 = vertices + 3 * (size_t)tr[2];
+            const float P[3] = {((v0[0] + v1[0]) + v2[0]) / 3.f, ((v0[1] + v1[1]) + v2[1]) / 3.f, ((v0[2] + v1[2]) + v2[2]) / 3.f};
+            sv_shade_head_shadowed(v0, v1, v2, sh, sv_shadow_at(sd, P, nullptr), rgb);
+            return;
+        }
+    }
+    sv_shade_one(seg, face, S, L, points, V, vertices, F, faces, base, mode, sh, rgb);  // tangent mode, the background
 }
 
 // One output pixel of the resolve: src is [s H][s W][3], dst [H][W][3].
@@ -450,6 +593,67 @@ __global__ void __launch_bounds__(GHR_SV_BLOCK) k_sv_raster(SvArgs a)
 #endif
 }
 
+// The light pass's raster: a (H, W, r, the tables) is the light view's; pix_to_face, qf and the four planes of a are not used.
+struct SvLayersArgs {
+    SvArgs a;
+    float layer;
+    float* q0;         // [H][W]
+    uint32_t* layers;  // [H][W][4], 16-B aligned
+};
+typedef uint32_t sv_u4 __attribute__((ext_vector_type(4)));
+
+// One tile per workgroup, one texel per thread; the tile's lists are walked twice: the front plane, then the counts behind it.
+__global__ void __launch_bounds__(GHR_SV_BLOCK) k_sv_layers(SvLayersArgs la)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ f4 s_rec[2 * GHR_SV_CHUNK];
+    const SvArgs& a = la.a;
+    const uint32_t tile = blockIdx.y * (uint32_t)a.tiles_x + blockIdx.x;
+    const int i = (int)blockIdx.y * GHR_SV_TILE + (int)threadIdx.x / GHR_SV_TILE;
+    const int j = (int)blockIdx.x * GHR_SV_TILE + (int)threadIdx.x % GHR_SV_TILE;
+    const bool in_image = i < a.H && j < a.W;
+    const float px = (float)j + 0.5f, py = (float)i + 0.5f;
+    const uint32_t beg = a.start[tile], n_own = a.start[tile + 1] - beg;
+    const uint32_t n_big = a.n_segments > 0u ? min(*a.nbig, a.n_segments) : 0u;
+    const uint32_t n = n_own + n_big;  // (workgroup-uniform)
+    float best_q = 0.f, inv_q0 = 0.f;
+    uint32_t n0 = 0u, n1 = 0u, n2 = 0u, n3 = 0u;
+    for (int walk = 0; walk < 2; walk++) {
+        if (walk == 1) inv_q0 = 1.f / best_q;  // (read only behind a covering segment with qs > 0: then best_q > 0)
+        for (uint32_t c0 = 0u; c0 < n; c0 += GHR_SV_CHUNK) {
+            const uint32_t m = min((uint32_t)GHR_SV_CHUNK, n - c0);
+            if (threadIdx.x < 2u * m) {
+                const uint32_t k = threadIdx.x / 2u, part = threadIdx.x % 2u, e = c0 + k;
+                // (the clamps of k_sv_raster: a workspace wrongly shared by two streams never indexes outside itself)
+                uint32_t id = e < n_own ? a.list[min(beg + e, a.list_cap - 1u)] : a.big[e - n_own];
+                id = min(id, a.n_segments - 1u);
+                s_rec[2u * k + part] = reinterpret_cast<const f4*>(a.rec)[2 * (size_t)id + part];
+            }
+            __syncthreads();
+            for (uint32_t k = 0u; k < m; k++) {
+                const f4 r0 = s_rec[2u * k], r1 = s_rec[2u * k + 1u];  // (one address per wave: broadcast)
+                const float r[GHR_SV_REC_WORDS] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+                const bool box = in_image && sv_in_box(r, a.r, px, py);
+                if (__builtin_amdgcn_ballot_w64(box) == 0ull) continue;  // nobody in this wave is inside the widened box
+                float t, q;
+                if (!(box && sv_covers(r, a.r, px, py, &t, &q))) continue;
+                if (walk == 0) {
+                    if (q > best_q) best_q = q;  // (a NaN or a q that is not > 0 never gets in)
+                } else if (q > 0.f) {
+                    const int layer = sv_layer_of(1.f / q - inv_q0, la.layer);
+                    n0 += layer == 0 ? 1u : 0u; n1 += layer == 1 ? 1u : 0u; n2 += layer == 2 ? 1u : 0u; n3 += layer == 3 ? 1u : 0u;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (!in_image) return;
+    const size_t o = (size_t)i * a.W + j;
+    la.q0[o] = best_q;
+    reinterpret_cast<sv_u4*>(la.layers)[o] = sv_u4{n0, n1, n2, n3};
+#endif
+}
+
 struct SvFaceDepthArgs {
     int32_t V, F, H, W;
     float near;
@@ -490,6 +694,25 @@ __global__ void __launch_bounds__(GHR_SV_BLOCK) k_sv_shade(SvShadeArgs a)
     uint8_t rgb[3];
     sv_shade_one(a.pix_to_segment[o], a.pix_to_face_out[o], a.S, a.L, a.points, a.V, a.vertices, a.F, a.faces, a.base, a.mode, a.sh,
                  rgb);
+    a.rgb[3 * (size_t)o] = rgb[0]; a.rgb[3 * (size_t)o + 1] = rgb[1]; a.rgb[3 * (size_t)o + 2] = rgb[2];
+#endif
+}
+
+struct SvShadeShadowedArgs {
+    SvShadeArgs a;
+    const float* t;  // [H][W]: the raster's t plane
+    SvShadow sd;
+};
+
+__global__ void __launch_bounds__(GHR_SV_BLOCK) k_sv_shade_shadowed(SvShadeShadowedArgs sa)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const SvShadeArgs& a = sa.a;
+    const uint32_t o = blockIdx.x * GHR_SV_BLOCK + threadIdx.x;
+    if (o >= (uint32_t)a.H * (uint32_t)a.W) return;
+    uint8_t rgb[3];
+    sv_shade_one_shadowed(a.pix_to_segment[o], a.pix_to_face_out[o], sa.t[o], a.S, a.L, a.points, a.V, a.vertices, a.F, a.faces, a.base,
+                          a.mode, a.sh, sa.sd, rgb);
     a.rgb[3 * (size_t)o] = rgb[0]; a.rgb[3 * (size_t)o + 1] = rgb[1]; a.rgb[3 * (size_t)o + 2] = rgb[2];
 #endif
 }

@@ -8,6 +8,10 @@ comparator on any device: the same float32 expressions in the same operand order
 whose widened box meets the chunk's pixel range -- the tile lists change which segments a pixel looks at, never the winner.
 The definition is this package's own and is stated at the top of ``csrc/ghr_strandview.h``.  A view is ``(M, H, W)`` as in
 ``visibility.py``.
+
+Self-shadowing is a deep opacity map of a light view: ``light_view`` fits a perspective light camera to the groom,
+``strand_shadow_map`` makes the map (``ghr_strandview_opacity``, or the composed form), and ``render_strands(shadows=...)`` shades
+with the transmittance it gives.  ``shadows=False`` (the default) is the unshadowed path, launch for launch.
 """
 from __future__ import annotations
 
@@ -25,6 +29,9 @@ MODES = {"kajiya": _lib.STRANDVIEW_KAJIYA, "tangent": _lib.STRANDVIEW_TANGENT}
 AMBIENT, KD, KS, SHININESS_LOG2 = 0.25, 0.65, 0.35, 5
 HAIR_RGB, HEAD_RGB, BACKGROUND_RGB = (0.45, 0.30, 0.18), (0.62, 0.62, 0.62), (1.0, 1.0, 1.0)
 LIGHT_CAMERA = (0.45, -0.60, -0.66)  # camera axes (x right, y down, z forward): above and to the right of the camera
+# the look constants of the shadows (chosen, not measured): the light map's size, the half-width in texels, kappa, the bias of the
+# head's shadow, and the layer depth as a fraction of the bounding sphere's radius
+SHADOW_SIZE, SHADOW_HALF_WIDTH, SHADOW_KAPPA, SHADOW_BIAS, SHADOW_LAYERS_PER_RADIUS = 1024, 1.0, 0.2, 0.02, 32
 
 
 # ---------------------------------------------------------------------------------------------------------------- helpers
@@ -222,8 +229,9 @@ def _quant8(x):
     return torch.fmin(torch.fmax(x * 255.0 + 0.5, zero), zero + 255).to(torch.uint8)
 
 
-def _shade_torch(points, v, f, H, W, seg, face, mode, sh, base=None):
-    """uint8 [H, W, 3] of the definition; v / f may be None (no mesh)"""
+def _shade_torch(points, v, f, H, W, seg, face, mode, sh, base=None, t=None, shadow=None, kappa=0.0, bias=0.0):
+    """uint8 [H, W, 3] of the definition; v / f may be None (no mesh).  ``shadow``: a ShadowMap (with ``t``, the raster's t plane):
+    the kajiya terms are multiplied by the transmittance; None: the unshadowed expressions."""
     dev = seg.device
     N = H * W
     S, L = points.shape[0], points.shape[1]
@@ -251,7 +259,12 @@ def _shade_torch(points, v, f, H, W, seg, face, mode, sh, base=None):
             for _ in range(int(sh["shininess_log2"])):
                 spec = spec * spec
             b = base[s] if base is not None else sc["base_rgb"][None].expand(len(on), 3)
-            col = [b[:, c] * (sc["ambient"] + sc["kd"] * sl) + sc["ks"] * spec for c in range(3)]
+            if shadow is not None:
+                tk = t.reshape(-1)[on]
+                Tr = _transmittance_torch([A[:, c] + tk * (B[:, c] - A[:, c]) for c in range(3)], shadow, kappa, bias)
+                col = [b[:, c] * (sc["ambient"] + sc["kd"] * (Tr * sl)) + sc["ks"] * (Tr * spec) for c in range(3)]
+            else:
+                col = [b[:, c] * (sc["ambient"] + sc["kd"] * sl) + sc["ks"] * spec for c in range(3)]
         out[on] = torch.stack([_quant8(c) for c in col], dim=1)
     if v is not None and f is not None and f.shape[0] and v.shape[0]:
         hd = ~((seg >= 0) & (seg < S * (L - 1))) & (face >= 0) & (face < f.shape[0])
@@ -264,9 +277,109 @@ def _shade_torch(points, v, f, H, W, seg, face, mode, sh, base=None):
             e1, e2 = [v1[:, c] - v0[:, c] for c in range(3)], [v2[:, c] - v0[:, c] for c in range(3)]
             n = _normalise([e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]])
             c = _dot(n, [sc["light"][k] for k in range(3)])
-            lit = sc["ambient"] + sc["kd"] * torch.fmax(c, -c)
+            if shadow is not None and mode != _lib.STRANDVIEW_TANGENT:
+                Tr = _transmittance_torch([_div((v0[:, k] + v1[:, k]) + v2[:, k], 3.0) for k in range(3)], shadow, kappa, bias)
+                lit = sc["ambient"] + sc["kd"] * (Tr * torch.fmax(c, -c))
+            else:
+                lit = sc["ambient"] + sc["kd"] * torch.fmax(c, -c)
             out[on] = torch.stack([_quant8(sc["head_rgb"][k] * lit) for k in range(3)], dim=1)
     return out.reshape(H, W, 3)
+
+
+def _div(a, b):
+    """a / b for a float b as a tensor division (a division by a host scalar may be evaluated as a product with 1 / b)"""
+    return a / torch.full_like(a, float(np.float32(b)))
+
+
+def _opacity_torch(points, Ml, Hl, Wl, rl, layer, near, chunk_elems=None):
+    """(q0 float32 [Hl, Wl], layers int32 [Hl, Wl, 4]) of the definition, brute force like _rasterize_torch: integer sums over
+    the covering mask, texel chunk by texel chunk"""
+    dev = points.device
+    N = Hl * Wl
+    q0 = torch.zeros(N, dtype=torch.float32, device=dev)
+    layers = torch.zeros((N, 4), dtype=torch.int32, device=dev)
+    S, L = points.shape[0], points.shape[1]
+    K = S * (L - 1)
+    if N and K:
+        if chunk_elems is None:
+            chunk_elems = 1 << (25 if dev.type == "cuda" else 21)
+        m = [float(x) for x in _m12(Ml)]
+        r32 = float(np.float32(rl))
+        rr = float(np.float32(rl) * np.float32(rl))
+        d1 = np.float32(layer)
+        d1, d3, d7 = float(d1), float(np.float32(3) * d1), float(np.float32(7) * d1)
+        sx, sy, q, valid = _project_torch(points, m, float(np.float32(near)))
+        ax, ay, qa = sx[:, :-1].reshape(-1), sy[:, :-1].reshape(-1), q[:, :-1].reshape(-1)
+        bx, by, qb = sx[:, 1:].reshape(-1), sy[:, 1:].reshape(-1), q[:, 1:].reshape(-1)
+        exists = (valid[:, :-1] & valid[:, 1:]).reshape(-1)
+        ulo, uhi = torch.fmin(ax, bx) - r32, torch.fmax(ax, bx) + r32
+        vlo, vhi = torch.fmin(ay, by) - r32, torch.fmax(ay, by) + r32
+        dx, dy, dq = bx - ax, by - ay, qb - qa
+        len2 = dx * dx + dy * dy
+        zero = torch.zeros((), dtype=torch.float32, device=dev)
+        chunk = max(1, chunk_elems // K)
+        for s0 in range(0, N, chunk):
+            p = torch.arange(s0, min(s0 + chunk, N), device=dev)
+            px = ((p % Wl).float() + 0.5)[:, None]
+            py = ((p // Wl).float() + 0.5)[:, None]
+            sid = torch.nonzero(exists & (uhi >= px.min()) & (ulo <= px.max()) & (vhi >= py.min()) & (vlo <= py.max()))[:, 0]
+            if sid.numel() == 0:
+                continue
+            cax, cay, cdx, cdy, cl2 = ax[sid], ay[sid], dx[sid], dy[sid], len2[sid]
+            t = ((px - cax) * cdx + (py - cay) * cdy) / cl2
+            t = torch.fmin(torch.fmax(t, zero), zero + 1)
+            t = torch.where((cl2 == 0) | torch.isnan(t), zero, t)
+            ex, ey = px - (cax + t * cdx), py - (cay + t * cdy)
+            covers = (px >= ulo[sid]) & (px <= uhi[sid]) & (py >= vlo[sid]) & (py <= vhi[sid]) & (ex * ex + ey * ey <= rr)
+            qs = qa[sid] + t * dq[sid]
+            counted = covers & (qs > 0)
+            qs = torch.where(counted, qs, zero + 1)
+            front = torch.where(counted, qs, zero).max(dim=1).values
+            u = torch.ones_like(qs) / qs - (torch.ones_like(front) / front)[:, None]
+            lay = torch.where(u < d1, 0, torch.where(u < d3, 1, torch.where(u < d7, 2, 3)))
+            q0[p] = front
+            layers[p] = torch.stack([(counted & (lay == k)).sum(dim=1) for k in range(4)], dim=1).to(torch.int32)
+    return q0.reshape(Hl, Wl), layers.reshape(Hl, Wl, 4)
+
+
+def _occluders_torch(P, shadow):
+    """(n float32, ql, the texel's index, inside) of the lookup for the world points P = [x, y, z] (three float32 tensors)"""
+    Hl, Wl = shadow.Hl, shadow.Wl
+    dev = P[0].device
+    m = [float(x) for x in _m12(shadow.Ml)]
+    lx, ly, ql, valid = _project_torch(torch.stack(P, dim=-1), m, float(np.float32(shadow.near)))
+    zero = torch.zeros_like(ql)
+    if Hl * Wl == 0:
+        return zero, ql, torch.zeros_like(ql, dtype=torch.int64), torch.zeros_like(valid)
+    inside = valid & (lx >= 0) & (lx < float(np.float32(Wl))) & (ly >= 0) & (ly < float(np.float32(Hl)))
+    e = torch.where(inside, ly, zero).long() * Wl + torch.where(inside, lx, zero).long()
+    q0 = shadow.q0.reshape(-1)[e]
+    n4 = shadow.layers.reshape(-1, 4)[e].long() & 0xffffffff
+    u = torch.ones_like(ql) / ql - torch.ones_like(q0) / q0
+    ok = inside & (q0 != 0) & (u > 0)
+    cnt = lambda x: torch.clamp(x, max=1 << 24).float()  # noqa: E731
+    i0 = n4[:, 0]
+    i1 = (i0 + n4[:, 1]) & 0xffffffff
+    i2 = (i1 + n4[:, 2]) & 0xffffffff
+    c0, c1, c2 = cnt(i0), cnt(i1), cnt(i2)
+    d = np.float32(shadow.layer)
+    k = lambda x: float(np.float32(x) * d)  # noqa: E731
+    d1, d3, d7 = float(d), k(3), k(7)
+    n = torch.where(u < d1, c0 * _div(u, d1),
+                    torch.where(u < d3, c0 + cnt(n4[:, 1]) * _div(u - d1, k(2)),
+                                torch.where(u < d7, c1 + cnt(n4[:, 2]) * _div(u - d3, k(4)),
+                                            c2 + cnt(n4[:, 3]) * torch.fmin(_div(u - d7, k(8)), zero + 1))))
+    return torch.where(ok, n, zero), ql, e, inside
+
+
+def _transmittance_torch(P, shadow, kappa, bias):
+    n, ql, e, inside = _occluders_torch(P, shadow)
+    Tr = torch.ones_like(n) / (1.0 + float(np.float32(kappa)) * n)
+    if shadow.qfl is not None and shadow.Hl * shadow.Wl:
+        qfl = shadow.qfl.reshape(-1)[e]
+        behind = inside & (qfl > 0) & (ql * float(np.float32(1) + np.float32(bias)) < qfl)
+        Tr = torch.where(behind, torch.zeros_like(Tr), Tr)
+    return Tr
 
 
 def _resolve_torch(src, H, W, s):
@@ -347,6 +460,72 @@ def _shade_fused(pts, v, f32, H, W, seg, face, mode, sh, base):
     return rgb
 
 
+_light_frames = None   # the light pass's buffers, cached per (S, L, Hl, Wl, V, F) and device like the camera's
+
+
+def _light_frames_for(S, L, Hl, Wl, V, Fc, dev):
+    global _light_frames
+    key = (S, L, Hl, Wl, V, Fc, str(dev))
+    if _light_frames is None or _light_frames.key != key:
+        _light_frames = None
+        _light_frames = _Frames(key, dev)
+    return _light_frames
+
+
+def _opacity_fused(pts, v, f32, Ml, Hl, Wl, rl, layer, near):
+    """(q0, layers, qfl or None) of the light view on the device"""
+    from .diff_gaussian_rasterization import _on_device, _ptr, _stream
+    dev = pts.device
+    S, L = pts.shape[0], pts.shape[1]
+    V, Fc = (v.shape[0], f32.shape[0]) if v is not None else (0, 0)
+    fr = _light_frames_for(S, L, Hl, Wl, V, Fc, dev)
+    q0 = torch.empty((Hl, Wl), dtype=torch.float32, device=dev)
+    layers = torch.empty((Hl, Wl, 4), dtype=torch.int32, device=dev)
+    Mc = _mc(Ml)
+    qfl = None
+    pix = None
+    if Fc and Hl * Wl:
+        pix, _ = vis._view_fused(v, f32, Ml, Hl, Wl, near, None, None, fr.vis_ws, None, None)
+    with _on_device(dev):
+        L_ = _lib.lib()
+        if pix is not None:
+            qfl = torch.empty((Hl, Wl), dtype=torch.float32, device=dev)
+            _lib.check(L_.ghr_strandview_face_depth(_stream(), V, _ptr(v) if V else None, Fc, _ptr(f32), ctypes.byref(Mc), float(near),
+                                                    Hl, Wl, _ptr(pix), _ptr(qfl)))
+        _lib.check(L_.ghr_strandview_opacity(_stream(), S, L, _ptr(pts) if S else None, ctypes.byref(Mc), float(near), Hl, Wl, float(rl),
+                                             float(layer), _ptr(fr.ws), fr.ws.numel(), _ptr(q0) if Hl * Wl else None,
+                                             _ptr(layers) if Hl * Wl else None))
+    return q0, layers, qfl
+
+
+def _shadow_struct(shadow, kappa, bias):
+    from .diff_gaussian_rasterization import _ptr
+    s = _lib.StrandViewShadow()
+    s.Ml = (ctypes.c_float * 12)(*[float(x) for x in _m12(shadow.Ml)])
+    s.near_w, s.Hl, s.Wl = float(shadow.near), int(shadow.Hl), int(shadow.Wl)
+    s.layer, s.kappa, s.bias = float(shadow.layer), float(kappa), float(bias)
+    n = shadow.Hl * shadow.Wl
+    s.q0 = _ptr(shadow.q0) if n else None
+    s.layers = _ptr(shadow.layers) if n else None
+    s.qfl = _ptr(shadow.qfl) if n and shadow.qfl is not None else None
+    return s
+
+
+def _shade_shadowed_fused(pts, v, f32, H, W, seg, face, t, mode, sh, base, shadow, kappa, bias):
+    from .diff_gaussian_rasterization import _on_device, _ptr, _stream
+    dev = pts.device
+    S, L = pts.shape[0], pts.shape[1]
+    V, Fc = (v.shape[0], f32.shape[0]) if v is not None else (0, 0)
+    rgb = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    st, sd = _shading_struct(sh), _shadow_struct(shadow, kappa, bias)
+    with _on_device(dev):
+        _lib.check(_lib.lib().ghr_strandview_shade_shadowed(
+            _stream(), S, L, _ptr(pts) if S else None, V, _ptr(v) if V else None, Fc, _ptr(f32) if Fc else None, H, W,
+            _ptr(seg) if H * W else None, _ptr(face) if H * W else None, _ptr(t) if H * W else None, int(mode), ctypes.byref(st),
+            _ptr(base) if base is not None else None, ctypes.byref(sd), _ptr(rgb) if H * W else None))
+    return rgb
+
+
 def _resolve_fused(src, H, W, s):
     from .diff_gaussian_rasterization import _on_device, _ptr, _stream
     dst = torch.empty((H, W, 3), dtype=torch.uint8, device=src.device)
@@ -392,11 +571,117 @@ def rasterize_strands(points, M, H, W, mesh=None, half_width: float = 0.75, head
     return _rasterize(pts, v, f32, M, int(H), int(W), half_width, head_bias, near, fused)
 
 
+def _bounding_sphere(points, mesh):
+    """(centre float64 [3], radius) of the finite points and mesh vertices: the centre of their bounds, the largest distance from
+    it; (0, 1) when there is nothing (or a single place)"""
+    parts = [points if isinstance(points, torch.Tensor) else torch.from_numpy(np.array(points, np.float32))]
+    if mesh is not None:
+        mv = mesh.vertices if hasattr(mesh, "vertices") else mesh[0]
+        parts.append(mv if isinstance(mv, torch.Tensor) else torch.from_numpy(np.array(mv, np.float32)))
+    lo, hi = np.full(3, np.inf), np.full(3, -np.inf)
+    kept = []
+    for p in parts:
+        p = p.detach().reshape(-1, 3)
+        p = p[torch.isfinite(p).all(dim=1)].double()
+        if p.shape[0]:
+            kept.append(p)
+            lo, hi = np.minimum(lo, p.min(dim=0).values.cpu().numpy()), np.maximum(hi, p.max(dim=0).values.cpu().numpy())
+    if not kept:
+        return np.zeros(3), 1.0
+    c = (lo + hi) / 2
+    rho = max(float(((p - torch.from_numpy(c).to(p.device)) ** 2).sum(dim=1).max().sqrt()) for p in kept)
+    return c, (rho if np.isfinite(rho) and rho > 0 else 1.0)
+
+
+def light_view(points, mesh=None, light=None, view=None, size=SHADOW_SIZE, distance: float = 8.0):
+    """A perspective light camera fitted to the groom: ``(Ml float32 [3, 4], Hl, Wl, rho)``.  The finite points and mesh vertices
+    get a bounding sphere (the centre of their bounds, radius ``rho``); the camera sits ``distance * rho`` from the centre along
+    ``light`` (a world vector towards the light; default: ``shading_for_view(view)["light"]``, the vector the shading uses) and
+    looks at the centre; the focal length makes the sphere fit the map with a margin of two texels.  ``size``: the map's side, or
+    (Hl, Wl).  In double on the host, rounded once."""
+    Hl, Wl = (int(size), int(size)) if np.ndim(size) == 0 else (int(size[0]), int(size[1]))
+    if min(Hl, Wl) < 6:
+        raise ValueError("light_view: the light map needs at least 6 texels a side (a margin of two on either side)")
+    if not distance > 1.0:
+        raise ValueError("light_view: distance must be > 1 (the camera sits outside the bounding sphere)")
+    if light is None:
+        if view is None:
+            raise ValueError("light_view: give light, or view for the shading's own light")
+        light = shading_for_view(view[0] if isinstance(view, (tuple, list)) and len(view) == 3 else view)["light"]
+    lw = np.asarray(light, np.float64).reshape(3)
+    lw = lw / np.linalg.norm(lw)
+    c, rho = _bounding_sphere(points, mesh)
+    z = -lw                                        # the camera looks from the light at the centre
+    up = np.eye(3)[int(np.argmin(np.abs(lw)))]     # the world axis farthest from the light's direction
+    x = np.cross(z, up)
+    x /= np.linalg.norm(x)
+    R = np.stack([x, np.cross(z, x), z])
+    eye = c + distance * rho * lw
+    f = (min(Hl, Wl) / 2.0 - 2.0) * np.sqrt(distance * distance - 1.0)   # the sphere's outline: radius f / sqrt(distance^2 - 1)
+    K = np.array([[f, 0, Wl / 2.0], [0, f, Hl / 2.0], [0, 0, 1.0]])
+    return vis.view_matrix(K, R, -R @ eye).reshape(3, 4), Hl, Wl, rho
+
+
+class ShadowMap:
+    """The deep opacity map of one light view: ``Ml`` float32 [12], ``Hl``, ``Wl``, ``near``, ``q0`` float32 [Hl, Wl], ``layers``
+    int32 [Hl, Wl, 4] (the bits of the uint32 counts), ``qfl`` float32 [Hl, Wl] or None (no mesh), and ``layer``."""
+    __slots__ = ("Ml", "Hl", "Wl", "near", "q0", "layers", "qfl", "layer")
+
+    def __init__(self, Ml, Hl, Wl, near, q0, layers, qfl, layer):
+        self.Ml, self.Hl, self.Wl, self.near, self.q0, self.layers, self.qfl, self.layer = _m12(Ml), Hl, Wl, near, q0, layers, qfl, layer
+
+
+def _check_shadow_scalars(half_width, layer, kappa, bias):
+    if not (np.isfinite(half_width) and half_width > 0):
+        raise ValueError("strand_view: the shadow half_width must be finite and > 0")
+    if not (np.isfinite(layer) and layer > 0):
+        raise ValueError("strand_view: the shadow layer must be finite and > 0")
+    if not (np.isfinite(kappa) and kappa >= 0):
+        raise ValueError("strand_view: shadow_kappa must be finite and >= 0")
+    if not (np.isfinite(bias) and bias >= 0):
+        raise ValueError("strand_view: shadow_bias must be finite and >= 0")
+
+
+def _shadow_map(pts, v, f32, Ml, Hl, Wl, half_width, layer, near, fused):
+    if fused:
+        q0, layers, qfl = _opacity_fused(pts, v, f32, Ml, Hl, Wl, half_width, layer, near)
+    else:
+        qfl = None
+        if v is not None and f32.shape[0] and Hl * Wl:
+            f64 = f32.long()
+            qfl = _face_depth_torch(v, f64, Ml, Hl, Wl, near, vis._rasterize_torch(v, f64, Ml, Hl, Wl, near))
+        q0, layers = _opacity_torch(pts, Ml, Hl, Wl, half_width, layer, near)
+    return ShadowMap(Ml, Hl, Wl, float(near), q0, layers, qfl, float(np.float32(layer)))
+
+
+@torch.no_grad()
+def strand_shadow_map(points, Ml, Hl, Wl, mesh=None, half_width: float = SHADOW_HALF_WIDTH, layer=None, near: float = NEAR,
+                      fused: bool = True, device=None) -> ShadowMap:
+    """The deep opacity map of ``points`` [S, L, 3] under the light view (Ml, Hl, Wl): the front plane, the four layer counts
+    behind it and, with a ``mesh``, the head's inverse depth (the mesh goes through the mesh raster and the face depth in the light
+    view).  ``layer``: the depth of the first layer in the light's w units (default: the bounding sphere's radius / 32)."""
+    dev = vis._device(device, fused)
+    if fused and dev.type != "cuda":
+        raise RuntimeError("strand_shadow_map(fused=True) needs a ROCm device: the kernels have no CPU path (fused=False is the "
+                           "PyTorch form)")
+    if layer is None:
+        layer = _bounding_sphere(points, mesh)[1] / SHADOW_LAYERS_PER_RADIUS
+    _check_shadow_scalars(half_width, layer, 0.0, 0.0)
+    pts = _points(points, dev)
+    v, f32 = _mesh_tensors(mesh, dev)
+    return _shadow_map(pts, v, f32, Ml, int(Hl), int(Wl), half_width, layer, near, fused)
+
+
 @torch.no_grad()
 def render_strands(points, view, mesh=None, colors=None, mode: str = "kajiya", supersample: int = 2, half_width: float = 0.75,
-                   head_bias: float = 0.0, near: float = NEAR, fused: bool = True, device=None, **shading):
+                   head_bias: float = 0.0, near: float = NEAR, fused: bool = True, device=None, shadows=False,
+                   shadow_size=SHADOW_SIZE, shadow_half_width: float = SHADOW_HALF_WIDTH, shadow_layer=None,
+                   shadow_kappa: float = SHADOW_KAPPA, shadow_bias: float = SHADOW_BIAS, **shading):
     """The picture of ``points`` [S, L, 3] under ``view`` = (M, H, W): uint8 [H, W, 3] on the device.  ``colors``: [S, 3] per-strand
-    base colours, one colour, or None (the default hair colour); ``shading``: the keywords of ``shading_for_view``."""
+    base colours, one colour, or None (the default hair colour); ``shading``: the keywords of ``shading_for_view``.
+    ``shadows``: False (the unshadowed picture), True (a deep opacity map of ``shadow_size`` is made for this call, from the
+    shading's own light: it follows the camera unless ``light=`` is given) or a ``ShadowMap`` (reused: a light fixed in the world
+    along a path).  The light map is not supersampled.  Tangent mode has no shadows."""
     dev = vis._device(device, fused)
     if fused and dev.type != "cuda":
         raise RuntimeError("render_strands(fused=True) needs a ROCm device: the kernels have no CPU path (fused=False is the "
@@ -419,11 +704,27 @@ def render_strands(points, view, mesh=None, colors=None, mode: str = "kajiya", s
             base = torch.from_numpy(c).to(dev).contiguous()
     sh = shading_for_view(M, **shading)
     v, f32 = _mesh_tensors(mesh, dev)
-    seg, _, face, _ = _rasterize(pts, v, f32, Ms, s * H, s * W, rs, head_bias, near, fused)
+    shadow = None
+    if shadows is not False and shadows is not None and mode == "kajiya":
+        if isinstance(shadows, ShadowMap):
+            shadow = shadows
+            _check_shadow_scalars(1.0, shadow.layer, shadow_kappa, shadow_bias)
+            if shadow.q0.device != dev:
+                raise ValueError("render_strands: the ShadowMap is on %s, the picture on %s" % (shadow.q0.device, dev))
+        else:
+            Ml, Hl, Wl, rho = light_view(pts, None if v is None else (v, f32), light=sh["light"], size=shadow_size)
+            layer = rho / SHADOW_LAYERS_PER_RADIUS if shadow_layer is None else shadow_layer
+            _check_shadow_scalars(shadow_half_width, layer, shadow_kappa, shadow_bias)
+            shadow = _shadow_map(pts, v, f32, Ml, Hl, Wl, shadow_half_width, layer, near, fused)
+    seg, t, face, _ = _rasterize(pts, v, f32, Ms, s * H, s * W, rs, head_bias, near, fused)
     if fused:
-        big = _shade_fused(pts, v, f32, s * H, s * W, seg, face, MODES[mode], sh, base)
+        if shadow is not None:
+            big = _shade_shadowed_fused(pts, v, f32, s * H, s * W, seg, face, t, MODES[mode], sh, base, shadow, shadow_kappa, shadow_bias)
+        else:
+            big = _shade_fused(pts, v, f32, s * H, s * W, seg, face, MODES[mode], sh, base)
         return _resolve_fused(big, H, W, s)
-    big = _shade_torch(pts, v, None if f32 is None else f32.long(), s * H, s * W, seg, face, MODES[mode], sh, base)
+    big = _shade_torch(pts, v, None if f32 is None else f32.long(), s * H, s * W, seg, face, MODES[mode], sh, base, t=t, shadow=shadow,
+                       kappa=shadow_kappa, bias=shadow_bias)
     return _resolve_torch(big, H, W, s)
 
 

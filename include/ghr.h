@@ -930,6 +930,35 @@ int ghr_strandview_shade(void* stream, int32_t S, int32_t L, const float* points
                          int32_t mode, const ghr_strandview_shading* shading, const float* base, uint8_t* rgb);
 int ghr_strandview_resolve(void* stream, int32_t H, int32_t W, int32_t supersample, const uint8_t* src, uint8_t* dst);
 
+/* ---- self-shadowing of the strand preview: a deep opacity map of a light view (csrc/ghr_strandview.h)
+ * Added without an ABI_VERSION bump, as the preview itself was: two new functions and one new struct, nothing existing changed.
+ * ghr_strandview_opacity: the light pass.  points [S][L][3] under the light view (Ml [12] on the HOST, Hl, Wl, near_w) with the
+ * half-width half_width (texels) and the layer depth `layer` (the light's w units).  Writes q0 [Hl][Wl] float (the front plane:
+ * the largest inverse depth that covers the texel's centre, 0: none) and layers [Hl][Wl][4] uint32 (the covering segments counted
+ * in four layers behind it).  The workspace is the one ghr_strandview_sizes(S, L, Hl, Wl) sizes; workspace_bytes is checked.
+ * ghr_strandview_shade_shadowed: ghr_strandview_shade with the raster's t plane and the light's map: in kajiya mode the diffuse
+ * and specular terms of a strand pixel and the diffuse term of a head pixel are multiplied by the transmittance at the pixel's
+ * world point; tangent mode and the background are ghr_strandview_shade's.  shadow->qfl (the head's inverse depth in the light
+ * view, from ghr_vis_view and ghr_strandview_face_depth) may be NULL: no mesh.
+ * S == 0 and Hl * Wl == 0 are valid.  Refused: what ghr_strandview_raster and _shade refuse, a layer or half_width that is not
+ * finite and > 0, a kappa or bias that is negative or not finite, a NULL plane, layers not 16-B aligned, a workspace too small. */
+typedef struct ghr_strandview_shadow {
+    float Ml[12];            /* the light view's pixel matrix */
+    float near_w;
+    int32_t Hl, Wl;
+    float layer, kappa, bias;
+    const float* q0;         /* [Hl][Wl] */
+    const uint32_t* layers;  /* [Hl][Wl][4], 16-B aligned */
+    const float* qfl;        /* [Hl][Wl] or NULL */
+} ghr_strandview_shadow;
+int ghr_strandview_opacity(void* stream, int32_t S, int32_t L, const float* points, const float* Ml, float near_w, int32_t Hl,
+                           int32_t Wl, float half_width, float layer, void* workspace, size_t workspace_bytes, float* q0,
+                           uint32_t* layers);
+int ghr_strandview_shade_shadowed(void* stream, int32_t S, int32_t L, const float* points, int32_t V, const float* vertices, int32_t F,
+                                  const int32_t* faces, int32_t H, int32_t W, const int32_t* pix_to_segment,
+                                  const int32_t* pix_to_face_out, const float* t, int32_t mode, const ghr_strandview_shading* shading,
+                                  const float* base, const ghr_strandview_shadow* shadow, uint8_t* rgb);
+
 /* Introspection for tests (device pointers into the workspaces; layout is otherwise private). */
 typedef struct ghr_ws_view {
     const float* rec;          /* [P][16]: x, y, conic a, b, c, opacity, features[10] */

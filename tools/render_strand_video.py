@@ -8,7 +8,10 @@ writes OUT/results/%06d.png (Pillow; no video is encoded).  --strands is what be
 [S, L, 3] array, or the PLY of its points with --strand_length L.  --cameras is the reference's *_matrices.pkl: name -> 4 x 4,
 used as transpose(0, 1)[:3, :4] as the script does; names that are frame numbers are the key frames.  The key cameras are brought
 to the pixels of --size as visibility.views_from_projections does, then strand_view.camera_path interpolates them.
---composed takes the PyTorch-composed comparator instead of the HIP kernels (any device; slow)."""
+--composed takes the PyTorch-composed comparator instead of the HIP kernels (any device; slow).
+--shadows adds self-shadowing (a deep opacity map of the light's view): by default the light follows the camera and
+the map is made per frame; with --world-light X Y Z the light is that world vector (towards the light) for the whole path and ONE
+map is made and reused."""
 import argparse
 import os
 import pickle
@@ -68,6 +71,9 @@ def main(argv=None):
     ap.add_argument("--half_width", type=float, default=0.75)
     ap.add_argument("--head_bias", type=float, default=0.0)
     ap.add_argument("--composed", action="store_true")
+    ap.add_argument("--shadows", action="store_true")
+    ap.add_argument("--world-light", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
+    ap.add_argument("--shadow_size", type=int, default=sv.SHADOW_SIZE)
     ap.add_argument("--device", default=None)
     a = ap.parse_args(argv)
     from PIL import Image
@@ -79,12 +85,20 @@ def main(argv=None):
     pts = torch.from_numpy(points).to(dev)
     out = os.path.join(a.out, "results")
     os.makedirs(out, exist_ok=True)
+    if a.world_light is not None and not a.shadows:
+        raise SystemExit("--world-light needs --shadows")
+    kw, shadows = {}, a.shadows
+    if a.world_light is not None:
+        kw["light"] = np.asarray(a.world_light, np.float64) / np.linalg.norm(a.world_light)
+        Ml, Hl, Wl, _ = sv.light_view(pts, mesh, light=kw["light"], size=a.shadow_size)
+        shadows = sv.strand_shadow_map(pts, Ml, Hl, Wl, mesh=mesh, fused=not a.composed, device=dev)
     for n, P in enumerate(path):
         pic = sv.render_strands(pts, (P.astype(np.float32).reshape(12), H, W), mesh=mesh, mode=a.mode, supersample=a.supersample,
-                                half_width=a.half_width, head_bias=a.head_bias, fused=not a.composed, device=dev)
+                                half_width=a.half_width, head_bias=a.head_bias, fused=not a.composed, device=dev, shadows=shadows,
+                                shadow_size=a.shadow_size, **kw)
         Image.fromarray(pic.cpu().numpy()).save(os.path.join(out, "%06d.png" % n))
-    print("render_strand_video: %d frames of %d x %d (%d strands of %d points%s) in %s"
-          % (len(path), H, W, points.shape[0], points.shape[1], ", composed" if a.composed else "", out))
+    print("render_strand_video: %d frames of %d x %d (%d strands of %d points%s%s) in %s"
+          % (len(path), H, W, points.shape[0], points.shape[1], ", composed" if a.composed else "", ", shadows" if a.shadows else "", out))
     return len(path)
 
 
