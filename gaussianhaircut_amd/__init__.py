@@ -15,6 +15,8 @@ One hot path of eth-ait/GaussianHaircut, rebuilt from scratch behind the referen
   their local frames and the latent texture, in HIP (reference: ``src/scene/gaussian_model_strands.py:456-515``)
 * ``gaussianhaircut_amd.strand_view``                  -- a preview of the groom: strands as depth-tested polylines over the head
   mesh, shaded, along an interpolated camera path, in HIP (reference: ``src/postprocessing/render_video.py``, without Blender)
+* ``gaussianhaircut_amd.comparison``                   -- the comparison video's frames: strand render over white, Pillow-exact resizes,
+  crop and the three-panel strip, in HIP (reference: ``src/postprocessing/concat_video.py``, without ffmpeg)
 * ``gaussianhaircut_amd.parallel``                    -- view-sharded data parallel step (RCCL all-reduce of Gaussian grads)
 
 The compute lives in ``csrc/`` (hand-written HIP, C ABI in ``include/ghr.h``).  No CPU fallback exists.

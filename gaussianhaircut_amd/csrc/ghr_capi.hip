@@ -23,6 +23,7 @@
 #include "ghr_eval.h"
 #include "ghr_orient.h"
 #include "ghr_gt.h"
+#include "ghr_compare.h"
 #include "ghr_preprocess.h"
 #include "ghr_project.h"
 #include "ghr_render_bwd.h"
@@ -1446,6 +1447,56 @@ int ghr_gt_from_render(void* stream, int32_t W, int32_t H, const float* renders,
     const bool vec = (N & 3) == 0 && eval_aligned16({renders, out_image, out_mask, out_angle, out_conf});
     if (vec) hipLaunchKernelGGL(ghr::k_gt_from_render<true>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(ghr::k_gt_from_render<false>, grid, dim3(256), 0, s, a);
+    return finish(s, 0);
+}
+
+// ---- the comparison video's frame assembly (ghr_compare.h) -------------------------------------------------------------------
+namespace {
+bool cmp_overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
+}  // namespace
+
+int ghr_cmp_over_white(void* stream, int64_t n_pixels, const uint8_t* rgba, uint8_t* rgb)
+{
+    if (n_pixels < 1) return fail(GHR_E_INVALID, "ghr_cmp_over_white: n_pixels must be >= 1");
+    if (!rgba || !rgb) return fail(GHR_E_INVALID, "ghr_cmp_over_white: NULL image");
+    const uint64_t groups = (((uint64_t)n_pixels + 3) / 4 + 255) / 256;
+    if (groups > 0x7fffffffu) return fail(GHR_E_INVALID, "ghr_cmp_over_white: image too large for the launch grid");
+    if (cmp_overlap(rgba, 4 * (size_t)n_pixels, rgb, 3 * (size_t)n_pixels))
+        return fail(GHR_E_INVALID, "ghr_cmp_over_white: rgba and rgb must not overlap");
+    hipStream_t s = (hipStream_t)stream;
+    const bool vec = ((uintptr_t)rgba & 15u) == 0 && ((uintptr_t)rgb & 3u) == 0;
+    if (vec) hipLaunchKernelGGL(ghr::k_cmp_over_white<true>, dim3((unsigned)groups), dim3(256), 0, s, n_pixels, rgba, rgb);
+    else hipLaunchKernelGGL(ghr::k_cmp_over_white<false>, dim3((unsigned)groups), dim3(256), 0, s, n_pixels, rgba, rgb);
+    return finish(s, 0);
+}
+
+int ghr_cmp_strip(void* stream, int32_t w, int32_t h, const uint8_t* gt, const uint8_t* preview, int32_t pw, int32_t ph,
+                  int32_t pad_left, int32_t pad_top, int32_t crop_left, int32_t crop_top, const uint8_t* render, uint8_t* out)
+{
+    if (w < 1 || h < 1 || pw < 1 || ph < 1) return fail(GHR_E_INVALID, "ghr_cmp_strip: sizes must be >= 1");
+    if (!gt || !preview || !render || !out) return fail(GHR_E_INVALID, "ghr_cmp_strip: NULL image");
+    if ((int64_t)w * h > ((int64_t)1 << 36) || (int64_t)pw * ph > ((int64_t)1 << 36) || w > (1 << 27))
+        return fail(GHR_E_INVALID, "ghr_cmp_strip: image too large for the launch grid");
+    // CenterCrop pads an axis only when the image is shorter than the window there, and then to the window's length exactly
+    const int32_t padded_w = pw < w ? w : pw, padded_h = ph < h ? h : ph;
+    if (pad_left < 0 || pad_top < 0 || pad_left > padded_w - pw || pad_top > padded_h - ph)
+        return fail(GHR_E_INVALID, "ghr_cmp_strip: the padding does not fit: an axis is padded up to the panel's size and no further");
+    if (crop_left < 0 || crop_top < 0 || crop_left > padded_w - w || crop_top > padded_h - h)
+        return fail(GHR_E_INVALID, "ghr_cmp_strip: the window does not lie inside the padded preview");
+    const size_t panel = (size_t)3 * w * h, strip = 3 * panel;
+    if (cmp_overlap(out, strip, gt, panel) || cmp_overlap(out, strip, render, panel) ||
+        cmp_overlap(out, strip, preview, (size_t)3 * pw * ph))
+        return fail(GHR_E_INVALID, "ghr_cmp_strip: out must not overlap an input");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::CmpStripArgs a{w, h, gt, preview, pw, ph, crop_left - pad_left, crop_top - pad_top, render, out};
+    const dim3 grid((unsigned)(((strip + 3) / 4 + 255) / 256));
+    const bool vec = (w & 3) == 0 && (((uintptr_t)gt | (uintptr_t)render | (uintptr_t)out) & 3u) == 0;
+    if (vec) hipLaunchKernelGGL(ghr::k_cmp_strip<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(ghr::k_cmp_strip<false>, grid, dim3(256), 0, s, a);
     return finish(s, 0);
 }
 

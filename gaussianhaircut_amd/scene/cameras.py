@@ -520,6 +520,61 @@ def ring_cameras(n, width, height, radius=4.0, fovy_deg=40.0, device="cpu", roll
     return cams
 
 
+def interpolate_poses(frames, R, T, fovx, fovy, speed_up: int = 4, max_frames: int = 300, frame_offset: int = 0) -> dict:
+    """The camera path of ``readColmapSceneInfo(interpolate_cameras=True)`` (``src/scene/dataset_readers.py:160-193``) as arrays.
+    ``frames [k]``: the key cameras' frame numbers, strictly increasing, at least two; ``R [k, 3, 3]`` (the transposed rotation, as
+    ``Camera.R`` keeps it), ``T [k, 3]``, ``fovx [k]``, ``fovy [k]``.  Every integer ``i`` of ``[frames[0], frames[-1])`` gets a
+    pose: the rotation from scipy's ``RotationSpline`` over the frame numbers; ``T`` and the two FoVs blended between the
+    neighbouring keys ``j`` and ``j + 1`` as ``alpha * prev + (1 - alpha) * next`` with ``alpha = 1 - (i - frames[j]) / (frames[j
+    + 1] - frames[j])``.  Of that list every ``speed_up``-th entry is kept and then ``[frame_offset : frame_offset + max_frames]``.
+    Returns float64 arrays ``frame [n]``, ``R [n, 3, 3]``, ``T [n, 3]``, ``fovx [n]``, ``fovy [n]`` and ``key [n]`` (the ``j``)."""
+    from scipy.spatial.transform import Rotation, RotationSpline
+    f = np.asarray(frames)
+    if f.ndim != 1 or f.shape[0] < 2:
+        raise ValueError("interpolate_poses: at least two key cameras are needed, got %s" % (f.shape,))
+    if not np.all(f == np.round(f)):
+        raise ValueError("interpolate_poses: frame numbers must be integers")
+    f = f.astype(np.int64)
+    if not np.all(np.diff(f) > 0):
+        raise ValueError("interpolate_poses: frame numbers must be strictly increasing, got %s" % (f.tolist(),))
+    k = f.shape[0]
+    R = np.asarray(R, np.float64).reshape(k, 3, 3)
+    T = np.asarray(T, np.float64).reshape(k, 3)
+    fovx, fovy = np.asarray(fovx, np.float64).reshape(k), np.asarray(fovy, np.float64).reshape(k)
+    if int(speed_up) < 1 or int(max_frames) < 0 or int(frame_offset) < 0:
+        raise ValueError("interpolate_poses: speed_up >= 1, max_frames >= 0 and frame_offset >= 0 are needed")
+    i = np.arange(f[0], f[-1], dtype=np.int64)
+    R_i = RotationSpline(f.astype(np.float64), Rotation.from_matrix(R))(i.astype(np.float64)).as_matrix()
+    j = np.searchsorted(f, i, side="right") - 1          # the last key at or before frame i
+    alpha = 1 - (i - f[j]) / (f[j + 1] - f[j])
+    blend = lambda v: (v[j].T * alpha + v[j + 1].T * (1 - alpha)).T   # noqa: E731
+    take = slice(None, None, int(speed_up))
+    cut = slice(int(frame_offset), int(frame_offset) + int(max_frames))
+    pick = lambda v: np.ascontiguousarray(v[take][cut], np.float64)   # noqa: E731
+    return dict(frame=pick(i), R=pick(R_i), T=pick(blend(T)), fovx=pick(blend(fovx)), fovy=pick(blend(fovy)), key=pick(j))
+
+
+def interpolated_cameras(keys, speed_up: int = 4, max_frames: int = 300, frame_offset: int = 0, device="cpu", znear=0.01,
+                         zfar=100.0) -> list:
+    """``Camera``s along the path ``interpolate_poses`` makes of the key cameras ``keys``: objects with ``R``, ``T`` (numpy, as
+    ``Camera`` keeps them), ``FoVx``, ``FoVy`` (a float or a 0-d tensor), ``image_width``, ``image_height`` and ``image_name``, a
+    string with ``int(image_name)`` the frame number.  The keys are sorted by ``image_name`` as strings, as the reference sorts
+    them; a path camera has the size of the key before it and ``image_name = '%06d' % frame``.  What the reference's ``CameraInfo``
+    carries besides -- the blended ``uid``, ``image`` and ``image_path`` -- has no counterpart in ``Camera`` and is not reproduced."""
+    keys = sorted(keys, key=lambda c: c.image_name)
+    if len(keys) < 2:
+        raise ValueError("interpolated_cameras: at least two key cameras are needed, got %d" % len(keys))
+    p = interpolate_poses([int(c.image_name) for c in keys], np.stack([np.asarray(c.R, np.float64) for c in keys]),
+                          np.stack([np.asarray(c.T, np.float64).reshape(3) for c in keys]), [float(c.FoVx) for c in keys],
+                          [float(c.FoVy) for c in keys], speed_up, max_frames, frame_offset)
+    cams = []
+    for n in range(p["frame"].shape[0]):
+        key = keys[int(p["key"][n])]
+        cams.append(Camera(p["R"][n], p["T"][n], p["fovx"][n], p["fovy"][n], key.image_width, key.image_height, znear=znear,
+                           zfar=zfar, device=device, image_name="%06d" % int(p["frame"][n])))
+    return cams
+
+
 PARITY_CAMERAS = ("front", "ring5", "ring13roll")
 
 

@@ -959,6 +959,26 @@ int ghr_strandview_shade_shadowed(void* stream, int32_t S, int32_t L, const floa
                                   const int32_t* pix_to_face_out, const float* t, int32_t mode, const ghr_strandview_shading* shading,
                                   const float* base, const ghr_strandview_shadow* shadow, uint8_t* rgb);
 
+/* ---- the comparison video's frame assembly (src/postprocessing/concat_video.py:26-40; csrc/ghr_compare.h)
+ * Added without an ABI_VERSION bump: two new functions, no existing struct or signature changed.
+ * ghr_cmp_over_white: rgba [n_pixels][4] -> rgb [n_pixels][3], Pillow's paste of the image over opaque white through its own
+ * alpha: per colour byte c of a pixel with alpha a, t = c a + 255 (255 - a) + 128 and out = ((t >> 8) + t) >> 8; alpha is dropped.
+ * Four pixels per thread with one 16-B load and three dword stores when rgba is 16-B and rgb 4-B aligned, single bytes otherwise:
+ * the same bytes either way.
+ * ghr_cmp_strip: out [h][3 w][3] = gt | window | render in one launch.  gt and render are [h][w][3]; preview [ph][pw][3] is the
+ * strand render already resized.  Pixel (y, x) of the window is preview pixel (y + crop_top - pad_top, x + crop_left - pad_left),
+ * or zero where that lies outside [0, ph) x [0, pw): torchvision's CenterCrop, which pads an axis with black up to the window's
+ * length when the image is shorter there (pad_left / pad_top of it before the image) and then cuts at crop_left / crop_top.  The
+ * padded image is max(pw, w) x max(ph, h): a padding that reaches past it or a window that does not lie inside it is refused.
+ * Dword accesses for the outer panels when w % 4 == 0 and gt, render and out are 4-B aligned, single bytes otherwise: the same
+ * bytes either way.
+ * Both refuse, with GHR_E_INVALID and a ghr_last_error() text: a NULL pointer, a size < 1, an output that overlaps an input, an
+ * image too large for the launch grid.  A refused call launches nothing.  Integer arithmetic alone: the same input gives the same
+ * bytes on every run. */
+int ghr_cmp_over_white(void* stream, int64_t n_pixels, const uint8_t* rgba, uint8_t* rgb);
+int ghr_cmp_strip(void* stream, int32_t w, int32_t h, const uint8_t* gt, const uint8_t* preview, int32_t pw, int32_t ph,
+                  int32_t pad_left, int32_t pad_top, int32_t crop_left, int32_t crop_top, const uint8_t* render, uint8_t* out);
+
 /* Introspection for tests (device pointers into the workspaces; layout is otherwise private). */
 typedef struct ghr_ws_view {
     const float* rec;          /* [P][16]: x, y, conic a, b, c, opacity, features[10] */
