@@ -2170,7 +2170,45 @@ int ghr_gaussian_probe_outside(void* stream, const ghr_mesh_grid* header, const 
 
 // ---- head-mesh visibility (include/ghr.h; csrc/ghr_visibility.h) --------------------------------------------------------------
 namespace {
-inline unsigned vis_blocks(int64_t n) { return (unsigned)((n + GHR_VIS_BLOCK - 1) / GHR_VIS_BLOCK); }
+// -- the tile lists (csrc/ghr_tilelists.h) that this raster and the two of the strand preview below are built on
+inline unsigned tl_blocks(uint64_t n) { return (unsigned)((n + GHR_TL_BLOCK - 1) / GHR_TL_BLOCK); }
+
+// the lists' share of a raster's arguments, from the layout and the workspace
+ghr::TileLists tl_bind(const ghr::TileListLayout& L, char* ws, uint32_t n_points, uint32_t n_prims, const float* points, const float* M,
+                       float near_w)
+{
+    ghr::TileLists tl{};
+    tl.n_points = n_points; tl.n_prims = n_prims; tl.tiles_x = L.tiles_x; tl.tiles_y = L.tiles_y;
+    tl.near = near_w;
+    for (int k = 0; k < 12; k++) tl.M[k] = M[k];
+    tl.points = points;
+    tl.proj = reinterpret_cast<float*>(ws + L.off_proj);
+    tl.rec = reinterpret_cast<float*>(ws + L.off_rec);
+    tl.start = reinterpret_cast<uint32_t*>(ws + L.off_start);
+    tl.count = reinterpret_cast<uint32_t*>(ws + L.off_count);
+    tl.nbig = reinterpret_cast<uint32_t*>(ws + L.off_nbig);
+    tl.list = reinterpret_cast<uint32_t*>(ws + L.off_list);
+    tl.big = reinterpret_cast<uint32_t*>(ws + L.off_big);
+    tl.list_cap = (uint32_t)L.list_cap;
+    return tl;
+}
+
+// One view's lists.  The tile counts and the big list's length (and what their owner put behind them: `fill_bytes`) start every
+// view at 0: one fill, so that a workspace needs no preparation by its owner and may change image size between views.  Then the
+// projection, the owner's setup kernel (launch_setup), the scan and the scatter; an image without pixels has no lists to build.
+template <int UNITS, class Setup>
+int tl_build(hipStream_t s, const ghr::TileLists& tl, void* fill, size_t fill_bytes, Setup launch_setup)
+{
+    GHR_HIP(hipMemsetAsync(fill, 0, fill_bytes, s));
+    if (tl.tiles_x == 0 || tl.tiles_y == 0) return GHR_OK;
+    if (tl.n_prims) {
+        if (tl.n_points) hipLaunchKernelGGL(ghr::k_tl_project, dim3(tl_blocks(tl.n_points)), dim3(GHR_TL_BLOCK), 0, s, tl);
+        launch_setup();
+    }
+    hipLaunchKernelGGL(ghr::k_tl_scan, dim3(1), dim3(GHR_TL_BLOCK), 0, s, tl);
+    if (tl.n_prims) hipLaunchKernelGGL((ghr::k_tl_scatter<UNITS>), dim3(tl_blocks(tl.n_prims)), dim3(GHR_TL_BLOCK), 0, s, tl);
+    return GHR_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -2219,31 +2257,18 @@ int ghr_vis_view(void* stream, int32_t V, const float* vertices, int32_t F, cons
     hipStream_t s = (hipStream_t)stream;
     char* ws = static_cast<char*>(workspace);
     ghr::VisArgs a{};
-    a.V = V; a.F = F; a.H = H; a.W = W; a.tiles_x = L.tiles_x; a.tiles_y = L.tiles_y;
-    a.near = near_w;
-    for (int k = 0; k < 12; k++) a.M[k] = M[k];
-    a.vertices = vertices; a.faces = faces;
-    a.proj = reinterpret_cast<float*>(ws + L.off_proj);
-    a.rec = reinterpret_cast<float*>(ws + L.off_rec);
-    a.start = reinterpret_cast<uint32_t*>(ws + L.off_start);
-    a.count = reinterpret_cast<uint32_t*>(ws + L.off_count);
-    a.nbig = reinterpret_cast<uint32_t*>(ws + L.off_nbig);
-    a.list = reinterpret_cast<uint32_t*>(ws + L.off_list);
-    a.big = reinterpret_cast<uint32_t*>(ws + L.off_big);
-    a.list_cap = (uint32_t)L.list_cap;
+    a.tl = tl_bind(L, ws, (uint32_t)V, (uint32_t)F, vertices, M, near_w);
+    a.V = V; a.F = F; a.H = H; a.W = W;
+    a.faces = faces;
     a.seen = reinterpret_cast<uint8_t*>(ws + L.off_seen);
     a.seen_head = reinterpret_cast<uint8_t*>(ws + L.off_seen_head);
     a.pix_to_face = pix_to_face; a.vis = vis; a.cnt = cnt; a.cnt_head = cnt_head;
-    // the tile counts, the big list's length and the vertex flags start every view at 0: one fill, so that a workspace needs no
-    // preparation by its owner and may change image size between views
-    GHR_HIP(hipMemsetAsync(ws + L.off_fill, 0, (size_t)L.fill_bytes, s));
+    // (the fill covers the vertex flags too)
+    if (int rc = tl_build<GHR_VIS_REC_UNITS>(s, a.tl, ws + L.off_fill, (size_t)L.fill_bytes, [&] {
+            hipLaunchKernelGGL(ghr::k_vis_setup, dim3(tl_blocks(F)), dim3(GHR_VIS_BLOCK), 0, s, a);
+        }))
+        return rc;
     if (pixels) {
-        if (F) {
-            if (V) hipLaunchKernelGGL(ghr::k_vis_project, dim3(vis_blocks(V)), dim3(GHR_VIS_BLOCK), 0, s, a);
-            hipLaunchKernelGGL(ghr::k_vis_setup, dim3(vis_blocks(F)), dim3(GHR_VIS_BLOCK), 0, s, a);
-        }
-        hipLaunchKernelGGL(ghr::k_vis_scan, dim3(1), dim3(GHR_VIS_BLOCK), 0, s, a);
-        if (F) hipLaunchKernelGGL(ghr::k_vis_scatter, dim3(vis_blocks(F)), dim3(GHR_VIS_BLOCK), 0, s, a);
         if (body) {
             uint8_t* head = reinterpret_cast<uint8_t*>(ws + L.off_head);
             hipLaunchKernelGGL(ghr::k_vis_head_mask, dim3((unsigned)L.tiles_x, (unsigned)L.tiles_y), dim3(GHR_VIS_BLOCK), 0, s,
@@ -2251,7 +2276,7 @@ int ghr_vis_view(void* stream, int32_t V, const float* vertices, int32_t F, cons
             a.head = head;
         }
         hipLaunchKernelGGL(ghr::k_vis_raster, dim3((unsigned)L.tiles_x, (unsigned)L.tiles_y), dim3(GHR_VIS_BLOCK), 0, s, a);
-        if (V && F && cnt) hipLaunchKernelGGL(ghr::k_vis_accumulate, dim3(vis_blocks(V)), dim3(GHR_VIS_BLOCK), 0, s, a);
+        if (V && F && cnt) hipLaunchKernelGGL(ghr::k_vis_accumulate, dim3(tl_blocks(V)), dim3(GHR_VIS_BLOCK), 0, s, a);
     }
     return finish(s, 0);
 }
@@ -2324,30 +2349,16 @@ int ghr_strandview_raster(void* stream, int32_t S, int32_t L, const float* point
     hipStream_t s = (hipStream_t)stream;
     char* ws = static_cast<char*>(workspace);
     ghr::SvArgs a{};
-    a.S = S; a.L = L; a.H = H; a.W = W; a.tiles_x = Y.tiles_x; a.tiles_y = Y.tiles_y;
-    a.n_points = (uint32_t)Y.n_points; a.n_segments = (uint32_t)Y.n_segments;
-    a.near = near_w; a.r = half_width; a.head_bias = head_bias;
-    for (int k = 0; k < 12; k++) a.M[k] = M[k];
-    a.points = points; a.pix_to_face = pix_to_face; a.qf = qf;
-    a.proj = reinterpret_cast<float*>(ws + Y.off_proj);
-    a.rec = reinterpret_cast<float*>(ws + Y.off_rec);
-    a.start = reinterpret_cast<uint32_t*>(ws + Y.off_start);
-    a.count = reinterpret_cast<uint32_t*>(ws + Y.off_count);
-    a.nbig = reinterpret_cast<uint32_t*>(ws + Y.off_nbig);
-    a.list = reinterpret_cast<uint32_t*>(ws + Y.off_list);
-    a.big = reinterpret_cast<uint32_t*>(ws + Y.off_big);
-    a.list_cap = (uint32_t)Y.list_cap;
+    a.tl = tl_bind(Y, ws, (uint32_t)Y.n_points, (uint32_t)Y.n_segments, points, M, near_w);
+    a.L = L; a.H = H; a.W = W;
+    a.r = half_width; a.head_bias = head_bias;
+    a.pix_to_face = pix_to_face; a.qf = qf;
     a.pix_to_segment = pix_to_segment; a.t = t; a.pix_to_face_out = pix_to_face_out; a.inv_depth = inv_depth;
     if (!pixels) return GHR_OK;
-    // the tile counts and the big list's length start every frame at 0: one fill, so that a workspace needs no preparation by
-    // its owner and may change image size between frames
-    GHR_HIP(hipMemsetAsync(ws + Y.off_fill, 0, (size_t)Y.fill_bytes, s));
-    if (a.n_segments) {
-        hipLaunchKernelGGL(ghr::k_sv_project, dim3(sv_blocks(Y.n_points)), dim3(GHR_SV_BLOCK), 0, s, a);
-        hipLaunchKernelGGL(ghr::k_sv_setup, dim3(sv_blocks(Y.n_segments)), dim3(GHR_SV_BLOCK), 0, s, a);
-    }
-    hipLaunchKernelGGL(ghr::k_sv_scan, dim3(1), dim3(GHR_SV_BLOCK), 0, s, a);
-    if (a.n_segments) hipLaunchKernelGGL(ghr::k_sv_scatter, dim3(sv_blocks(Y.n_segments)), dim3(GHR_SV_BLOCK), 0, s, a);
+    if (int rc = tl_build<GHR_SV_REC_UNITS>(s, a.tl, ws + Y.off_fill, (size_t)Y.fill_bytes, [&] {
+            hipLaunchKernelGGL(ghr::k_sv_setup, dim3(tl_blocks(Y.n_segments)), dim3(GHR_SV_BLOCK), 0, s, a);
+        }))
+        return rc;
     hipLaunchKernelGGL(ghr::k_sv_raster, dim3((unsigned)Y.tiles_x, (unsigned)Y.tiles_y), dim3(GHR_SV_BLOCK), 0, s, a);
     return finish(s, 0);
 }
@@ -2425,27 +2436,14 @@ int ghr_strandview_opacity(void* stream, int32_t S, int32_t L, const float* poin
     char* ws = static_cast<char*>(workspace);
     ghr::SvLayersArgs la{};
     ghr::SvArgs& a = la.a;
-    a.S = S; a.L = L; a.H = Hl; a.W = Wl; a.tiles_x = Y.tiles_x; a.tiles_y = Y.tiles_y;
-    a.n_points = (uint32_t)Y.n_points; a.n_segments = (uint32_t)Y.n_segments;
-    a.near = near_w; a.r = half_width;
-    for (int k = 0; k < 12; k++) a.M[k] = Ml[k];
-    a.points = points;
-    a.proj = reinterpret_cast<float*>(ws + Y.off_proj);
-    a.rec = reinterpret_cast<float*>(ws + Y.off_rec);
-    a.start = reinterpret_cast<uint32_t*>(ws + Y.off_start);
-    a.count = reinterpret_cast<uint32_t*>(ws + Y.off_count);
-    a.nbig = reinterpret_cast<uint32_t*>(ws + Y.off_nbig);
-    a.list = reinterpret_cast<uint32_t*>(ws + Y.off_list);
-    a.big = reinterpret_cast<uint32_t*>(ws + Y.off_big);
-    a.list_cap = (uint32_t)Y.list_cap;
+    a.tl = tl_bind(Y, ws, (uint32_t)Y.n_points, (uint32_t)Y.n_segments, points, Ml, near_w);
+    a.L = L; a.H = Hl; a.W = Wl;
+    a.r = half_width;
     la.layer = layer; la.q0 = q0; la.layers = layers;
-    GHR_HIP(hipMemsetAsync(ws + Y.off_fill, 0, (size_t)Y.fill_bytes, s));
-    if (a.n_segments) {
-        hipLaunchKernelGGL(ghr::k_sv_project, dim3(sv_blocks(Y.n_points)), dim3(GHR_SV_BLOCK), 0, s, a);
-        hipLaunchKernelGGL(ghr::k_sv_setup, dim3(sv_blocks(Y.n_segments)), dim3(GHR_SV_BLOCK), 0, s, a);
-    }
-    hipLaunchKernelGGL(ghr::k_sv_scan, dim3(1), dim3(GHR_SV_BLOCK), 0, s, a);
-    if (a.n_segments) hipLaunchKernelGGL(ghr::k_sv_scatter, dim3(sv_blocks(Y.n_segments)), dim3(GHR_SV_BLOCK), 0, s, a);
+    if (int rc = tl_build<GHR_SV_REC_UNITS>(s, a.tl, ws + Y.off_fill, (size_t)Y.fill_bytes, [&] {
+            hipLaunchKernelGGL(ghr::k_sv_setup, dim3(tl_blocks(Y.n_segments)), dim3(GHR_SV_BLOCK), 0, s, a);
+        }))
+        return rc;
     hipLaunchKernelGGL(ghr::k_sv_layers, dim3((unsigned)Y.tiles_x, (unsigned)Y.tiles_y), dim3(GHR_SV_BLOCK), 0, s, la);
     return finish(s, 0);
 }

@@ -76,26 +76,21 @@
 //       Look constants (defaults of the keywords, CHOSEN here like ambient and kd, not measured): light map 1024 x 1024, rl 1.0 texel,
 //           kappa 0.2, shadow_bias 0.02, d = rho / 32 with rho the radius of the bounding sphere the light camera is fitted to.
 //
-// Per frame (ghr_strandview_raster): one fill of the tile counters, then
-//   k_sv_project   one thread per point: {sx, sy, q, valid}, 16 B
-//   k_sv_setup     one thread per segment: a 32-B record  ax ay bx by | qa qb xy bits  and its rectangle of 16 x 16 tiles.
-//                  The rectangle is vis_pixel_range of the box widened by r -- the same four floats the coverage rule compares
-//                  the centre with -- so it can never be too small: a centre inside the closed box satisfies j + 0.5 >= lo, and
-//                  vis_pixel_range's floor of the rounded lo - 0.5 is never above such a j (monotone rounding, j exact), likewise
-//                  at the upper end.  xy = first tile x | y << 16; bits = flags | (tiles across - 1) << 8 | (tiles down - 1) << 16.
-//                  A segment of more than GHR_SV_BIG_RECT tiles goes to the frame's one BIG list, which every tile walks after its
-//                  own: the lists hold at most GHR_SV_BIG_RECT entries per segment, so the workspace is sized from S, L, H, W
-//                  alone, with no read-back.
-//   k_sv_scan      one workgroup: exclusive scan of the tile counts; the counts become the fill cursors
-//   k_sv_scatter   one thread per segment: its id into the lists of its tiles (integer atomics; the order inside a list is free)
-//   k_sv_raster    one 256-thread workgroup per tile, one pixel per thread; records staged in LDS GHR_SV_CHUNK at a time; a wave
-//                  none of whose lanes is in a record's widened box skips it by ballot; pix_to_face / qf are read once.
+// Per frame (ghr_strandview_raster): the fill, projection, scan and scatter of ghr_tilelists.h (which also owns the tile rectangle
+// and the staged walk of a tile's list), and this header's own kernels:
+//   k_sv_setup     one thread per segment: a 32-B record  ax ay bx by | qa qb xy bits  from its two projected points, then tl_count.
+//                  The rectangle is tl_pixel_range of the box widened by r -- the same four floats the coverage rule compares the
+//                  centre with -- so it can never be too small: a centre inside the closed box satisfies j + 0.5 >= lo, and
+//                  tl_pixel_range's floor of the rounded lo - 0.5 is never above such a j (monotone rounding, j exact), likewise
+//                  at the upper end.  A segment of more than GHR_SV_BIG_RECT tiles goes to the big list.
+//   k_sv_raster    the tile's walk with GHR_SV_CHUNK records per round (tl_walk's loop written out here: it measured faster so) and
+//                  the winner's total order; pix_to_face / qf are read once.
 // and, on their own entries: k_sv_face_depth (one thread per pixel: qf), k_sv_shade (one thread per pixel: it gathers the winner's
 // two world points or the face's three vertices), k_sv_resolve (one thread per output pixel).  Integer atomics only.
-// The light pass (ghr_strandview_opacity) is the same fill, k_sv_project, k_sv_setup, k_sv_scan and k_sv_scatter in the light view, then
-//   k_sv_layers    k_sv_raster's shape, but the lists are walked TWICE in one launch: walk 1 keeps the largest qs in a register,
-//                  walk 2 re-tests coverage and classifies every covering segment against that register into four counters in
-//                  registers; the epilogue writes q0 (4 B) and the four counts as one 16-B store.  No atomics, no pix_to_face.
+// The light pass (ghr_strandview_opacity) is the same lists in the light view, then
+//   k_sv_layers    k_sv_raster's shape, but TWO tl_walks in one launch: walk 1 keeps the largest qs in a register, walk 2 re-tests
+//                  coverage and classifies every covering segment against that register into four counters in registers; the
+//                  epilogue writes q0 (4 B) and the four counts as one 16-B store.  No atomics, no pix_to_face, no segment ids.
 // and k_sv_shade_shadowed (one thread per camera pixel, behind ghr_strandview_shade_shadowed) is k_sv_shade with the lookup.
 // Everything per element is GHR_HD so that tests/hostsim/ghr_hostsim_strandview.cpp runs the product's own arithmetic on the CPU.
 #pragma once
@@ -104,14 +99,15 @@
 #include "ghr_products.h"
 #endif
 
-#define GHR_SV_TILE 16
-#define GHR_SV_BLOCK 256
+#define GHR_SV_TILE GHR_TL_TILE
+#define GHR_SV_BLOCK GHR_TL_BLOCK
 #define GHR_SV_CHUNK 128     // records staged in LDS per round of k_sv_raster (two 16-B units each: one per thread)
 #define GHR_SV_REC_WORDS 8   // two 16-B units per segment
+#define GHR_SV_REC_UNITS (GHR_SV_REC_WORDS / 4)
 #define GHR_SV_BIG_RECT 16   // a segment of more tiles than this goes to the big list
-#define GHR_SV_NEVER 1u
-#define GHR_SV_EMPTY 2u
-#define GHR_SV_BIG 4u
+#define GHR_SV_NEVER GHR_TL_NEVER  // the list builder's flags in a record's last word, under the names a walk of segments reads them by
+#define GHR_SV_EMPTY GHR_TL_EMPTY
+#define GHR_SV_BIG GHR_TL_BIG
 #define GHR_SV_KAJIYA 0
 #define GHR_SV_TANGENT 1
 #define GHR_SV_MAX_SHININESS_LOG2 16
@@ -131,21 +127,9 @@ GHR_HD void sv_setup_one(const float* pa, const float* pb, float r, int H, int W
 {
     const bool never = pa[3] == 0.f || pb[3] == 0.f;
     rec[0] = pa[0]; rec[1] = pa[1]; rec[2] = pb[0]; rec[3] = pb[1]; rec[4] = pa[2]; rec[5] = pb[2];
-    uint32_t bits = never ? GHR_SV_NEVER : 0u, xy = 0u;
-    int j0 = 0, j1 = -1, i0 = 0, i1 = -1;
     const float ulo = fminf(pa[0], pb[0]) - r, uhi = fmaxf(pa[0], pb[0]) + r;
     const float vlo = fminf(pa[1], pb[1]) - r, vhi = fmaxf(pa[1], pb[1]) + r;
-    if (!never && vis_pixel_range(ulo, uhi, W, &j0, &j1) && vis_pixel_range(vlo, vhi, H, &i0, &i1)) {
-        const uint32_t x0 = (uint32_t)j0 / GHR_SV_TILE, x1 = (uint32_t)j1 / GHR_SV_TILE;
-        const uint32_t y0 = (uint32_t)i0 / GHR_SV_TILE, y1 = (uint32_t)i1 / GHR_SV_TILE;
-        xy = x0 | (y0 << 16);
-        if ((uint64_t)(x1 - x0 + 1u) * (y1 - y0 + 1u) > GHR_SV_BIG_RECT) bits |= GHR_SV_BIG;
-        else bits |= ((x1 - x0) << 8) | ((y1 - y0) << 16);  // (each below GHR_SV_BIG_RECT)
-    } else {
-        bits |= GHR_SV_EMPTY;
-    }
-    memcpy(rec + 6, &xy, 4);
-    memcpy(rec + 7, &bits, 4);
+    tl_rect(never ? GHR_SV_NEVER : 0u, ulo, uhi, vlo, vhi, H, W, GHR_SV_BIG_RECT, rec + 6);
 }
 
 GHR_HD bool sv_in_box(const float* rec, float r, float px, float py)
@@ -187,16 +171,12 @@ GHR_HD float sv_face_depth_one(const float* M, float near, const float* vertices
     if (f < 0 || f >= F) return 0.f;
     const int32_t t[3] = {faces[3 * (size_t)f], faces[3 * (size_t)f + 1], faces[3 * (size_t)f + 2]};
     if (t[0] < 0 || t[0] >= V || t[1] < 0 || t[1] >= V || t[2] < 0 || t[2] >= V) return 0.f;
-    if (t[0] == t[1] || t[1] == t[2] || t[0] == t[2]) return 0.f;
     float p[3][4];
     for (int k = 0; k < 3; k++) vis_project_one(M, vertices + 3 * (size_t)t[k], near, p[k]);
-    if (p[0][3] == 0.f || p[1][3] == 0.f || p[2][3] == 0.f) return 0.f;
-    if (mesh_flat(p[0][0], p[0][1], p[1][0], p[1][1], p[2][0], p[2][1])) return 0.f;
-    float r[GHR_VIS_REC_WORDS] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < 3; k++) { r[2 * k] = p[k][0]; r[2 * k + 1] = p[k][1]; r[6 + k] = p[k][2]; }
-    const uint32_t bits = (t[0] > t[1] ? 1u : 0u) | (t[1] > t[2] ? 2u : 0u) | (t[2] > t[0] ? 4u : 0u);
-    memcpy(r + 9, &bits, 4);
-    float d;
+    float r[GHR_VIS_REC_WORDS], d;
+    const uint32_t bits = vis_face_record(p[0], p[1], p[2], t, r);  // (a NEVER face fails vis_covers)
+    r[10] = 0.f;
+    memcpy(r + 11, &bits, 4);
     if (!vis_covers(r, px, py, &d)) return 0.f;
     return d > 0.f ? d : 0.f;  // (a NaN fails the comparison)
 }
@@ -233,7 +213,8 @@ GHR_HD uint32_t sv_quant8(float v)
 #endif
 }
 
-GHR_HD void sv_shade_strand(const float* A, const float* B, const float* base, int mode, const SvShading& sh, uint8_t* rgb)
+// Tr: the transmittance on the two light terms; 1.f (1.f x == x) where there is no shadow map.  Tangent mode has no light.
+GHR_HD void sv_shade_strand(const float* A, const float* B, const float* base, int mode, const SvShading& sh, float Tr, uint8_t* rgb)
 {
     const float d[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
     float T[3];
@@ -249,17 +230,17 @@ GHR_HD void sv_shade_strand(const float* A, const float* B, const float* base, i
     const float sl = sqrtf(fmaxf(0.f, 1.f - cl * cl)), sv = sqrtf(fmaxf(0.f, 1.f - cv * cv));
     float spec = fmaxf(0.f, cl * cv + sl * sv);
     for (int k = 0; k < sh.shininess_log2; k++) spec = spec * spec;
-    for (int c = 0; c < 3; c++) rgb[c] = (uint8_t)sv_quant8(base[c] * (sh.ambient + sh.kd * sl) + sh.ks * spec);
+    for (int c = 0; c < 3; c++) rgb[c] = (uint8_t)sv_quant8(base[c] * (sh.ambient + sh.kd * (Tr * sl)) + sh.ks * (Tr * spec));
 }
 
-GHR_HD void sv_shade_head(const float* v0, const float* v1, const float* v2, const SvShading& sh, uint8_t* rgb)
+GHR_HD void sv_shade_head(const float* v0, const float* v1, const float* v2, const SvShading& sh, float Tr, uint8_t* rgb)
 {
     const float e1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]}, e2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
     const float n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
     float nn[3];
     sv_normalise(n, nn);
     const float c = sv_dot(nn, sh.light);
-    const float lit = sh.ambient + sh.kd * fmaxf(c, -c);
+    const float lit = sh.ambient + sh.kd * (Tr * fmaxf(c, -c));
     for (int k = 0; k < 3; k++) rgb[k] = (uint8_t)sv_quant8(sh.head_rgb[k] * lit);
 }
 
@@ -270,13 +251,13 @@ GHR_HD void sv_shade_one(int32_t seg, int32_t face, int S, int L, const float* p
     if (seg >= 0 && L >= 2 && (int64_t)seg < (int64_t)S * (L - 1)) {
         const int s = seg / (L - 1), i = seg % (L - 1);
         const float* A = points + 3 * ((size_t)s * L + i);
-        sv_shade_strand(A, A + 3, base ? base + 3 * (size_t)s : sh.base_rgb, mode, sh, rgb);
+        sv_shade_strand(A, A + 3, base ? base + 3 * (size_t)s : sh.base_rgb, mode, sh, 1.f, rgb);
         return;
     }
     if (face >= 0 && face < F) {
         const int32_t* t = faces + 3 * (size_t)face;
         if (t[0] >= 0 && t[0] < V && t[1] >= 0 && t[1] < V && t[2] >= 0 && t[2] < V) {
-            sv_shade_head(vertices + 3 * (size_t)t[0], vertices + 3 * (size_t)t[1], vertices + 3 * (size_t)t[2], sh, rgb);
+            sv_shade_head(vertices + 3 * (size_t)t[0], vertices + 3 * (size_t)t[1], vertices + 3 * (size_t)t[2], sh, 1.f, rgb);
             return;
         }
     }
@@ -339,33 +320,6 @@ GHR_HD float sv_shadow_at(const SvShadow& sd, const float* P, float* n_out)
     return sv_transmittance(n, sd.kappa, behind);
 }
 
-// sv_shade_strand's kajiya branch with the transmittance on the two light terms
-GHR_HD void sv_shade_strand_shadowed(const float* A, const float* B, const float* base, const SvShading& sh, float Tr, uint8_t* rgb)
-{
-    const float d[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
-    float T[3];
-    sv_normalise(d, T);
-    const float v[3] = {sh.eye[0] - 0.5f * (A[0] + B[0]), sh.eye[1] - 0.5f * (A[1] + B[1]), sh.eye[2] - 0.5f * (A[2] + B[2])};
-    float Vn[3];
-    sv_normalise(v, Vn);
-    const float cl = sv_dot(T, sh.light), cv = sv_dot(T, Vn);
-    const float sl = sqrtf(fmaxf(0.f, 1.f - cl * cl)), sv = sqrtf(fmaxf(0.f, 1.f - cv * cv));
-    float spec = fmaxf(0.f, cl * cv + sl * sv);
-    for (int k = 0; k < sh.shininess_log2; k++) spec = spec * spec;
-    for (int c = 0; c < 3; c++) rgb[c] = (uint8_t)sv_quant8(base[c] * (sh.ambient + sh.kd * (Tr * sl)) + sh.ks * (Tr * spec));
-}
-
-GHR_HD void sv_shade_head_shadowed(const float* v0, const float* v1, const float* v2, const SvShading& sh, float Tr, uint8_t* rgb)
-{
-    const float e1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]}, e2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
-    const float n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-    float nn[3];
-    sv_normalise(n, nn);
-    const float c = sv_dot(nn, sh.light);
-    const float lit = sh.ambient + sh.kd * (Tr * fmaxf(c, -c));
-    for (int k = 0; k < 3; k++) rgb[k] = (uint8_t)sv_quant8(sh.head_rgb[k] * lit);
-}
-
 // One pixel of the shadowed picture: sv_shade_one with the lookup at the strand point A + t (B - A) or at the face's centroid.
 GHR_HD void sv_shade_one_shadowed(int32_t seg, int32_t face, float t, int S, int L, const float* points, int V, const float* vertices,
                                   int F, const int32_t* faces, const float* base, int mode, const SvShading& sh, const SvShadow& sd,
@@ -376,7 +330,7 @@ GHR_HD void sv_shade_one_shadowed(int32_t seg, int32_t face, float t, int S, int
         const float* A = points + 3 * ((size_t)s * L + i);
         const float* B = A + 3;
         const float P[3] = {A[0] + t * (B[0] - A[0]), A[1] + t * (B[1] - A[1]), A[2] + t * (B[2] - A[2])};
-        sv_shade_strand_shadowed(A, B, base ? base + 3 * (size_t)s : sh.base_rgb, sh, sv_shadow_at(sd, P, nullptr), rgb);
+        sv_shade_strand(A, B, base ? base + 3 * (size_t)s : sh.base_rgb, mode, sh, sv_shadow_at(sd, P, nullptr), rgb);
         return;
     }
     if (mode == GHR_SV_KAJIYA && face >= 0 && face < F) {  // (no strand here: the branch above returned)
@@ -384,7 +338,7 @@ GHR_HD void sv_shade_one_shadowed(int32_t seg, int32_t face, float t, int S, int
         if (tr[0] >= 0 && tr[0] < V && tr[1] >= 0 && tr[1] < V && tr[2] >= 0 && tr[2] < V) {
             const float *v0 = vertices + 3 * (size_t)tr[0], *v1 = vertices + 3 * (size_t)tr[1], *v2 = vertices + 3 * (size_t)tr[2];
             const float P[3] = {((v0[0] + v1[0]) + v2[0]) / 3.f, ((v0[1] + v1[1]) + v2[1]) / 3.f, ((v0[2] + v1[2]) + v2[2]) / 3.f};
-            sv_shade_head_shadowed(v0, v1, v2, sh, sv_shadow_at(sd, P, nullptr), rgb);
+            sv_shade_head(v0, v1, v2, sh, sv_shadow_at(sd, P, nullptr), rgb);
             return;
         }
     }
@@ -403,141 +357,52 @@ GHR_HD void sv_resolve_one(const uint8_t* src, int W, int s, int i, int j, uint8
 }
 
 // ---- the workspace ---------------------------------------------------------------------------------------------------------
-// Offsets in bytes, 16-B aligned.  [off_fill, off_fill + fill_bytes) is what a frame zeroes first: the tile counts and the length
-// of the big list.
-struct SvLayout {
-    uint64_t off_proj, off_rec, off_start, off_fill, off_count, off_nbig, fill_bytes, off_list, off_big, bytes;
-    uint64_t list_cap, n_points, n_segments;
-    int32_t tiles_x, tiles_y;
+// The tile lists of ghr_tilelists.h over the S L points and the S (L - 1) segments, and nothing else.
+struct SvLayout : TileListLayout {
+    uint64_t bytes, n_points, n_segments;
 };
 
 inline const char* sv_layout(int64_t S, int64_t L, int64_t H, int64_t W, SvLayout* Y)
 {
-    if (S < 0 || H < 0 || W < 0) return "negative size";
     if (L < 2) return "L < 2: a strand needs two points";
-    if (S > 0x7fffffff || L > 0x7fffffff || H > 0x7fffffff || W > 0x7fffffff) return "a size exceeds 2^31 - 1";
-    if ((uint64_t)H * (uint64_t)W > 0x7fffffffull) return "H * W exceeds 32-bit offsets";
-    if ((uint64_t)S * (uint64_t)L > 0x7fffffffull / 3) return "S * L * 3 exceeds 32-bit offsets";
-    const uint64_t tx = ((uint64_t)W + GHR_SV_TILE - 1) / GHR_SV_TILE, ty = ((uint64_t)H + GHR_SV_TILE - 1) / GHR_SV_TILE;
-    if (tx > 65535 || ty > 65535) return "image too large for 16-bit tile coordinates";
-    const uint64_t T = tx * ty, N = (uint64_t)S * (uint64_t)L, K = (uint64_t)S * (uint64_t)(L - 1);
-    const uint64_t per_seg = T < GHR_SV_BIG_RECT ? T : GHR_SV_BIG_RECT;
-    const uint64_t cap = K * per_seg;
-    if (cap > 0x7fffffffull) return "the tile lists exceed 32-bit offsets";
-    Y->tiles_x = (int32_t)tx; Y->tiles_y = (int32_t)ty;
-    Y->list_cap = cap; Y->n_points = N; Y->n_segments = K;
-    uint64_t off = 0;
-    Y->off_proj = off; off = mesh_up16(off + 16ull * N);
-    Y->off_rec = off; off = mesh_up16(off + 4ull * GHR_SV_REC_WORDS * K);
-    Y->off_start = off; off = mesh_up16(off + 4ull * (T + 1));
-    Y->off_fill = off;
-    Y->off_count = off; off = mesh_up16(off + 4ull * T);
-    Y->off_nbig = off; off += 16;
-    Y->fill_bytes = off - Y->off_fill;
-    Y->off_list = off; off = mesh_up16(off + 4ull * cap);
-    Y->off_big = off; off = mesh_up16(off + 4ull * K);
-    Y->bytes = off + 16;  // (never 0: a caller's allocation of `bytes` has an address)
+    if (S > 0 && L > (0x7fffffffll / 3) / S) return "S * L * 3 exceeds 32-bit offsets";
+    // (S * L fits from here on; a negative S is passed on as it is, for the refusal)
+    const int64_t N = S < 0 ? S : S * L, K = S < 0 ? S : S * (L - 1);
+    if (const char* why = tl_layout(N, K, H, W, GHR_SV_REC_UNITS, GHR_SV_BIG_RECT, Y)) return why;
+    Y->n_points = (uint64_t)N; Y->n_segments = (uint64_t)K;
+    Y->bytes = Y->off_fill + Y->fill_bytes + 16;  // (never 0: a caller's allocation of `bytes` has an address)
     return nullptr;
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------
 #if defined(__HIPCC__)
 struct SvArgs {
-    int32_t S, L, H, W, tiles_x, tiles_y;
-    uint32_t n_points, n_segments;
-    float near, r, head_bias;
-    float M[12];
-    const float* points;         // [S][L][3]
+    TileLists tl;                // points [S][L][3]; n_prims = S (L - 1)
+    int32_t L, H, W;
+    float r, head_bias;
     const int32_t* pix_to_face;  // [H][W] or NULL: no mesh
     const float* qf;             // [H][W] or NULL with it
-    float* proj;                 // [S L][4]
-    float* rec;                  // [S (L - 1)][8]
-    uint32_t* start;             // [T + 1]
-    uint32_t* count;             // [T]: counts, then fill cursors
-    uint32_t* nbig;
-    uint32_t* list;              // [list_cap]
-    uint32_t* big;               // [S (L - 1)]
-    uint32_t list_cap;
     int32_t* pix_to_segment;     // [H][W]
     float* t;                    // [H][W]
     int32_t* pix_to_face_out;    // [H][W]
     float* inv_depth;            // [H][W]
 };
 
-__global__ void __launch_bounds__(GHR_SV_BLOCK) k_sv_project(SvArgs a)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t v = blockIdx.x * GHR_SV_BLOCK + threadIdx.x;
-    if (v >= a.n_points) return;
-    const float X[3] = {a.points[3 * (size_t)v], a.points[3 * (size_t)v + 1], a.points[3 * (size_t)v + 2]};
-    float o[4];
-    vis_project_one(a.M, X, a.near, o);
-    reinterpret_cast<f4*>(a.proj)[v] = f4{o[0], o[1], o[2], o[3]};
-#endif
-}
-
 __global__ void __launch_bounds__(GHR_SV_BLOCK) k_sv_setup(SvArgs a)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     const uint32_t k = blockIdx.x * GHR_SV_BLOCK + threadIdx.x;
-    if (k >= a.n_segments) return;
+    if (k >= a.tl.n_prims) return;
     const uint32_t s = k / (uint32_t)(a.L - 1), i = k % (uint32_t)(a.L - 1);
     const size_t p = (size_t)s * (uint32_t)a.L + i;  // (p + 1 < S L)
-    const f4 pa = reinterpret_cast<const f4*>(a.proj)[p], pb = reinterpret_cast<const f4*>(a.proj)[p + 1];
+    const f4 pa = reinterpret_cast<const f4*>(a.tl.proj)[p], pb = reinterpret_cast<const f4*>(a.tl.proj)[p + 1];
     const float fa[4] = {pa.x, pa.y, pa.z, pa.w}, fb[4] = {pb.x, pb.y, pb.z, pb.w};
     float r[GHR_SV_REC_WORDS];
     sv_setup_one(fa, fb, a.r, a.H, a.W, r);
-    f4* out = reinterpret_cast<f4*>(a.rec) + 2 * (size_t)k;
+    f4* out = reinterpret_cast<f4*>(a.tl.rec) + 2 * (size_t)k;
     out[0] = f4{r[0], r[1], r[2], r[3]};
     out[1] = f4{r[4], r[5], r[6], r[7]};
-    uint32_t xy, bits;
-    memcpy(&xy, r + 6, 4); memcpy(&bits, r + 7, 4);
-    if (bits & GHR_SV_EMPTY) return;
-    if (bits & GHR_SV_BIG) {
-        const uint32_t pos = atomicAdd(a.nbig, 1u);
-        if (pos < a.n_segments) a.big[pos] = k;  // (one entry per segment at the most: always true)
-        return;
-    }
-    const uint32_t x0 = xy & 0xffffu, y0 = xy >> 16, nx = (bits >> 8) & 0xffu, ny = (bits >> 16) & 0xffu;
-    for (uint32_t y = y0; y <= y0 + ny; y++)
-        for (uint32_t x = x0; x <= x0 + nx; x++) atomicAdd(&a.count[y * (uint32_t)a.tiles_x + x], 1u);
-#endif
-}
-
-// One workgroup.  start[t] = the entries of the tiles before t; count[t] becomes the fill cursor of tile t (= start[t]).
-__global__ void __launch_bounds__(GHR_SV_BLOCK) k_sv_scan(SvArgs a)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    __shared__ uint32_t s_tmp[4];
-    const uint32_t T = (uint32_t)a.tiles_x * (uint32_t)a.tiles_y;
-    uint32_t run = 0u;
-    for (uint32_t base = 0u; base < T; base += GHR_SV_BLOCK) {
-        const uint32_t t = base + threadIdx.x;
-        const uint32_t n = t < T ? a.count[t] : 0u;
-        uint32_t total;
-        const uint32_t before = block_excl_scan_256(n, s_tmp, &total);
-        if (t < T) { a.start[t] = run + before; a.count[t] = run + before; }
-        run += total;
-        __syncthreads();  // s_tmp is written again in the next round
-    }
-    if (threadIdx.x == 0) a.start[T] = run;
-#endif
-}
-
-__global__ void __launch_bounds__(GHR_SV_BLOCK) k_sv_scatter(SvArgs a)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t k = blockIdx.x * GHR_SV_BLOCK + threadIdx.x;
-    if (k >= a.n_segments) return;
-    const uint32_t* r = reinterpret_cast<const uint32_t*>(a.rec) + (size_t)GHR_SV_REC_WORDS * k;
-    const uint32_t xy = r[6], bits = r[7];
-    if (bits & (GHR_SV_EMPTY | GHR_SV_BIG)) return;
-    const uint32_t x0 = xy & 0xffffu, y0 = xy >> 16, nx = (bits >> 8) & 0xffu, ny = (bits >> 16) & 0xffu;
-    for (uint32_t y = y0; y <= y0 + ny; y++)
-        for (uint32_t x = x0; x <= x0 + nx; x++) {
-            const uint32_t pos = atomicAdd(&a.count[y * (uint32_t)a.tiles_x + x], 1u);
-            if (pos < a.list_cap) a.list[pos] = k;  // (at most GHR_SV_BIG_RECT entries per segment: always true)
-        }
+    tl_count(a.tl, r + 6, k);
 #endif
 }
 
@@ -545,27 +410,27 @@ __global__ void __launch_bounds__(GHR_SV_BLOCK) k_sv_scatter(SvArgs a)
 __global__ void __launch_bounds__(GHR_SV_BLOCK) k_sv_raster(SvArgs a)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    __shared__ f4 s_rec[2 * GHR_SV_CHUNK];
+    __shared__ f4 s_rec[GHR_SV_REC_UNITS * GHR_SV_CHUNK];
     __shared__ uint32_t s_id[GHR_SV_CHUNK];
-    const uint32_t tile = blockIdx.y * (uint32_t)a.tiles_x + blockIdx.x;
     const int i = (int)blockIdx.y * GHR_SV_TILE + (int)threadIdx.x / GHR_SV_TILE;
     const int j = (int)blockIdx.x * GHR_SV_TILE + (int)threadIdx.x % GHR_SV_TILE;
     const bool in_image = i < a.H && j < a.W;
     const float px = (float)j + 0.5f, py = (float)i + 0.5f;
-    const uint32_t beg = a.start[tile], n_own = a.start[tile + 1] - beg;
-    const uint32_t n_big = a.n_segments > 0u ? min(*a.nbig, a.n_segments) : 0u;
-    const uint32_t n = n_own + n_big;  // (workgroup-uniform)
     float best_q = 0.f, best_t = 0.f;
     int32_t best_k = -1;
+    // tl_walk's loop, written out: through the shared walk this kernel measured 0.6 - 1 % slower per frame (profiles/strand_preview.txt)
+    const TileLists& tl = a.tl;
+    const uint32_t tile = blockIdx.y * (uint32_t)tl.tiles_x + blockIdx.x;
+    const uint32_t beg = tl.start[tile], n_own = tl.start[tile + 1] - beg;
+    const uint32_t n_big = tl.n_prims > 0u ? min(*tl.nbig, tl.n_prims) : 0u;
+    const uint32_t n = n_own + n_big;  // (workgroup-uniform)
     for (uint32_t c0 = 0u; c0 < n; c0 += GHR_SV_CHUNK) {
         const uint32_t m = min((uint32_t)GHR_SV_CHUNK, n - c0);
         if (threadIdx.x < 2u * m) {
             const uint32_t k = threadIdx.x / 2u, part = threadIdx.x % 2u, e = c0 + k;
-            // (beg + e < start[T] <= list_cap and every id < S (L - 1); the clamps keep a workspace that two streams were wrongly
-            // given at once from ever indexing outside it)
-            uint32_t id = e < n_own ? a.list[min(beg + e, a.list_cap - 1u)] : a.big[e - n_own];
-            id = min(id, a.n_segments - 1u);
-            s_rec[2u * k + part] = reinterpret_cast<const f4*>(a.rec)[2 * (size_t)id + part];
+            uint32_t id = e < n_own ? tl.list[min(beg + e, tl.list_cap - 1u)] : tl.big[e - n_own];  // (tl_walk's clamps)
+            id = min(id, tl.n_prims - 1u);
+            s_rec[2u * k + part] = reinterpret_cast<const f4*>(tl.rec)[2 * (size_t)id + part];
             if (part == 0u) s_id[k] = id;
         }
         __syncthreads();
@@ -606,47 +471,27 @@ typedef uint32_t sv_u4 __attribute__((ext_vector_type(4)));
 __global__ void __launch_bounds__(GHR_SV_BLOCK) k_sv_layers(SvLayersArgs la)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    __shared__ f4 s_rec[2 * GHR_SV_CHUNK];
+    __shared__ f4 s_rec[GHR_SV_REC_UNITS * GHR_SV_CHUNK];
     const SvArgs& a = la.a;
-    const uint32_t tile = blockIdx.y * (uint32_t)a.tiles_x + blockIdx.x;
+    const uint32_t tile = blockIdx.y * (uint32_t)a.tl.tiles_x + blockIdx.x;
     const int i = (int)blockIdx.y * GHR_SV_TILE + (int)threadIdx.x / GHR_SV_TILE;
     const int j = (int)blockIdx.x * GHR_SV_TILE + (int)threadIdx.x % GHR_SV_TILE;
     const bool in_image = i < a.H && j < a.W;
     const float px = (float)j + 0.5f, py = (float)i + 0.5f;
-    const uint32_t beg = a.start[tile], n_own = a.start[tile + 1] - beg;
-    const uint32_t n_big = a.n_segments > 0u ? min(*a.nbig, a.n_segments) : 0u;
-    const uint32_t n = n_own + n_big;  // (workgroup-uniform)
-    float best_q = 0.f, inv_q0 = 0.f;
+    const auto in_box = [&](const float* r) { return in_image && sv_in_box(r, a.r, px, py); };
+    float best_q = 0.f;
+    tl_walk<GHR_SV_REC_UNITS, GHR_SV_CHUNK, false>(a.tl, tile, s_rec, nullptr, in_box, [&](const float* r, uint32_t) {
+        float t, q;
+        if (sv_covers(r, a.r, px, py, &t, &q) && q > best_q) best_q = q;  // (a NaN or a q that is not > 0 never gets in)
+    });
+    const float inv_q0 = 1.f / best_q;  // (read only behind a covering segment with qs > 0: then best_q > 0)
     uint32_t n0 = 0u, n1 = 0u, n2 = 0u, n3 = 0u;
-    for (int walk = 0; walk < 2; walk++) {
-        if (walk == 1) inv_q0 = 1.f / best_q;  // (read only behind a covering segment with qs > 0: then best_q > 0)
-        for (uint32_t c0 = 0u; c0 < n; c0 += GHR_SV_CHUNK) {
-            const uint32_t m = min((uint32_t)GHR_SV_CHUNK, n - c0);
-            if (threadIdx.x < 2u * m) {
-                const uint32_t k = threadIdx.x / 2u, part = threadIdx.x % 2u, e = c0 + k;
-                // (the clamps of k_sv_raster: a workspace wrongly shared by two streams never indexes outside itself)
-                uint32_t id = e < n_own ? a.list[min(beg + e, a.list_cap - 1u)] : a.big[e - n_own];
-                id = min(id, a.n_segments - 1u);
-                s_rec[2u * k + part] = reinterpret_cast<const f4*>(a.rec)[2 * (size_t)id + part];
-            }
-            __syncthreads();
-            for (uint32_t k = 0u; k < m; k++) {
-                const f4 r0 = s_rec[2u * k], r1 = s_rec[2u * k + 1u];  // (one address per wave: broadcast)
-                const float r[GHR_SV_REC_WORDS] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-                const bool box = in_image && sv_in_box(r, a.r, px, py);
-                if (__builtin_amdgcn_ballot_w64(box) == 0ull) continue;  // nobody in this wave is inside the widened box
-                float t, q;
-                if (!(box && sv_covers(r, a.r, px, py, &t, &q))) continue;
-                if (walk == 0) {
-                    if (q > best_q) best_q = q;  // (a NaN or a q that is not > 0 never gets in)
-                } else if (q > 0.f) {
-                    const int layer = sv_layer_of(1.f / q - inv_q0, la.layer);
-                    n0 += layer == 0 ? 1u : 0u; n1 += layer == 1 ? 1u : 0u; n2 += layer == 2 ? 1u : 0u; n3 += layer == 3 ? 1u : 0u;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    tl_walk<GHR_SV_REC_UNITS, GHR_SV_CHUNK, false>(a.tl, tile, s_rec, nullptr, in_box, [&](const float* r, uint32_t) {
+        float t, q;
+        if (!(sv_covers(r, a.r, px, py, &t, &q) && q > 0.f)) return;
+        const int layer = sv_layer_of(1.f / q - inv_q0, la.layer);
+        n0 += layer == 0 ? 1u : 0u; n1 += layer == 1 ? 1u : 0u; n2 += layer == 2 ? 1u : 0u; n3 += layer == 3 ? 1u : 0u;
+    });
     if (!in_image) return;
     const size_t o = (size_t)i * a.W + j;
     la.q0[o] = best_q;

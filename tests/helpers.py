@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import shutil
 import subprocess
 
 import numpy as np
@@ -87,6 +88,32 @@ def assert_grads_close(got: dict, ref: dict, keys=None, tol=TOL):
 
 
 # --------------------------------------------------------------------------------------------------------------------
+HOSTSIM = os.path.join(ROOT, "tests", "hostsim")
+CSRC = os.path.join(ROOT, "gaussianhaircut_amd", "csrc")
+
+
+def host_cxx():
+    """ROCm's clang++ first: it links the sanitizer runtimes statically, so the program needs nothing from its environment"""
+    import pytest
+    for cand in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++"), shutil.which("g++")):
+        if cand and os.path.exists(cand):
+            return cand
+    pytest.skip("no host C++ compiler found")
+
+
+def compile_hostsim(out_name, src_name, extra, deps):
+    """tests/hostsim/<src_name> as plain C++ into tests/hostsim/_build/<out_name>, again when the source or one of `deps` (file names
+    under tests/hostsim or csrc that it includes) is newer."""
+    src = os.path.join(HOSTSIM, src_name)
+    out = os.path.join(HOSTSIM, "_build", out_name)
+    dep_paths = [src] + [os.path.join(HOSTSIM if os.path.exists(os.path.join(HOSTSIM, d)) else CSRC, d) for d in deps]
+    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in dep_paths):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        subprocess.run([host_cxx(), "-x", "c++", "-std=c++17", "-ffp-contract=off", "-g", "-Wall", "-Werror"] + extra + ["-o", out, src],
+                       check=True)
+    return out
+
+
 class _ViewArgs(ctypes.Structure):
     _fields_ = [
         ("P", ctypes.c_int32), ("W", ctypes.c_int32), ("H", ctypes.c_int32), ("C", ctypes.c_int32),

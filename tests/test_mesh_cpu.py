@@ -10,7 +10,6 @@ Every result is a boolean or an integer: every comparison is exact.
  4. the PyTorch comparator (fused=False) on CPU tensors against the model; the refusals of the C ABI."""
 import ctypes
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -24,32 +23,12 @@ from tests import mesh_cases as mc
 
 CASES = list(mc.meshes())
 CLOSED = [n for n in CASES if mc.meshes()[n][3]]
-HOSTSIM = os.path.join(hp.ROOT, "tests", "hostsim")
-
-
-def _cxx():
-    """ROCm's clang++ first: it links the sanitizer runtimes statically, so the program needs nothing from its environment"""
-    for cand in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++"), shutil.which("g++")):
-        if cand and os.path.exists(cand):
-            return cand
-    pytest.skip("no host C++ compiler found")
-
-
-def _compile(out_name, src_name, extra):
-    src = os.path.join(HOSTSIM, src_name)
-    out_dir = os.path.join(HOSTSIM, "_build")
-    out = os.path.join(out_dir, out_name)
-    deps = [src, os.path.join(HOSTSIM, "ghr_hostsim_mesh.cpp"), os.path.join(hp.ROOT, "gaussianhaircut_amd", "csrc", "ghr_mesh.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(out_dir, exist_ok=True)
-        subprocess.run([_cxx(), "-x", "c++", "-std=c++17", "-ffp-contract=off", "-g", "-Wall", "-Werror"] + extra + ["-o", out, src],
-                       check=True)
-    return out
+DEPS = ["ghr_hostsim_mesh.cpp", "ghr_mesh.h"]
 
 
 @pytest.fixture(scope="module")
 def sim():
-    L = ctypes.CDLL(_compile("libghr_hostsim_mesh.so", "ghr_hostsim_mesh.cpp", ["-O2", "-fPIC", "-shared"]))
+    L = ctypes.CDLL(hp.compile_hostsim("libghr_hostsim_mesh.so", "ghr_hostsim_mesh.cpp", ["-O2", "-fPIC", "-shared"], DEPS))
     vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
     L.ghrsim_mesh_sizes.argtypes = [i32, vp, i32, vp, i32, vp, vp]
     L.ghrsim_mesh_build.argtypes = [i32, vp, i32, vp, i32, vp, ctypes.c_ulonglong, vp]
@@ -232,9 +211,9 @@ def test_sanitized_stand_alone_program_runs_the_cases_clean(tmp_path, model):
     """ghr_mesh_selfcheck: the builder, the table check, contains and the probe function under AddressSanitizer and
     UndefinedBehaviorSanitizer, as a program of its own (exact-size buffers); the non-finite queries ride along."""
     san = ["-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
-    if os.path.basename(_cxx()) == "g++":
+    if os.path.basename(hp.host_cxx()) == "g++":
         san += ["-static-libasan", "-static-libubsan"]
-    exe = _compile("ghr_mesh_selfcheck_san", "ghr_mesh_selfcheck.cpp", san)
+    exe = hp.compile_hostsim("ghr_mesh_selfcheck_san", "ghr_mesh_selfcheck.cpp", san, DEPS)
     path = str(tmp_path / "cases.bin")
     with open(path, "wb") as fh:
         for name in CASES:

@@ -14,7 +14,6 @@
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -25,8 +24,6 @@ from gaussianhaircut_amd import _lib
 from gaussianhaircut_amd import strand_prior as sp
 from tests import helpers as hp
 from tests import sds_cases as sc
-
-HOSTSIM = os.path.join(hp.ROOT, "tests", "hostsim")
 
 SMALL, case = sc.SMALL, sc.case
 
@@ -120,29 +117,12 @@ def test_draw_and_size_refusals():
 
 
 # ---- 2 ------------------------------------------------------------------------------------------------------------------------
-def _cxx():
-    """ROCm's clang++ first: it links the sanitizer runtimes statically, so the program needs nothing from its environment"""
-    for cand in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++"), shutil.which("g++")):
-        if cand and os.path.exists(cand):
-            return cand
-    pytest.skip("no host C++ compiler found")
-
-
-def _compile(out_name, src_name, extra):
-    src = os.path.join(HOSTSIM, src_name)
-    out_dir = os.path.join(HOSTSIM, "_build")
-    out = os.path.join(out_dir, out_name)
-    deps = [src, os.path.join(HOSTSIM, "ghr_hostsim_sds.cpp"), os.path.join(hp.ROOT, "gaussianhaircut_amd", "csrc", "ghr_sds.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(out_dir, exist_ok=True)
-        subprocess.run([_cxx(), "-x", "c++", "-std=c++17", "-ffp-contract=off", "-g", "-Wall", "-Werror"] + extra + ["-o", out, src],
-                       check=True)
-    return out
+DEPS = ["ghr_hostsim_sds.cpp", "ghr_sds.h"]
 
 
 @pytest.fixture(scope="module")
 def sim():
-    L = ctypes.CDLL(_compile("libghr_hostsim_sds.so", "ghr_hostsim_sds.cpp", ["-O2", "-fPIC", "-shared"]))
+    L = ctypes.CDLL(hp.compile_hostsim("libghr_hostsim_sds.so", "ghr_hostsim_sds.cpp", ["-O2", "-fPIC", "-shared"], DEPS))
     vp, i32, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
     L.ghrsim_sds_local.argtypes = [i32, i32, i32, vp, vp, i32, vp, f32, vp, vp]
     L.ghrsim_sds_local_backward.argtypes = [i32, i32, i32, vp, i32, vp, vp, f32, vp, vp, vp]
@@ -252,9 +232,9 @@ def test_sanitized_stand_alone_program_runs_the_walks_clean(sim, tmp_path):
     """ghr_sds_selfcheck: the per-element functions and the walks under AddressSanitizer and UndefinedBehaviorSanitizer, as a
     program of its own (exact-size buffers)."""
     san = ["-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
-    if os.path.basename(_cxx()) == "g++":
+    if os.path.basename(hp.host_cxx()) == "g++":
         san += ["-static-libasan", "-static-libubsan"]
-    exe = _compile("ghr_sds_selfcheck_san", "ghr_sds_selfcheck.cpp", san)
+    exe = hp.compile_hostsim("ghr_sds_selfcheck_san", "ghr_sds_selfcheck.cpp", san, DEPS)
     path = str(tmp_path / "cases.bin")
     names = sorted(SMALL)
     with open(path, "wb") as fh:

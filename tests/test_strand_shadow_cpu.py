@@ -22,29 +22,15 @@ from gaussianhaircut_amd import strand_view as sv
 from tests import helpers as hp
 from tests import strand_shadow_cases as ss
 from tests import strand_view_cases as sc
-from tests.test_strand_view_cpu import _cxx, _p, _same_bits, _shading_bytes
+from tests.test_strand_view_cpu import SV_HEADERS, _p, _same_bits, _shading_bytes
 
-HOSTSIM = os.path.join(hp.ROOT, "tests", "hostsim")
+DEPS = ["ghr_hostsim_strandshadow.cpp"] + SV_HEADERS
 MAPS, FRAMES = ss.MAPS, ss.FRAMES
-
-
-def _compile(out_name, src_name, extra):
-    src = os.path.join(HOSTSIM, src_name)
-    out_dir = os.path.join(HOSTSIM, "_build")
-    out = os.path.join(out_dir, out_name)
-    csrc = os.path.join(hp.ROOT, "gaussianhaircut_amd", "csrc")
-    deps = [src, os.path.join(HOSTSIM, "ghr_hostsim_strandshadow.cpp")] + [os.path.join(csrc, h) for h in
-                                                                           ("ghr_strandview.h", "ghr_visibility.h", "ghr_mesh.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(out_dir, exist_ok=True)
-        subprocess.run([_cxx(), "-x", "c++", "-std=c++17", "-ffp-contract=off", "-g", "-Wall", "-Werror"] + extra + ["-o", out, src],
-                       check=True)
-    return out
 
 
 @pytest.fixture(scope="module")
 def sim():
-    L = ctypes.CDLL(_compile("libghr_hostsim_strandshadow.so", "ghr_hostsim_strandshadow.cpp", ["-O2", "-fPIC", "-shared"]))
+    L = ctypes.CDLL(hp.compile_hostsim("libghr_hostsim_strandshadow.so", "ghr_hostsim_strandshadow.cpp", ["-O2", "-fPIC", "-shared"], DEPS))
     vp, i32, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
     L.ghrsim_ss_opacity.argtypes = [i32, i32, vp, vp, f32, i32, i32, f32, f32, vp, vp, vp, vp]
     L.ghrsim_ss_lookup.argtypes = [i32, vp, vp, f32, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp]
@@ -203,9 +189,9 @@ def test_sanitized_stand_alone_program_runs_the_cases_clean(tmp_path):
     """ghr_strandshadow_selfcheck: the per-element functions and the two-walk light pass under AddressSanitizer and
     UndefinedBehaviorSanitizer, as a program of its own (exact-size buffers)."""
     san = ["-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
-    if os.path.basename(_cxx()) == "g++":
+    if os.path.basename(hp.host_cxx()) == "g++":
         san += ["-static-libasan", "-static-libubsan"]
-    exe = _compile("ghr_strandshadow_selfcheck_san", "ghr_strandshadow_selfcheck.cpp", san)
+    exe = hp.compile_hostsim("ghr_strandshadow_selfcheck_san", "ghr_strandshadow_selfcheck.cpp", san, DEPS)
     path = str(tmp_path / "cases.bin")
     raw = lambda a: np.ascontiguousarray(a).tobytes()  # noqa: E731
     with open(path, "wb") as fh:

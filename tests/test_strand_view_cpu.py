@@ -11,7 +11,6 @@ Every result is an integer, a byte or a float32 compared by its bits: every comp
  4. camera_path against a restatement with scipy; the refusals of the C ABI."""
 import ctypes
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -24,34 +23,13 @@ from tests import helpers as hp
 from tests import strand_view_cases as sc
 
 CASES = sc.CASES
-HOSTSIM = os.path.join(hp.ROOT, "tests", "hostsim")
-
-
-def _cxx():
-    """ROCm's clang++ first: it links the sanitizer runtimes statically, so the program needs nothing from its environment"""
-    for cand in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++"), shutil.which("g++")):
-        if cand and os.path.exists(cand):
-            return cand
-    pytest.skip("no host C++ compiler found")
-
-
-def _compile(out_name, src_name, extra):
-    src = os.path.join(HOSTSIM, src_name)
-    out_dir = os.path.join(HOSTSIM, "_build")
-    out = os.path.join(out_dir, out_name)
-    csrc = os.path.join(hp.ROOT, "gaussianhaircut_amd", "csrc")
-    deps = [src, os.path.join(HOSTSIM, "ghr_hostsim_strandview.cpp")] + [os.path.join(csrc, h) for h in
-                                                                         ("ghr_strandview.h", "ghr_visibility.h", "ghr_mesh.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(out_dir, exist_ok=True)
-        subprocess.run([_cxx(), "-x", "c++", "-std=c++17", "-ffp-contract=off", "-g", "-Wall", "-Werror"] + extra + ["-o", out, src],
-                       check=True)
-    return out
+SV_HEADERS = ["ghr_hostsim_tilelists.h", "ghr_strandview.h", "ghr_visibility.h", "ghr_tilelists.h", "ghr_mesh.h"]
+DEPS = ["ghr_hostsim_strandview.cpp"] + SV_HEADERS
 
 
 @pytest.fixture(scope="module")
 def sim():
-    L = ctypes.CDLL(_compile("libghr_hostsim_strandview.so", "ghr_hostsim_strandview.cpp", ["-O2", "-fPIC", "-shared"]))
+    L = ctypes.CDLL(hp.compile_hostsim("libghr_hostsim_strandview.so", "ghr_hostsim_strandview.cpp", ["-O2", "-fPIC", "-shared"], DEPS))
     vp, i32, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
     L.ghrsim_sv_face_depth.argtypes = [i32, vp, i32, vp, vp, f32, i32, i32, vp, vp]
     L.ghrsim_sv_raster.argtypes = [i32, i32, vp, vp, f32, i32, i32, f32, f32] + [vp] * 8
@@ -184,9 +162,9 @@ def test_sanitized_stand_alone_program_runs_the_cases_clean(tmp_path):
     """ghr_strandview_selfcheck: the per-element functions and the table walk under AddressSanitizer and
     UndefinedBehaviorSanitizer, as a program of its own (exact-size buffers)."""
     san = ["-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
-    if os.path.basename(_cxx()) == "g++":
+    if os.path.basename(hp.host_cxx()) == "g++":
         san += ["-static-libasan", "-static-libubsan"]
-    exe = _compile("ghr_strandview_selfcheck_san", "ghr_strandview_selfcheck.cpp", san)
+    exe = hp.compile_hostsim("ghr_strandview_selfcheck_san", "ghr_strandview_selfcheck.cpp", san, DEPS)
     path = str(tmp_path / "cases.bin")
     with open(path, "wb") as fh:
         for name in CASES:

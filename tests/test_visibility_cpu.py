@@ -14,7 +14,6 @@ Every result is an integer or a byte: every comparison is exact.
 import ctypes
 import os
 import pickle
-import shutil
 import subprocess
 
 import numpy as np
@@ -29,33 +28,12 @@ from tests import helpers as hp
 from tests import visibility_cases as vc
 
 CASES = list(vc.CASES)
-HOSTSIM = os.path.join(hp.ROOT, "tests", "hostsim")
-
-
-def _cxx():
-    """ROCm's clang++ first: it links the sanitizer runtimes statically, so the program needs nothing from its environment"""
-    for cand in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++"), shutil.which("g++")):
-        if cand and os.path.exists(cand):
-            return cand
-    pytest.skip("no host C++ compiler found")
-
-
-def _compile(out_name, src_name, extra):
-    src = os.path.join(HOSTSIM, src_name)
-    out_dir = os.path.join(HOSTSIM, "_build")
-    out = os.path.join(out_dir, out_name)
-    csrc = os.path.join(hp.ROOT, "gaussianhaircut_amd", "csrc")
-    deps = [src, os.path.join(HOSTSIM, "ghr_hostsim_visibility.cpp"), os.path.join(csrc, "ghr_visibility.h"), os.path.join(csrc, "ghr_mesh.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(out_dir, exist_ok=True)
-        subprocess.run([_cxx(), "-x", "c++", "-std=c++17", "-ffp-contract=off", "-g", "-Wall", "-Werror"] + extra + ["-o", out, src],
-                       check=True)
-    return out
+DEPS = ["ghr_hostsim_visibility.cpp", "ghr_hostsim_tilelists.h", "ghr_visibility.h", "ghr_tilelists.h", "ghr_mesh.h"]
 
 
 @pytest.fixture(scope="module")
 def sim():
-    L = ctypes.CDLL(_compile("libghr_hostsim_visibility.so", "ghr_hostsim_visibility.cpp", ["-O2", "-fPIC", "-shared"]))
+    L = ctypes.CDLL(hp.compile_hostsim("libghr_hostsim_visibility.so", "ghr_hostsim_visibility.cpp", ["-O2", "-fPIC", "-shared"], DEPS))
     vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
     L.ghrsim_vis_sizes.argtypes = [i64, i64, i64, i64, ctypes.POINTER(ctypes.c_ulonglong), vp]
     L.ghrsim_vis_head_mask.argtypes = [i32, i32, vp, vp, vp]
@@ -169,9 +147,9 @@ def test_sanitized_stand_alone_program_runs_the_cases_clean(tmp_path):
     """ghr_visibility_selfcheck: the per-element functions and the table walk under AddressSanitizer and
     UndefinedBehaviorSanitizer, as a program of its own (exact-size buffers)."""
     san = ["-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
-    if os.path.basename(_cxx()) == "g++":
+    if os.path.basename(hp.host_cxx()) == "g++":
         san += ["-static-libasan", "-static-libubsan"]
-    exe = _compile("ghr_visibility_selfcheck_san", "ghr_visibility_selfcheck.cpp", san)
+    exe = hp.compile_hostsim("ghr_visibility_selfcheck_san", "ghr_visibility_selfcheck.cpp", san, DEPS)
     path = str(tmp_path / "cases.bin")
     with open(path, "wb") as fh:
         for name in CASES:
