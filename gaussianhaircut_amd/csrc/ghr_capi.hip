@@ -1625,11 +1625,17 @@ int ghr_mark_visible(void* stream, int32_t P, const float* means3D, const float*
     return finish(s, 0);
 }
 
+static_assert(GHR_KNN_ALIGN == ALIGN, "a cloud's regions are aligned like every workspace");
+
+static void knn_boxes(hipStream_t s, const ghr::KnnCloud& c, const float* points, const int64_t* order)
+{
+    hipLaunchKernelGGL(ghr::k_knn_boxes, dim3((unsigned)c.nsuper), dim3(64 * GHR_KNN_WAVES), 0, s, c, points, (const long long*)order);
+}
+
 int ghr_knn_workspace_size(int64_t P, size_t* bytes)
 {
     if (!bytes || P < 0 || P >= ((int64_t)1 << 31)) return fail(GHR_E_INVALID, "ghr_knn_workspace_size: bad args");
-    const size_t nb = ((size_t)P + GHR_KNN_BLOCK - 1) / GHR_KNN_BLOCK, ns = (nb + GHR_KNN_SUPER - 1) / GHR_KNN_SUPER;
-    *bytes = up((size_t)P * sizeof(float4)) + up(nb * 2 * sizeof(float4)) + up(ns * 2 * sizeof(float4)) + ALIGN;
+    *bytes = ghr::knn_layout((uint64_t)P).bytes + ALIGN;
     return GHR_OK;
 }
 
@@ -1649,16 +1655,11 @@ int ghr_knn_mean_dist2(void* stream, int64_t P, const float* points, const int64
     if (P < 0 || P >= ((int64_t)1 << 31)) return fail(GHR_E_INVALID, "ghr_knn_mean_dist2: P must be in [0, 2^31)");
     if (P == 0) return GHR_OK;
     if (!points || !order || !ws || !out) return fail(GHR_E_INVALID, "ghr_knn_mean_dist2: NULL buffer");
-    const size_t nb = ((size_t)P + GHR_KNN_BLOCK - 1) / GHR_KNN_BLOCK, ns = (nb + GHR_KNN_SUPER - 1) / GHR_KNN_SUPER;
-    char* base = align_base(ws);
-    float4* sorted = (float4*)base;
-    float4* bbox = (float4*)(base + up((size_t)P * sizeof(float4)));
-    float4* sbox = (float4*)((char*)bbox + up(nb * 2 * sizeof(float4)));
+    const ghr::KnnCloud c = ghr::knn_cloud(align_base(ws), (uint64_t)P);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(ghr::k_knn_boxes, dim3((unsigned)ns), dim3(64 * GHR_KNN_WAVES), 0, s, (int)P, points,
-                       (const long long*)order, sorted, bbox, sbox);
-    hipLaunchKernelGGL(ghr::k_knn_search, dim3((unsigned)((nb + GHR_KNN_WAVES - 1) / GHR_KNN_WAVES)),
-                       dim3(64 * GHR_KNN_WAVES), 0, s, (int)P, sorted, bbox, sbox, out);
+    knn_boxes(s, c, points, order);
+    hipLaunchKernelGGL(ghr::k_knn_search, dim3((unsigned)((c.nblocks + GHR_KNN_WAVES - 1) / GHR_KNN_WAVES)),
+                       dim3(64 * GHR_KNN_WAVES), 0, s, c, out);
     return finish(s, 0);
 }
 
@@ -1671,18 +1672,12 @@ static int nn_sizes(const char* fn, int64_t Px, int64_t Py)
     return GHR_OK;
 }
 
-static size_t nn_cloud_bytes(size_t P)
-{
-    const size_t nb = (P + GHR_KNN_BLOCK - 1) / GHR_KNN_BLOCK, ns = (nb + GHR_KNN_SUPER - 1) / GHR_KNN_SUPER;
-    return up(P * sizeof(float4)) + up(nb * 2 * sizeof(float4)) + up(ns * 2 * sizeof(float4));
-}
-
 int ghr_nn_workspace_size(int64_t Px, int64_t Py, size_t* bytes)
 {
     static const char* fn = "ghr_nn_workspace_size: %s";
     if (!bytes) return fail(GHR_E_INVALID, fn, "bytes is NULL");
     if (int rc = nn_sizes(fn, Px, Py)) return rc;
-    *bytes = nn_cloud_bytes((size_t)Px) + nn_cloud_bytes((size_t)Py) + ALIGN;
+    *bytes = ghr::knn_layout((uint64_t)Px).bytes + ghr::knn_layout((uint64_t)Py).bytes + ALIGN;
     return GHR_OK;
 }
 
@@ -1697,28 +1692,16 @@ int ghr_nn_search(void* stream, int64_t Px, const float* x, const int64_t* order
     if (!x || !order_x || !keys_x_sorted) return fail(GHR_E_INVALID, fn, "x, order_x or keys_x_sorted is NULL");
     if (!y || !order_y || !keys_y_sorted) return fail(GHR_E_INVALID, fn, "y, order_y or keys_y_sorted is NULL");
     if (!ws || !dist || !idx) return fail(GHR_E_INVALID, fn, "ws, dist or idx is NULL");
-    const size_t nbx = ((size_t)Px + GHR_KNN_BLOCK - 1) / GHR_KNN_BLOCK, nsx = (nbx + GHR_KNN_SUPER - 1) / GHR_KNN_SUPER;
-    const size_t nby = ((size_t)Py + GHR_KNN_BLOCK - 1) / GHR_KNN_BLOCK, nsy = (nby + GHR_KNN_SUPER - 1) / GHR_KNN_SUPER;
     char* base = align_base(ws);
-    float4* xs = (float4*)base;
-    float4* bbox_x = (float4*)(base + up((size_t)Px * sizeof(float4)));
-    float4* sbox_x = (float4*)((char*)bbox_x + up(nbx * 2 * sizeof(float4)));
-    base += nn_cloud_bytes((size_t)Px);
-    float4* ys = (float4*)base;
-    float4* bbox_y = (float4*)(base + up((size_t)Py * sizeof(float4)));
-    float4* sbox_y = (float4*)((char*)bbox_y + up(nby * 2 * sizeof(float4)));
+    const ghr::KnnCloud cx = ghr::knn_cloud(base, (uint64_t)Px);
+    const ghr::KnnCloud cy = ghr::knn_cloud(base + ghr::knn_layout((uint64_t)Px).bytes, (uint64_t)Py);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(ghr::k_knn_boxes, dim3((unsigned)nsx), dim3(64 * GHR_KNN_WAVES), 0, s, (int)Px, x, (const long long*)order_x,
-                       xs, bbox_x, sbox_x);
-    hipLaunchKernelGGL(ghr::k_knn_boxes, dim3((unsigned)nsy), dim3(64 * GHR_KNN_WAVES), 0, s, (int)Py, y, (const long long*)order_y,
-                       ys, bbox_y, sbox_y);
-    const dim3 grid((unsigned)((nbx + GHR_NN_WAVES - 1) / GHR_NN_WAVES)), block(64 * GHR_NN_WAVES);
-    if (norm == 2)
-        hipLaunchKernelGGL(ghr::k_nn_search<2>, grid, block, 0, s, (int)Px, xs, (const unsigned long long*)keys_x_sorted, (int)Py, ys,
-                           bbox_y, sbox_y, (const unsigned long long*)keys_y_sorted, dist, idx);
-    else
-        hipLaunchKernelGGL(ghr::k_nn_search<1>, grid, block, 0, s, (int)Px, xs, (const unsigned long long*)keys_x_sorted, (int)Py, ys,
-                           bbox_y, sbox_y, (const unsigned long long*)keys_y_sorted, dist, idx);
+    knn_boxes(s, cx, x, order_x);
+    knn_boxes(s, cy, y, order_y);
+    const dim3 grid((unsigned)((cx.nblocks + GHR_NN_WAVES - 1) / GHR_NN_WAVES)), block(64 * GHR_NN_WAVES);
+    const auto kx = (const unsigned long long*)keys_x_sorted, ky = (const unsigned long long*)keys_y_sorted;
+    if (norm == 2) hipLaunchKernelGGL(ghr::k_nn_search<2>, grid, block, 0, s, cx, kx, cy, ky, dist, idx);
+    else hipLaunchKernelGGL(ghr::k_nn_search<1>, grid, block, 0, s, cx, kx, cy, ky, dist, idx);
     return finish(s, 0);
 }
 

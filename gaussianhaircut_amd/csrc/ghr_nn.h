@@ -13,22 +13,18 @@
 //
 // Pipeline (ghr_knn_keys on both clouds with the bounds of their UNION -- equal keys then mean equal places --, a key sort of
 // each on the host side, ghr_nn_search):
-//   k_knn_boxes   (ghr_knn.h, unchanged) once per cloud: points in key order as float4 (x, y, z, original index as bits) and
-//                 the boxes of every block of 64 and every superblock of 64 blocks; of x only the sorted points are used.
-//   k_nn_search   one wave per block of 64 queries in the key order of x, one query per lane.  The walk is k_knn_search's:
-//                 superblocks some lane still needs, then blocks some lane still needs (wave ballots), each needed block loaded
-//                 once as 64 coalesced float4 into the wave's private LDS tile and scanned by all lanes.  Two differences:
-//     seed        there is no own block, and without a first bound every box passes.  The wave takes the y block at which the
-//                 key of its median query would be inserted into y's sorted keys (a binary search on wave-uniform values,
-//                 i.e. scalar code), scans it first and walks from its superblock on.  The seed decides speed only: the
-//                 winner under the total order above does not depend on the order candidates are met in.
-//     pruning     a box is skipped when boxdist > best, NOT >=: a box at exactly the best distance may hold a lower index
-//                 that ties.  boxdist is a true lower bound of the fp32 d of every point in the box (knn_box_dist for
-//                 norm 2, nn_box_dist_l1 for norm 1), so a skipped point has d > best and can neither win nor tie.  The price
-//                 of the tie rule: with exact duplicates (best = 0) every box that CONTAINS the query is scanned, where
-//                 k_knn_search's >= would skip them.
-//   A lane whose own box test failed scans the block too: its d >= boxdist > best cannot enter.
-//
+//   k_knn_boxes   (ghr_knn.h) once per cloud: points in key order as float4 (x, y, z, original index as bits) and the boxes of
+//                 every block of 64 and every superblock of 64 blocks; of x only the sorted points are used.
+//   k_nn_search   one wave per block of 64 queries in the key order of x, one query per lane, around knn_walk (ghr_knn.h) over
+//                 y's cloud.  Its own are the walk's first block and the policy NnNearest<NORM>:
+//     seed        there is no own block, and without a first bound every box passes.  The first block is the y block at which
+//                 the key of the wave's median query would be inserted into y's sorted keys (nn_seed_block: wave-uniform
+//                 values, i.e. scalar code), nothing skipped in it.  The seed decides speed only: the winner under the
+//                 total order above does not depend on the order candidates are met in.
+//     pruning     a lane needs a box unless boxdist > best, NOT >=: a box at exactly the best distance may hold a lower index
+//                 that ties.  boxdist (knn_box_dist, nn_box_dist_l1) is a true lower bound of the fp32 d of every point in
+//                 the box, so a skipped point can neither win nor tie.  The price: with exact duplicates (best = 0) every
+//                 box that CONTAINS the query is scanned, where distCUDA2's >= would skip them.
 //   k_chamfer_point   one thread per query, a kernel of its own (the search keeps its registers for the walk, and many callers
 //                 want no normals): term[i] = 1 - cos or 1 - |cos|, cos = (a . b) / (max(|a|, eps) max(|b|, eps)), eps = 1e-6,
 //                 a = x_normals[i], b = y_normals[idx[i]] (the formula torch documents for F.cosine_similarity); and
@@ -39,26 +35,21 @@
 //                 cosine term.  y side (k_chamfer_bwd_y), one thread per candidate: the caller gives the inverted lists
 //                 (start [Py + 1], members in ASCENDING i: a stable sort of idx, integers only); the thread walks its list
 //                 with one fp32 accumulator per component, the first product assigned, later ones added.  A candidate nobody
-//                 chose gets +0.  The same bits run after run.
+//                 chose gets +0.  The same bits run after run.  (Kernels under __HIPCC__; the rest is GHR_HD for the host walk.)
 #pragma once
 #include "ghr_knn.h"
-
-namespace ghr {
 
 #define GHR_NN_WAVES 4        // waves per workgroup of k_nn_search
 #define GHR_NN_BLOCK 256      // threads per workgroup of the per-point kernels
 #define GHR_NN_COS_EPS 1e-6f
 
-#ifdef GHR_NN_COUNT_BLOCKS
-// measurement build only (tools/build_variant.sh -DGHR_NN_COUNT_BLOCKS): [0] candidate blocks scanned, [1] waves
-__device__ unsigned long long g_nn_count[2];
-#endif
+namespace ghr {
 
 // The L1 sibling of knn_box_dist: a lower bound of d = (|dx| + |dy|) + |dz| from q to any point c inside [lo, hi].  Along x,
 // as there: q.x < lo.x gives fl(c.x - q.x) >= fl(lo.x - q.x) = gx >= 0 (fp32 subtraction is monotone under round-to-nearest),
 // q.x > hi.x gives |fl(c.x - q.x)| = fl(q.x - c.x) >= fl(q.x - hi.x) = gx, otherwise gx = 0; so |dx| >= gx, and likewise y, z.
 // Adding non-negative values is monotone in each operand, and the bound adds in d's order, so boxdist <= d, inf included.
-__device__ __forceinline__ float nn_box_dist_l1(float3 q, float4 lo, float4 hi)
+GHR_HD float nn_box_dist_l1(float3 q, float4 lo, float4 hi)
 {
     const float gx = fmaxf(fmaxf(lo.x - q.x, q.x - hi.x), 0.f);
     const float gy = fmaxf(fmaxf(lo.y - q.y, q.y - hi.y), 0.f);
@@ -67,101 +58,77 @@ __device__ __forceinline__ float nn_box_dist_l1(float3 q, float4 lo, float4 hi)
 }
 
 template <int NORM>
-__device__ __forceinline__ float nn_box_dist(float3 q, float4 lo, float4 hi)
+GHR_HD float nn_dist(const float4& c, const float3& q)
 {
-    return NORM == 2 ? knn_box_dist(q, lo, hi) : nn_box_dist_l1(q, lo, hi);
+    return NORM == 2 ? knn_dist2(c, q) : (fabsf(c.x - q.x) + fabsf(c.y - q.y)) + fabsf(c.z - q.z);
 }
 
-// Scans n (<= 64) candidates of the block staged in `tile`: (d, original index) ascending, a NaN d never enters.
-template <int NORM>
-__device__ __forceinline__ void nn_scan_tile(const float4* tile, int n, float3 q, float& best, int& besti)
+// (d, original index) ascending; a NaN d never enters
+GHR_HD void nn_take(float d, int cj, float& best, int& besti)
 {
-    for (int j = 0; j < n; ++j) {
-        const float4 c = tile[j];  // the same address in every lane: an LDS broadcast
-        const float dx = c.x - q.x, dy = c.y - q.y, dz = c.z - q.z;
-        const float d = NORM == 2 ? (dx * dx + dy * dy) + dz * dz : (fabsf(dx) + fabsf(dy)) + fabsf(dz);
-        const int cj = __float_as_int(c.w);
-        if (d < best || (d == best && cj < besti)) {
-            best = d;
-            besti = cj;
-        }
+    if (d < best || (d == best && cj < besti)) {
+        best = d;
+        besti = cj;
     }
 }
 
-// xs / ys: the clouds in key order (k_knn_boxes); keys_x / keys_y: their SORTED keys; bbox / sbox: y's boxes.
-// dist / idx: [Px], written at the queries' original indices.  Each wave works on its own, as in k_knn_search.
+// knn_walk's policy (see KnnTop3): the nearest candidate and, among equal d, the lowest original index.
 template <int NORM>
-__global__ void __launch_bounds__(64 * GHR_NN_WAVES) k_nn_search(int Px, const float4* __restrict__ xs,
-                                                                  const unsigned long long* __restrict__ keys_x, int Py,
-                                                                  const float4* __restrict__ ys,
-                                                                  const float4* __restrict__ bbox,
-                                                                  const float4* __restrict__ sbox,
-                                                                  const unsigned long long* __restrict__ keys_y,
+struct NnNearest {
+    // +inf, not FLT_MAX: a d that overflowed still has to find its lowest index; INT_MAX loses every index tie
+    float best = __builtin_inff();
+    int besti = 0x7fffffff;
+    GHR_HD float bound(float3 q, float4 lo, float4 hi) const { return NORM == 2 ? knn_box_dist(q, lo, hi) : nn_box_dist_l1(q, lo, hi); }
+    GHR_HD bool needs(float boxdist) const { return !(boxdist > best); }
+    GHR_HD void scan(const float4* tile, int n, int skip, float3 q)
+    {
+        float b = best;
+        int bi = besti;
+        for (int j = 0; j < n; ++j) {
+            const float4 c = tile[j];  // the same address in every lane: an LDS broadcast
+            const float d = nn_dist<NORM>(c, q);
+            if (j != skip) nn_take(d, knn_as_int(c.w), b, bi);
+        }
+        best = b;
+        besti = bi;
+    }
+    GHR_HD int index(int Py) const { return (unsigned)besti < (unsigned)Py ? besti : 0; }  // (every d NaN: nothing entered)
+};
+
+// The block of sorted keys [P] at which key kq would be inserted (lower bound), P >= 1.
+GHR_HD int nn_seed_block(const unsigned long long* keys, int P, unsigned long long kq)
+{
+    int lo = 0, hi = P;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < kq) lo = mid + 1; else hi = mid;
+    }
+    return (lo < P - 1 ? lo : P - 1) / GHR_KNN_BLOCK;
+}
+
+#if defined(__HIPCC__)
+// x / y: the clouds in key order (k_knn_boxes; of x only the sorted points are read); keys_x / keys_y: their SORTED keys.
+// dist / idx: [Px], written at the queries' original indices.
+template <int NORM>
+__global__ void __launch_bounds__(64 * GHR_NN_WAVES) k_nn_search(KnnCloud x, const unsigned long long* __restrict__ keys_x,
+                                                                  KnnCloud y, const unsigned long long* __restrict__ keys_y,
                                                                   float* __restrict__ dist, int* __restrict__ idx)
 {
     __shared__ float4 tiles[GHR_NN_WAVES][GHR_KNN_BLOCK];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float4* tile = tiles[wave];
-    const int nqb = (int)(((long long)Px + GHR_KNN_BLOCK - 1) / GHR_KNN_BLOCK);
-    const int nblocks = (int)(((long long)Py + GHR_KNN_BLOCK - 1) / GHR_KNN_BLOCK);
-    const int nsuper = (nblocks + GHR_KNN_SUPER - 1) / GHR_KNN_SUPER;
     const long long qb = (long long)blockIdx.x * GHR_NN_WAVES + wave;
-    if (qb >= nqb) return;
+    if (qb >= x.nblocks) return;
     const long long q0 = qb * GHR_KNN_BLOCK;
-    const bool valid = q0 + lane < Px;
-    const int nq = (int)min((long long)GHR_KNN_BLOCK, Px - q0);
-    const float4 q4 = xs[valid ? q0 + lane : q0];
-    const float3 q = make_float3(q4.x, q4.y, q4.z);
-    // +inf, not FLT_MAX: a d that overflowed still has to find its lowest index; INT_MAX loses every index tie
-    float best = __builtin_inff();
-    int besti = 0x7fffffff;
-
-    // seed: where the median query's key would be inserted into y's sorted keys (lower bound; wave-uniform)
-    const unsigned long long kq = keys_x[q0 + nq / 2];
-    int lo = 0, hi = Py;
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (keys_y[mid] < kq) lo = mid + 1; else hi = mid;
-    }
-    const int seed = min(lo, Py - 1) / GHR_KNN_BLOCK;
-    {
-        const int n = min(GHR_KNN_BLOCK, Py - seed * GHR_KNN_BLOCK);
-        if (lane < n) tile[lane] = ys[(long long)seed * GHR_KNN_BLOCK + lane];
-        knn_wave_lds_fence();
-        nn_scan_tile<NORM>(tile, n, q, best, besti);
-    }
-#ifdef GHR_NN_COUNT_BLOCKS
-    unsigned scanned = 1;
-#endif
-
-    const int seed_sb = seed / GHR_KNN_SUPER;
-    for (int s = 0; s < nsuper; ++s) {
-        const int sb = seed_sb + s < nsuper ? seed_sb + s : seed_sb + s - nsuper;  // the seed's superblock first
-        if (!__any(valid && !(nn_box_dist<NORM>(q, sbox[2 * sb], sbox[2 * sb + 1]) > best))) continue;
-        const int b_end = min(nblocks, (sb + 1) * GHR_KNN_SUPER);
-        for (int blk = sb * GHR_KNN_SUPER; blk < b_end; ++blk) {
-            if (blk == seed) continue;  // scanned above
-            if (!__any(valid && !(nn_box_dist<NORM>(q, bbox[2 * (long long)blk], bbox[2 * (long long)blk + 1]) > best))) continue;
-            const int n = min(GHR_KNN_BLOCK, Py - blk * GHR_KNN_BLOCK);
-            knn_wave_lds_fence();  // every lane is done reading the previous tile
-            if (lane < n) tile[lane] = ys[(long long)blk * GHR_KNN_BLOCK + lane];
-            knn_wave_lds_fence();
-            nn_scan_tile<NORM>(tile, n, q, best, besti);
-#ifdef GHR_NN_COUNT_BLOCKS
-            ++scanned;
-#endif
-        }
-    }
-#ifdef GHR_NN_COUNT_BLOCKS
-    if (lane == 0) {
-        atomicAdd(&g_nn_count[0], (unsigned long long)scanned);
-        atomicAdd(&g_nn_count[1], 1ull);
-    }
-#endif
+    const bool valid = q0 + lane < x.P;
+    const int nq = (int)min((long long)GHR_KNN_BLOCK, x.P - q0);
+    const float4 q4 = x.sorted[valid ? q0 + lane : q0];
+    const int seed = nn_seed_block(keys_y, y.P, keys_x[q0 + nq / 2]);
+    NnNearest<NORM> near;
+    knn_walk(y, tiles[wave], make_float3(q4.x, q4.y, q4.z), valid, seed, -1, near);
     if (valid) {
-        const int o = __float_as_int(q4.w);  // in [0, Px): k_knn_boxes clamps the caller's permutation
-        dist[o] = best;
-        idx[o] = (unsigned)besti < (unsigned)Py ? besti : 0;  // every d NaN: nothing entered
+        const int o = knn_as_int(q4.w);  // in [0, Px): k_knn_boxes clamps the caller's permutation
+        dist[o] = near.best;
+        idx[o] = near.index(y.P);
     }
 }
 
@@ -293,5 +260,6 @@ __global__ void __launch_bounds__(GHR_NN_BLOCK) k_chamfer_bwd_y(int Px, int Py, 
     if (d_y_normals)
         for (int k = 0; k < 3; ++k) d_y_normals[(size_t)j * 3 + k] = accn[k];
 }
+#endif  // __HIPCC__
 
 }  // namespace ghr

@@ -19,7 +19,6 @@ give the same bits.
 """
 from __future__ import annotations
 
-import ctypes
 from collections import namedtuple
 from typing import Optional, Tuple
 
@@ -27,17 +26,11 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from .simple_knn import _C as _knn
+from .simple_knn._C import _ptr, _stream
 
 KNN = namedtuple("KNN", "dists idx knn")
 PAIR_CHUNK = 2 ** 26  # pairs per brute-force chunk of the comparator
-
-
-def _ptr(t: Optional[torch.Tensor]) -> ctypes.c_void_p:
-    return ctypes.c_void_p(None if t is None else t.data_ptr())
-
-
-def _stream() -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def hip_applies(*tensors: Optional[torch.Tensor]) -> bool:
@@ -94,12 +87,7 @@ def union_keys(x: torch.Tensor, y: torch.Tensor) -> Tuple[torch.Tensor, torch.Te
     xmn, xmx = torch.aminmax(x, dim=0)
     ymn, ymx = torch.aminmax(y, dim=0)
     bounds = torch.cat((torch.minimum(xmn, ymn), torch.maximum(xmx, ymx)))
-    out = []
-    for p in (x, y):
-        k = torch.empty(p.shape[0], dtype=torch.int64, device=p.device)
-        _lib.check(_lib.lib().ghr_knn_keys(_stream(), p.shape[0], _ptr(p), _ptr(bounds), _ptr(k)))
-        out.append(k)
-    return out[0], out[1]
+    return _knn.keys(x, bounds), _knn.keys(y, bounds)
 
 
 def search_hip(x: torch.Tensor, y: torch.Tensor, norm: int = 2) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -111,7 +99,7 @@ def search_hip(x: torch.Tensor, y: torch.Tensor, norm: int = 2) -> Tuple[torch.T
         if Px == 0:
             return dist, idx
         kx, ky = union_keys(x, y)
-        sx, sy = torch.sort(kx, stable=True), torch.sort(ky, stable=True)
+        sx, sy = _knn.sort_keys(kx), _knn.sort_keys(ky)
         ws = torch.empty(_lib.nn_workspace_size(Px, Py), dtype=torch.uint8, device=x.device)
         _lib.check(_lib.lib().ghr_nn_search(_stream(), Px, _ptr(x), _ptr(sx.indices), _ptr(sx.values), Py, _ptr(y), _ptr(sy.indices),
                                             _ptr(sy.values), norm, _ptr(ws), _ptr(dist), _ptr(idx)))

@@ -15,6 +15,7 @@ Kernels run on the current stream of the points' device.  There is no CPU path. 
 from __future__ import annotations
 
 import ctypes
+from typing import Optional
 
 import torch
 
@@ -24,8 +25,8 @@ except ImportError:  # imported as top-level `simple_knn._C` (reference-style sy
     from gaussianhaircut_amd import _lib
 
 
-def _ptr(t: torch.Tensor) -> ctypes.c_void_p:
-    return ctypes.c_void_p(t.data_ptr())
+def _ptr(t: Optional[torch.Tensor]) -> ctypes.c_void_p:
+    return ctypes.c_void_p(None if t is None else t.data_ptr())
 
 
 def _stream() -> ctypes.c_void_p:
@@ -47,18 +48,24 @@ def prepare(points: torch.Tensor) -> torch.Tensor:
     return points.detach().to(torch.float32).contiguous()
 
 
-def keys(pts: torch.Tensor) -> torch.Tensor:
-    """63-bit Morton codes of ``prepare``d points over their bounds (int64 [P]); they steer the search's speed only."""
-    mn, mx = torch.aminmax(pts, dim=0)
-    bounds = torch.cat((mn, mx))
+def keys(pts: torch.Tensor, bounds: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """63-bit Morton codes of ``prepare``d points (int64 [P]) over ``bounds`` (fp32 [6] on their device: min x, y, z, max x, y, z;
+    None: the points' own); they steer the search's speed only."""
+    if bounds is None:
+        bounds = torch.cat(torch.aminmax(pts, dim=0))
     k = torch.empty(pts.shape[0], dtype=torch.int64, device=pts.device)
     _lib.check(_lib.lib().ghr_knn_keys(_stream(), pts.shape[0], _ptr(pts), _ptr(bounds), _ptr(k)))
     return k
 
 
+def sort_keys(k: torch.Tensor):
+    """The stable sort of the keys: ``.values`` the sorted keys, ``.indices`` the int64 permutation."""
+    return torch.sort(k, stable=True)
+
+
 def sort_order(k: torch.Tensor) -> torch.Tensor:
     """The int64 permutation that sorts the keys."""
-    return torch.sort(k, stable=True).indices
+    return sort_keys(k).indices
 
 
 def mean_dist2(pts: torch.Tensor, order: torch.Tensor) -> torch.Tensor:

@@ -1,7 +1,7 @@
 """create_from_pcd without a GPU: ``fetch_ply`` on COLMAP-layout PLY files, ``create_from_points`` against the reference's
 own ``create_from_pcd`` (tests/golden/reference_pcd_golden.npz, made by tests/golden/make_reference_pcd_golden.py), the
 ``simple_knn`` drop-in layout, the C ABI's argument checks of the ``ghr_knn_*`` entry points and their kernels' resources.
-The kNN itself runs on the GPU only: tests/test_gpu_knn.py."""
+The kNN itself: tests/test_knn_cpu.py (a host walk of the kernels) and tests/test_gpu_knn.py."""
 import ctypes
 import os
 import subprocess
@@ -183,3 +183,8 @@ def test_knn_kernels_compile_without_scratch_or_spills():
         assert k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0 and k["sgpr_spill_count"] == 0, (sub, k)
         assert k["vgpr_count"] <= 64, (sub, k)  # eight waves per SIMD at the 256-thread workgroups they are declared for
     assert [v for k, v in meta.items() if "k_knn_search" in k][0]["group_segment_fixed_size"] <= 4096
+    nn = [v for k, v in meta.items() if "k_nn_search" in k]   # the same walk (knn_walk) in the cross-cloud search, norm 1 and 2
+    assert len(nn) == 2, [k for k in meta if "k_nn_search" in k]
+    for k in nn:
+        assert k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0 and k["sgpr_spill_count"] == 0, k
+        assert k["group_segment_fixed_size"] <= 4096, k
