@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GHR_LIB_PATH") or os.path.join(CSRC, "libghr_hip.so")  # override: kernel experiments
 SOURCES = ["ghr_capi.hip"]
 HEADERS = ["ghr_device.h", "ghr_preprocess.h", "ghr_binning.h", "ghr_render_fwd.h", "ghr_render_bwd.h", "ghr_render_bwd2.h", "ghr_render_bwd3.h",
-           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_products.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_tilelists.h", "ghr_visibility.h", "ghr_strandview.h", "ghr_sds.h", "ghr_nn.h", "ghr_compare.h"]
+           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_products.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_meshdist.h", "ghr_tilelists.h", "ghr_visibility.h", "ghr_strandview.h", "ghr_sds.h", "ghr_nn.h", "ghr_compare.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-fPIC",
                "-shared"]
 
@@ -177,6 +177,14 @@ class MeshGrid(ctypes.Structure):
                 ("bytes", ctypes.c_uint64)]
 
 
+class MeshTris(ctypes.Structure):
+    """``ghr_mesh_tris`` (include/ghr.h): the header of a closest-point triangle blob."""
+    _fields_ = [("magic", ctypes.c_uint32), ("n_faces", ctypes.c_int32), ("n_blocks", ctypes.c_int32), ("n_super", ctypes.c_int32),
+                ("lo", ctypes.c_float * 3), ("hi", ctypes.c_float * 3), ("pad_", ctypes.c_uint32 * 2),
+                ("off_rec", ctypes.c_uint64), ("off_bbox", ctypes.c_uint64), ("off_sbox", ctypes.c_uint64),
+                ("off_keys", ctypes.c_uint64), ("bytes", ctypes.c_uint64)]
+
+
 PROBE_REFERENCE, PROBE_AXIS_SCALED = 0, 1  # GHR_PROBE_*
 STRANDVIEW_KAJIYA, STRANDVIEW_TANGENT = 0, 1  # GHR_STRANDVIEW_*
 
@@ -226,6 +234,7 @@ EXPORTS = ["ghr_last_error", "ghr_abi_version", "ghr_forward_sizes", "ghr_binnin
            "ghr_latent_loss_sums_floats", "ghr_latent_loss_forward", "ghr_latent_loss_backward",
            "ghr_model_forward_segment_shared", "ghr_model_backward_segment_shared", "ghr_shared_sh_fold",
            "ghr_mesh_grid_sizes", "ghr_mesh_grid_build", "ghr_mesh_contains", "ghr_gaussian_probe_outside",
+           "ghr_mesh_tris_sizes", "ghr_mesh_tris_build", "ghr_mesh_closest", "ghr_mesh_distance_backward",
            "ghr_vis_sizes", "ghr_vis_view", "ghr_vis_head_mask",
            "ghr_strandview_sizes", "ghr_strandview_face_depth", "ghr_strandview_raster", "ghr_strandview_shade",
            "ghr_strandview_resolve", "ghr_strandview_opacity", "ghr_strandview_shade_shadowed",
@@ -329,6 +338,10 @@ def lib() -> ctypes.CDLL:
     L.ghr_mesh_grid_build.argtypes = [i32, vp, i32, vp, i32, vp, ctypes.c_size_t]
     L.ghr_mesh_contains.argtypes = [vp, ctypes.POINTER(MeshGrid), vp, ctypes.c_int64, vp, vp, vp]
     L.ghr_gaussian_probe_outside.argtypes = [vp, ctypes.POINTER(MeshGrid), vp, ctypes.c_int64, vp, vp, vp, i32, vp]
+    L.ghr_mesh_tris_sizes.argtypes = [i32, vp, i32, vp, ctypes.POINTER(MeshTris)]
+    L.ghr_mesh_tris_build.argtypes = [i32, vp, i32, vp, vp, ctypes.c_size_t]
+    L.ghr_mesh_closest.argtypes = [vp, ctypes.POINTER(MeshTris), vp, ctypes.c_int64] + [vp] * 6
+    L.ghr_mesh_distance_backward.argtypes = [vp, ctypes.c_int64] + [vp] * 6
     L.ghr_vis_sizes.argtypes = [i32, i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
     L.ghr_vis_view.argtypes = [vp, i32, vp, i32, vp, ctypes.POINTER(ctypes.c_float * 12), f32, i32, i32] + [vp] * 7
     L.ghr_vis_head_mask.argtypes = [vp, i32, i32, vp, vp, vp]

@@ -8,6 +8,9 @@
 * ``prune_strands`` / ``export_strands``  -- src/preprocessing/export_strands.py:58-79: drop the strands of which less than half
   the points lie outside the head mesh, write ``<name>_strands.pkl`` and ``<name>_strands.ply``.
 
+* ``split_strands``  -- a definition of our own in the place of the commented-out block of src/preprocessing/export_curves.py:48-101:
+  cut a strand where it enters the head mesh and re-root what follows on the scalp (``HeadMesh.closest_point``, DESIGN.md 8o);
+
 * ``cut_scalp`` / ``scalp_uv_mask`` / ``write_scalp_data``  -- src/preprocessing/extract_non_visible_head_scalp.py:177-229: cut
   the scalp mesh to the vertices the views do not see as bare head (``visibility.vertex_visibility``), write
   ``scalp_data/`` (stage 2's strand generator starts from it).
@@ -105,6 +108,58 @@ def prune_strands(points, mesh: HeadMesh, fused: bool = True):
     outside = ~mesh.contains(points, fused=fused)
     keep = 2 * outside.sum(dim=1) >= L
     return points[keep], keep
+
+
+@torch.no_grad()
+def split_strands(points, head: HeadMesh, scalp: HeadMesh = None, max_root_dist: float = 0.1, fused: bool = True):
+    """points [S, L, 3] -> (pieces [S', L, 3] float32, source [S'] int64: the strand every piece came from), on the points' device.
+
+    1. a strand of which fewer than half the points are outside ``head`` is dropped (``prune_strands``' rule);
+    2. every kept strand is cut into its maximal runs of consecutive outside points.  The run that holds point 0 stays rooted
+       where it is.  A later run is dropped when ``scalp`` is None; otherwise the scalp's closest point to the run's first point
+       (``scalp.closest_point``; every such root in ONE query) is prepended as its root when ``sqrtf(dist2) < max_root_dist``,
+       and the run is dropped when it is not;
+    3. pieces of fewer than 2 points are dropped;
+    4. a piece of n < L points is brought back to L by replacing its first segment (p0, p1) with
+       ``np.linspace(p0, p1, L - n + 2)`` (evaluated in float64, stored as float32; both ends exact), followed by ``piece[2:]``.
+       (The reference's commented-out code resamples by duplicating p1; this does not.)
+    Pieces are ordered by (strand, position along it).  Everything after the two queries is numpy on the host."""
+    assert points.dim() == 3 and points.shape[-1] == 3, points.shape
+    S, L = int(points.shape[0]), int(points.shape[1])
+    outside = (~head.contains(points, fused=fused)).cpu().numpy()
+    p = np.ascontiguousarray(points.detach().cpu().numpy(), np.float32)
+    keep = 2 * outside.sum(axis=1) >= L
+    runs = []  # (strand, first, end)
+    for s in np.nonzero(keep)[0]:
+        o = outside[s]
+        edge = np.flatnonzero(np.diff(np.concatenate(([False], o, [False])).astype(np.int8)))
+        runs += [(int(s), int(a), int(b)) for a, b in zip(edge[0::2], edge[1::2])]
+    later = [i for i, (_, a, _) in enumerate(runs) if a > 0]
+    roots = {}
+    if scalp is not None and later:
+        firsts = torch.from_numpy(np.stack([p[runs[i][0], runs[i][1]] for i in later])).to(points.device)
+        d2, _, c = scalp.closest_point(firsts, fused=fused)
+        d2, c = d2.cpu().numpy(), c.cpu().numpy()
+        for j, i in enumerate(later):
+            if np.sqrt(d2[j]) < max_root_dist:
+                roots[i] = c[j]
+    pieces, source = [], []
+    for i, (s, a, b) in enumerate(runs):
+        piece = p[s, a:b]
+        if a > 0:
+            if i not in roots:
+                continue
+            piece = np.concatenate([roots[i][None, :], piece])
+        n = len(piece)
+        if n < 2:
+            continue
+        if n < L:
+            head_seg = np.linspace(piece[0].astype(np.float64), piece[1].astype(np.float64), L - n + 2).astype(np.float32)
+            piece = np.concatenate([head_seg, piece[2:]])
+        pieces.append(piece)
+        source.append(s)
+    out = np.stack(pieces).astype(np.float32) if pieces else np.zeros((0, L, 3), np.float32)
+    return torch.from_numpy(out).to(points.device), torch.tensor(source, dtype=torch.int64, device=points.device)
 
 
 def export_strands(points, directory: str, name) -> tuple:

@@ -34,6 +34,7 @@
 #include "ghr_latent.h"
 #include "ghr_shared.h"
 #include "ghr_mesh.h"
+#include "ghr_meshdist.h"
 #include "ghr_visibility.h"
 #include "ghr_strandview.h"
 #include "ghr_sds.h"
@@ -2146,6 +2147,96 @@ int ghr_gaussian_probe_outside(void* stream, const ghr_mesh_grid* header, const 
     ghr::MeshProbeArgs a{ghr::mesh_view(*reinterpret_cast<const ghr::MeshGrid*>(header), grid_dev), P, probe, xyz, scaling, rotation,
                          outside};
     hipLaunchKernelGGL(ghr::k_gaussian_probe_outside, dim3((unsigned)blocks), dim3(GHR_MESH_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+}  // extern "C"
+
+// ---- closest point on a triangle mesh (include/ghr.h; csrc/ghr_meshdist.h) ----------------------------------------------------
+namespace {
+static_assert(sizeof(ghr_mesh_tris) == sizeof(ghr::MeshTris), "ghr_mesh_tris is ghr::MeshTris");
+
+int tris_header_check(const char* fn, const ghr_mesh_tris* h, const void* tris_dev)
+{
+    if (!h) return lt_bad(fn, "header is NULL");
+    if (h->magic != GHR_MD_MAGIC) return lt_bad(fn, "header is not a triangle-blob header (magic)");
+    if (h->n_faces < 1) return lt_bad(fn, "header.n_faces < 1");
+    if (h->n_blocks != (h->n_faces + GHR_KNN_BLOCK - 1) / GHR_KNN_BLOCK || h->n_super != (h->n_blocks + GHR_KNN_SUPER - 1) / GHR_KNN_SUPER)
+        return lt_bad(fn, "header.n_blocks / n_super do not belong to header.n_faces");
+    if (!tris_dev) return lt_bad(fn, "tris_dev is NULL");
+    if (!al16(tris_dev)) return lt_bad(fn, "tris_dev is not 16-B aligned");
+    if ((h->off_rec | h->off_bbox | h->off_sbox | h->off_keys) & 15u) return lt_bad(fn, "header offsets are not 16-B aligned");
+    if (h->off_rec + 4ull * GHR_MD_REC_WORDS * (uint64_t)h->n_faces > h->bytes || h->off_bbox + 32ull * (uint64_t)h->n_blocks > h->bytes ||
+        h->off_sbox + 32ull * (uint64_t)h->n_super > h->bytes || h->off_keys + 8ull * (uint64_t)h->n_blocks > h->bytes)
+        return lt_bad(fn, "header offsets reach past header.bytes");
+    return GHR_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int ghr_mesh_tris_sizes(int32_t n_vertices, const float* vertices, int32_t n_faces, const int32_t* faces, ghr_mesh_tris* header)
+{
+    static const char* fn = "ghr_mesh_tris_sizes: %s";
+    if (!header) return lt_bad(fn, "header is NULL");
+    if (const char* why = ghr::mesh_tris_plan(n_vertices, vertices, n_faces, faces, reinterpret_cast<ghr::MeshTris*>(header)))
+        return lt_bad(fn, why);
+    return GHR_OK;
+}
+
+int ghr_mesh_tris_build(int32_t n_vertices, const float* vertices, int32_t n_faces, const int32_t* faces, void* blob, size_t bytes)
+{
+    static const char* fn = "ghr_mesh_tris_build: %s";
+    ghr::MeshTris plan;
+    if (const char* why = ghr::mesh_tris_plan(n_vertices, vertices, n_faces, faces, &plan)) return lt_bad(fn, why);
+    if (!blob) return lt_bad(fn, "blob is NULL");
+    if (!al16(blob)) return lt_bad(fn, "blob is not 16-B aligned");
+    if ((uint64_t)bytes != plan.bytes) return lt_bad(fn, "bytes is not what ghr_mesh_tris_sizes reports for this mesh");
+    if (const char* why = ghr::mesh_tris_fill(vertices, faces, plan, blob)) return lt_bad(fn, why);
+    return GHR_OK;
+}
+
+int ghr_mesh_closest(void* stream, const ghr_mesh_tris* header, const void* tris_dev, int64_t Q, const float* points,
+                     const int64_t* order, const uint64_t* keys_sorted, float* dist2, int32_t* face, float* point)
+{
+    static const char* fn = "ghr_mesh_closest: %s";
+    if (int rc = tris_header_check(fn, header, tris_dev)) return rc;
+    if (Q < 0 || Q >= ((int64_t)1 << 31)) return lt_bad(fn, "Q must be in [0, 2^31)");
+    if (Q == 0) return GHR_OK;
+    if (!points || !order || !keys_sorted) return lt_bad(fn, "points, order or keys_sorted is NULL");
+    if (!dist2 || !face || !point) return lt_bad(fn, "dist2, face or point is NULL");
+    const int64_t waves = (Q + GHR_KNN_BLOCK - 1) / GHR_KNN_BLOCK;
+    hipStream_t s = (hipStream_t)stream;
+    ghr::MdSearchArgs a{ghr::md_view(*reinterpret_cast<const ghr::MeshTris*>(header), tris_dev), (int)Q, points, (const long long*)order,
+                        (const unsigned long long*)keys_sorted, dist2, face, point};
+    hipLaunchKernelGGL(ghr::k_meshdist_search, dim3((unsigned)((waves + GHR_MD_WAVES - 1) / GHR_MD_WAVES)), dim3(64 * GHR_MD_WAVES), 0, s, a);
+    return finish(s, 0);
+}
+
+#ifdef GHR_MD_COUNT_BLOCKS
+// measurement build only: reads {face blocks scanned, waves, faces evaluated} since the last call and zeroes them (synchronises)
+int ghr_meshdist_read_counters(uint64_t* out3)
+{
+    unsigned long long h[3] = {0, 0, 0}, z[3] = {0, 0, 0};
+    GHR_HIP(hipDeviceSynchronize());
+    GHR_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(ghr::g_md_count), sizeof(h)));
+    GHR_HIP(hipMemcpyToSymbol(HIP_SYMBOL(ghr::g_md_count), z, sizeof(z)));
+    out3[0] = h[0]; out3[1] = h[1]; out3[2] = h[2];
+    return GHR_OK;
+}
+#endif
+
+int ghr_mesh_distance_backward(void* stream, int64_t Q, const float* points, const float* closest, const float* dist2,
+                               const uint8_t* inside, const float* g, float* d_points)
+{
+    static const char* fn = "ghr_mesh_distance_backward: %s";
+    if (Q < 0 || Q >= ((int64_t)1 << 31)) return lt_bad(fn, "Q must be in [0, 2^31)");
+    if (Q == 0) return GHR_OK;
+    if (!points || !closest || !dist2 || !inside) return lt_bad(fn, "points, closest, dist2 or inside is NULL");
+    if (!g || !d_points) return lt_bad(fn, "g or d_points is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ghr::k_meshdist_bwd, dim3((unsigned)((Q + GHR_MD_BLOCK - 1) / GHR_MD_BLOCK)), dim3(GHR_MD_BLOCK), 0, s,
+                       (long long)Q, points, closest, dist2, inside, g, d_points);
     return finish(s, 0);
 }
 

@@ -8,6 +8,12 @@ operand order, brute force over all faces in chunks -- the grid changes which fa
 
 The definition of "inside" is this package's own (three axis rays with exact, complementary edge predicates, majority of the
 three parities); on a closed mesh, away from the surface, it agrees with every sound definition, pysdf's included.
+
+``closest_point`` / ``signed_distance`` (csrc/ghr_meshdist.h) add the magnitude: the closest point of the mesh, its
+squared distance and its face by a definition of our own (three clamped edge candidates and a clamped interior candidate per
+face in float32, the smallest ``d``, the lowest face index among equals), the sign from ``contains``.  The triangle blob (faces in
+Morton order, blocks of 64 with their boxes) is built on first use and kept per device.  The module-level ``signed_distance`` is
+differentiable in the points.
 """
 from __future__ import annotations
 
@@ -74,6 +80,10 @@ class HeadMesh:
         ctypes.memmove(ctypes.byref(self.header), self._blob.data_ptr(), ctypes.sizeof(self.header))
         self._dev = {}
         self._cmp = {}
+        self._tris_header = None  # the closest-point tables: built on first use
+        self._tris_blob = None
+        self._tris_dev = {}
+        self._tris_cmp = {}
 
     @classmethod
     def from_obj(cls, path: str, grid: int = 0):
@@ -183,6 +193,101 @@ class HeadMesh:
                     cross[ii, a] = crossed.sum(dim=1, dtype=torch.int32)
         return ((cross & 1).sum(dim=1) >= 2), cross
 
+
+    # ------------------------------------------------------------------ closest point (csrc/ghr_meshdist.h)
+    def tris_blob(self) -> np.ndarray:
+        """The host copy of the closest-point tables, bytes (built on first use; tests compare it with the host simulator's)."""
+        if self._tris_blob is None:
+            L = _lib.lib()
+            nv, nf = len(self.vertices), len(self.faces)
+            h = _lib.MeshTris()
+            _lib.check(L.ghr_mesh_tris_sizes(nv, self.vertices.ctypes.data, nf, self.faces.ctypes.data, ctypes.byref(h)))
+            nbytes = int(h.bytes)
+            blob = torch.empty(nbytes, dtype=torch.uint8)
+            _lib.check(L.ghr_mesh_tris_build(nv, self.vertices.ctypes.data, nf, self.faces.ctypes.data, blob.data_ptr(), nbytes))
+            ctypes.memmove(ctypes.byref(h), blob.data_ptr(), ctypes.sizeof(h))
+            self._tris_header, self._tris_blob = h, blob
+        return self._tris_blob.numpy()
+
+    def _tris_tables(self, device):
+        """(the blob, the key bounds [6]) on ``device``."""
+        key = str(device)
+        if key not in self._tris_dev:
+            self.tris_blob()
+            h = self._tris_header
+            bounds = torch.tensor(list(h.lo) + list(h.hi), dtype=torch.float32)
+            self._tris_dev[key] = (self._tris_blob.to(device), bounds.to(device))
+        return self._tris_dev[key]
+
+    def _closest_fused(self, pts):
+        if not pts.is_cuda:
+            raise RuntimeError("HeadMesh.closest_point(fused=True) needs a tensor on a ROCm device: the kernels have no CPU path "
+                               "(fused=False is the PyTorch form)")
+        from .simple_knn import _C as _knn
+        Q = pts.shape[0]
+        dist2 = torch.empty(Q, dtype=torch.float32, device=pts.device)
+        face = torch.empty(Q, dtype=torch.int32, device=pts.device)
+        point = torch.empty((Q, 3), dtype=torch.float32, device=pts.device)
+        if Q == 0:
+            return dist2, face, point
+        guard, _ptr, _stream = _launch_env(pts)
+        with guard:
+            blob, bounds = self._tris_tables(pts.device)
+            srt = _knn.sort_keys(_knn.keys(pts, bounds))
+            _lib.check(_lib.lib().ghr_mesh_closest(_stream(), ctypes.byref(self._tris_header), _ptr(blob), Q, _ptr(pts),
+                                                   _ptr(srt.indices), _ptr(srt.values), _ptr(dist2), _ptr(face), _ptr(point)))
+        return dist2, face, point
+
+    def _closest_tables(self, device):
+        """A, B, C of every face (its vertices in vertex-index order), per component, as tensors [1, F]."""
+        key = str(device)
+        if key not in self._tris_cmp:
+            fs = np.sort(self.faces, axis=1)
+            self._tris_cmp[key] = [[torch.from_numpy(np.ascontiguousarray(self.vertices[fs[:, k], c])).to(device)[None, :]
+                                    for c in range(3)] for k in range(3)]
+        return self._tris_cmp[key]
+
+    def _closest_torch(self, pts, chunk_elems: int = 1 << 20):
+        F = len(self.faces)
+        if F == 0:
+            raise ValueError("HeadMesh.closest_point: the mesh has no faces")
+        A, B, C = self._closest_tables(pts.device)
+        Q = pts.shape[0]
+        dist2 = torch.full((Q,), float("inf"), dtype=torch.float32, device=pts.device)
+        face = torch.full((Q,), -1, dtype=torch.int32, device=pts.device)
+        point = pts.clone()
+        idx = (pts.abs() <= torch.finfo(torch.float32).max).all(dim=1).nonzero(as_tuple=True)[0]  # (a NaN fails the comparison)
+        rows = max(1, chunk_elems // F)
+        ar = torch.arange(F, device=pts.device)
+        for s in range(0, int(idx.numel()), rows):
+            ii = idx[s:s + rows]
+            q = [pts[ii, c][:, None] for c in range(3)]
+            d, c = _md_face(A, B, C, q)
+            mn = d.min(dim=1, keepdim=True).values
+            w = torch.where(d == mn, ar[None, :], F).min(dim=1).values  # the lowest face index among equal d
+            dist2[ii] = d.gather(1, w[:, None])[:, 0]
+            face[ii] = w.to(torch.int32)
+            point[ii] = torch.stack([c[k].expand_as(d).gather(1, w[:, None])[:, 0] for k in range(3)], dim=1)
+        return dist2, face, point
+
+    @torch.no_grad()
+    def closest_point(self, points, fused: bool = True):
+        """points [..., 3] -> (dist2 [...] float32: the squared distance to the mesh, face [...] int32: the face that holds the
+        closest point -- the lowest index among the faces at that distance --, point [..., 3]) by the definition at the top of
+        csrc/ghr_meshdist.h.  A point with a non-finite coordinate gets (+inf, -1, itself).  ``fused=False``: the PyTorch-composed
+        comparator, brute force over all faces in chunks, the same float32 expressions in the same order (any device)."""
+        shape = tuple(points.shape[:-1])
+        assert points.shape[-1] == 3, points.shape
+        pts = points.detach().reshape(-1, 3).float().contiguous()
+        dist2, face, point = self._closest_fused(pts) if fused else self._closest_torch(pts)
+        return dist2.reshape(shape), face.reshape(shape), point.reshape(shape + (3,))
+
+    def signed_distance(self, points, fused: bool = True):
+        """[...]: ``inside ? -sqrtf(dist2) : sqrtf(dist2)`` with ``inside`` from ``contains`` -- NEGATIVE INSIDE the mesh, positive
+        outside (pysdf's SDF has the opposite sign).  +inf for a point with a non-finite coordinate.  Differentiable in the
+        points (see the module-level ``signed_distance``)."""
+        return signed_distance(points, self, fused=fused)
+
     # ------------------------------------------------------------------ public
     @torch.no_grad()
     def contains(self, points, fused: bool = True, return_crossings: bool = False):
@@ -238,3 +343,116 @@ class HeadMesh:
         if fused_contains is None:
             fused_contains = xyz.is_cuda
         return ~self.contains(pts, fused=fused_contains).any(dim=1)
+
+
+# ---- closest point: the composed candidates (the expressions of csrc/ghr_meshdist.h, operand for operand) ---------------------
+def _md_sub(a, b):
+    return (a[0] - b[0], a[1] - b[1], a[2] - b[2])
+
+
+def _md_dot(a, b):
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+
+def _md_cross(a, b):
+    return (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
+
+
+def _md_clamp(x, lo, hi):
+    t = torch.where(x > lo, x, lo)
+    return torch.where(t < hi, t, hi)
+
+
+def _md_edge(P0, P1, q):
+    e, w = _md_sub(P1, P0), _md_sub(q, P0)
+    ee, ew = _md_dot(e, e), _md_dot(e, w)
+    zero, one = torch.zeros((), dtype=ew.dtype, device=ew.device), torch.ones((), dtype=ew.dtype, device=ew.device)
+    t = torch.where(ee > 0, _md_clamp(ew / ee, zero, one), zero)
+    c = [torch.where(t == 1, P1[k], P0[k] + t * e[k]) for k in range(3)]
+    c = [_md_clamp(c[k], torch.minimum(P0[k], P1[k]), torch.maximum(P0[k], P1[k])) for k in range(3)]
+    r = _md_sub(c, q)
+    return _md_dot(r, r), c
+
+
+def _md_face(A, B, C, q):
+    """d [Q, F] and the closest point (three [Q, F]) of every (query, face) pair; A, B, C: three [1, F] each, q: three [Q, 1]."""
+    d, best = _md_edge(A, B, q)
+    for P0, P1 in ((A, C), (B, C)):
+        dk, p = _md_edge(P0, P1, q)
+        take = dk < d
+        d = torch.where(take, dk, d)
+        best = [torch.where(take, p[k], best[k]) for k in range(3)]
+    ab, ac = _md_sub(B, A), _md_sub(C, A)
+    n = _md_cross(ab, ac)
+    nn = _md_dot(n, n)
+    s0 = _md_dot(_md_cross(_md_sub(C, B), _md_sub(q, B)), n)
+    s1 = _md_dot(_md_cross(_md_sub(A, C), _md_sub(q, C)), n)
+    s2 = _md_dot(_md_cross(ab, _md_sub(q, A)), n)
+    accepted = (nn > 0) & (s0 >= 0) & (s1 >= 0) & (s2 >= 0)
+    k = torch.where(nn > 0, _md_dot(n, _md_sub(q, A)) / nn, torch.zeros((), dtype=nn.dtype, device=nn.device))
+    p = [q[i] - k * n[i] for i in range(3)]
+    p = [_md_clamp(p[i], torch.minimum(torch.minimum(A[i], B[i]), C[i]), torch.maximum(torch.maximum(A[i], B[i]), C[i]))
+         for i in range(3)]
+    r = _md_sub(p, q)
+    dk = _md_dot(r, r)
+    take = accepted & (dk < d)
+    d = torch.where(take, dk, d)
+    best = [torch.where(take, p[i], best[i]) for i in range(3)]
+    return d, best
+
+
+def _sqrt32(d):
+    """sqrtf's correctly rounded float32 root (through float64, as ``probe_points``)."""
+    return torch.sqrt(d.double()).float()
+
+
+class _SignedDistance(torch.autograd.Function):
+    """points [Q, 3] -> sd [Q].  Backward: ``t = g sign``, ``t ((q - c) / sqrtf(d))`` per component, 0 where ``d == 0`` or the point
+    was not finite -- the closest point and the sign are constants of the step (the gradient of a distance field), one thread per
+    point in HIP (``fused``) or the same expressions composed."""
+
+    @staticmethod
+    def forward(ctx, pts, mesh, fused):
+        dist2, _, closest = mesh.closest_point(pts, fused=fused)
+        inside = mesh.contains(pts, fused=fused)
+        root = _sqrt32(dist2)
+        ctx.save_for_backward(pts, closest, dist2, inside)
+        ctx.fused = fused
+        return torch.where(inside, -root, root)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        pts, closest, dist2, inside = ctx.saved_tensors
+        g = g.to(torch.float32).contiguous()
+        if ctx.fused:
+            Q = pts.shape[0]
+            d_pts = torch.empty_like(pts)
+            if Q:
+                guard, _ptr, _stream = _launch_env(pts)
+                in8 = inside.to(torch.uint8)
+                with guard:
+                    _lib.check(_lib.lib().ghr_mesh_distance_backward(_stream(), Q, _ptr(pts), _ptr(closest), _ptr(dist2), _ptr(in8),
+                                                                     _ptr(g), _ptr(d_pts)))
+            return d_pts, None, None
+        fmax = torch.finfo(torch.float32).max
+        live = (dist2 > 0) & (dist2 <= fmax) & (pts.abs() <= fmax).all(dim=1)
+        t = g * torch.where(inside, -torch.ones_like(g), torch.ones_like(g))
+        root = torch.where(live, _sqrt32(dist2), torch.ones_like(dist2))
+        d_pts = t[:, None] * ((pts - closest) / root[:, None])
+        return torch.where(live[:, None], d_pts, torch.zeros_like(d_pts)), None, None
+
+
+def signed_distance(points, mesh: HeadMesh, fused: bool = True):
+    """[...] for points [..., 3]: the signed distance to ``mesh``, ``inside ? -sqrtf(d) : sqrtf(d)`` with ``d`` from
+    ``mesh.closest_point`` and ``inside`` from ``mesh.contains`` -- NEGATIVE INSIDE (pysdf's ``SDF`` is positive inside: the
+    opposite sign).  Differentiable in ``points`` only: the gradient is ``sign (q - c) / sqrtf(d)``, the unit vector from the
+    closest point ``c``, 0 where ``d == 0`` or the point is not finite.  ``fused=True`` needs a ROCm tensor (HIP forward and
+    backward); ``fused=False`` is the PyTorch-composed comparator on any device."""
+    assert points.shape[-1] == 3, points.shape
+    if fused and not points.is_cuda:
+        raise RuntimeError("signed_distance(fused=True) needs a tensor on a ROCm device: the kernels have no CPU path "
+                           "(fused=False is the PyTorch form)")
+    shape = tuple(points.shape[:-1])
+    pts = points.reshape(-1, 3).float().contiguous()
+    return _SignedDistance.apply(pts, mesh, bool(fused)).reshape(shape)

@@ -71,6 +71,15 @@ class GaussianModelStrands(GaussianModel):
         self.use_sds = False  # the reference's constructor says True: its networks are built there; here a prior is attached
         self.prior = None
         self.Lsds = None
+        self.collision = None
+        self.Lpen = None
+
+    def attach_collision(self, collision):
+        """``collision``: a callable ``pts [S, L, 3] -> Lpen`` (``strand_collision.HeadCollision``).  From now on
+        ``initialize_gaussians_hair()`` sets ``self.Lpen`` from the polyline points; ``None`` detaches.  Off by default."""
+        self.collision = collision
+        self.Lpen = None
+        return self
 
     def attach_prior(self, prior):
         """``prior``: a callable ``dirs -> Lsds`` (``strand_prior.StrandPrior``).  From now on ``initialize_gaussians_hair()`` sets
@@ -94,13 +103,17 @@ class GaussianModelStrands(GaussianModel):
         self.initialize_gaussians_hair()
         return self
 
-    def initialize_gaussians_hair(self, prior: bool = True):
+    def initialize_gaussians_hair(self, prior: bool = True, collision: bool = True):
         """gaussian_model_strands.py:435-515.  On a ROCm device one HIP kernel each way (``ghr_strand_build``, csrc/ghr_strands.h)
         instead of ~55 PyTorch kernels per iteration; the polyline points ``_pts`` are then made on first use.  With a prior
         attached (``attach_prior``) and ``prior`` true, ``self.Lsds`` is computed from the strand directions (:456-515);
-        ``prior=False`` rebuilds the Gaussians only (a step's further views) and leaves ``Lsds`` as it is."""
+        ``prior=False`` rebuilds the Gaussians only (a step's further views) and leaves ``Lsds`` as it is.  Likewise ``self.Lpen``
+        with a collision term attached (``attach_collision``), unless ``collision`` is false (a step whose weight for it is 0)."""
         if getattr(self, "use_sds", False) and prior:
             self.Lsds = self.prior(self._dirs)
+        if getattr(self, "collision", None) is not None and prior and collision:
+            self.__dict__.pop("_pts_value", None)  # the points of the CURRENT directions
+            self.Lpen = self.collision(self._pts)
         self._dir = self._dirs.reshape(-1, 3)
         if FUSED_STRAND_BUILD and _strand_build_applies(self.pts_origins, self._dirs):
             self.__dict__.pop("_pts_value", None)

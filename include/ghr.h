@@ -816,6 +816,38 @@ int ghr_mesh_contains(void* stream, const ghr_mesh_grid* header, const void* gri
 int ghr_gaussian_probe_outside(void* stream, const ghr_mesh_grid* header, const void* grid_dev, int64_t P, const float* xyz,
                                const float* scaling, const float* rotation, int32_t probe, uint8_t* outside);
 
+/* ---- closest point on and signed distance to a triangle mesh (csrc/ghr_meshdist.h)
+ * Added without an ABI_VERSION bump: four new functions and one new struct, no existing struct or signature changed.
+ * The definition of the closest point, of dist2 and of the winning face is the one at the top of csrc/ghr_meshdist.h: three
+ * clamped edge candidates and a clamped interior candidate per face in float32, the smallest d, the lowest face index among
+ * equals.  ghr_mesh_tris_sizes / ghr_mesh_tris_build run on the HOST (plain C++, deterministic): vertices [V][3] with
+ * |coordinate| <= 2^30, faces [F][3] indices into them, F >= 1.  _sizes validates the mesh and fills *header, whose `bytes` is
+ * the size of the blob; _build fills `blob` (host memory, 16-B aligned, `bytes` long), which starts with the header.  The
+ * caller copies the blob to the device as it is.
+ * ghr_mesh_closest: points [Q][3], Q < 2^31; order [Q] the permutation that sorts the 63-bit keys of the points
+ * (ghr_knn_keys over the bounds header.lo, header.hi), keys_sorted [Q] those keys sorted.  dist2 [Q], face [Q], point [Q][3]
+ * are written at the queries' original indices; a query with a non-finite coordinate gets +inf, -1 and itself.
+ * ghr_mesh_distance_backward: the gradient of sd = (inside ? -1 : 1) sqrtf(dist2) to the points: closest [Q][3], dist2 [Q],
+ * inside [Q] bytes (ghr_mesh_contains'), g [Q] the upstream gradient -> d_points [Q][3] = (g sign) ((q - c) / sqrtf(dist2)),
+ * 0 where dist2 == 0 or the query was not finite.
+ * `header` is the HOST copy of the blob's header, `tris_dev` the blob on the device.  Q == 0 is GHR_OK and launches nothing.
+ * A refused call launches nothing and ghr_last_error() says why. */
+typedef struct ghr_mesh_tris {
+    uint32_t magic;
+    int32_t n_faces, n_blocks, n_super;
+    float lo[3], hi[3];      /* box of the vertices that faces use: the bounds of the keys */
+    uint32_t pad_[2];
+    uint64_t off_rec, off_bbox, off_sbox, off_keys;  /* byte offsets into the blob */
+    uint64_t bytes;
+} ghr_mesh_tris;
+int ghr_mesh_tris_sizes(int32_t n_vertices, const float* vertices, int32_t n_faces, const int32_t* faces, ghr_mesh_tris* header);
+int ghr_mesh_tris_build(int32_t n_vertices, const float* vertices, int32_t n_faces, const int32_t* faces, void* blob,
+                        size_t bytes);
+int ghr_mesh_closest(void* stream, const ghr_mesh_tris* header, const void* tris_dev, int64_t Q, const float* points,
+                     const int64_t* order, const uint64_t* keys_sorted, float* dist2, int32_t* face, float* point);
+int ghr_mesh_distance_backward(void* stream, int64_t Q, const float* points, const float* closest, const float* dist2,
+                               const uint8_t* inside, const float* g, float* d_points);
+
 /* ---- head-mesh visibility: a triangle rasterizer and the per-vertex view counts (csrc/ghr_visibility.h)
  * Added without an ABI_VERSION bump: three new functions, no existing struct or signature changed.
  * The definition of pix_to_face, of the head mask and of "seen" is the one at the top of csrc/ghr_visibility.h: pixel centres

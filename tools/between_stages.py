@@ -6,6 +6,9 @@
         M/point_cloud_cropped/iteration_N/raw_point_cloud.ply -> M/point_cloud_filtered/iteration_N/point_cloud.ply (+ raw_)
     python tools/between_stages.py export --points P.npy|P.pkl --mesh HEAD.obj --out_dir DIR [--iter 30000]
         strand points [S, L, 3] -> DIR/N_strands.pkl, DIR/N_strands.ply
+    python tools/between_stages.py split  --points P.npy|P.pkl --mesh HEAD.obj --out_dir DIR [--scalp SCALP.obj] [--max_root_dist 0.1]
+        strand points [S, L, 3] -> DIR/N_strands.pkl, DIR/N_strands.ply: strands cut where they enter the head, the pieces after a
+        cut re-rooted on the scalp mesh when it is given and nearer than --max_root_dist (dropped otherwise)
     python tools/between_stages.py scalp  --mesh HEAD.obj --cams CAMS.pkl --path_to_data D --out_dir FLAME_DIR
                                           --scalp_idx I --scalp_faces F --scalp_uvs UV [--seam_pairs SEAMS.json]
         D/masks_2/{body,hair}/<view>.png -> FLAME_DIR/scalp_data/{scalp.obj, cut_scalp_verts.pickle, dif_mask.png, vis/<view>.jpg}
@@ -77,7 +80,7 @@ def _scalp(a, fused, dev):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("step", choices=["crop", "filter", "export", "scalp"])
+    ap.add_argument("step", choices=["crop", "filter", "export", "split", "scalp"])
     ap.add_argument("--model_path")
     ap.add_argument("--path_to_data")
     ap.add_argument("--mesh")
@@ -93,6 +96,8 @@ def main(argv=None):
     ap.add_argument("--scalp_faces")
     ap.add_argument("--scalp_uvs")
     ap.add_argument("--seam_pairs")
+    ap.add_argument("--scalp")
+    ap.add_argument("--max_root_dist", type=float, default=0.1)
     ap.add_argument("--prob_thr", type=float, default=0.5)
     ap.add_argument("--n_views_thr", type=float, default=0.1)
     a = ap.parse_args(argv)
@@ -113,6 +118,12 @@ def main(argv=None):
         keep = bs.filter_head_intersections(m, HeadMesh.from_obj(a.mesh), probe=a.probe, fused=fused)
         m.save_ply(os.path.join(a.model_path, "point_cloud_filtered", it, "point_cloud.ply"))
         print("filter: kept %d of %d Gaussians" % (int(keep.sum()), keep.numel()))
+    elif a.step == "split":
+        p = torch.from_numpy(np.ascontiguousarray(_load_array(a.points), np.float32)).to(dev)
+        pieces, source = bs.split_strands(p, HeadMesh.from_obj(a.mesh), HeadMesh.from_obj(a.scalp) if a.scalp else None,
+                                          max_root_dist=a.max_root_dist, fused=fused)
+        print("split: %d strands -> %d pieces of %d strands" % (p.shape[0], pieces.shape[0], int(torch.unique(source).numel())))
+        print("export: %s %s" % bs.export_strands(pieces, a.out_dir, a.iter))
     else:
         if a.points.endswith(".npy"):
             p = np.load(a.points)
