@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GHR_LIB_PATH") or os.path.join(CSRC, "libghr_hip.so")  # override: kernel experiments
 SOURCES = ["ghr_capi.hip"]
 HEADERS = ["ghr_device.h", "ghr_preprocess.h", "ghr_binning.h", "ghr_render_fwd.h", "ghr_render_bwd.h", "ghr_render_bwd2.h", "ghr_render_bwd3.h",
-           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_products.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_meshdist.h", "ghr_tilelists.h", "ghr_visibility.h", "ghr_strandview.h", "ghr_sds.h", "ghr_nn.h", "ghr_compare.h"]
+           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_products.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_meshdist.h", "ghr_tilelists.h", "ghr_visibility.h", "ghr_strandview.h", "ghr_sds.h", "ghr_nn.h", "ghr_compare.h", "ghr_texstrands.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-fPIC",
                "-shared"]
 
@@ -240,7 +240,8 @@ EXPORTS = ["ghr_last_error", "ghr_abi_version", "ghr_forward_sizes", "ghr_binnin
            "ghr_strandview_resolve", "ghr_strandview_opacity", "ghr_strandview_shade_shadowed",
            "ghr_sds_local", "ghr_sds_local_backward", "ghr_sds_texture", "ghr_sds_texture_backward",
            "ghr_nn_workspace_size", "ghr_nn_search", "ghr_chamfer_point", "ghr_chamfer_point_backward",
-           "ghr_cmp_over_white", "ghr_cmp_strip"]
+           "ghr_cmp_over_white", "ghr_cmp_strip",
+           "ghr_ts_fetch", "ghr_ts_fetch_backward", "ghr_ts_world", "ghr_ts_world_backward"]
 
 _lib = None
 
@@ -365,6 +366,10 @@ def lib() -> ctypes.CDLL:
     L.ghr_chamfer_point_backward.argtypes = [vp, ctypes.c_int64, ctypes.c_int64, i32] + [vp] * 8 + [i32] + [vp] * 5
     L.ghr_cmp_over_white.argtypes = [vp, ctypes.c_int64, vp, vp]
     L.ghr_cmp_strip.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
+    L.ghr_ts_fetch.argtypes = [vp, i32, i32, i32, i32] + [vp] * 7
+    L.ghr_ts_fetch_backward.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.ghr_ts_world.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, f32, vp, vp]
+    L.ghr_ts_world_backward.argtypes = [vp, i32, i32, i32, vp, vp, f32, vp, vp, vp]
     L.ghr_ws_inspect.argtypes = [i32, i32, i32, i32, u32, vp, vp, vp, ctypes.POINTER(WsView)]
     for name in EXPORTS:
         fn = getattr(L, name)

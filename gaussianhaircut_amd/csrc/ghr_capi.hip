@@ -38,6 +38,7 @@
 #include "ghr_visibility.h"
 #include "ghr_strandview.h"
 #include "ghr_sds.h"
+#include "ghr_texstrands.h"
 
 namespace {
 
@@ -2671,6 +2672,103 @@ int ghr_sds_texture_backward(void* stream, int32_t N, int32_t n, int32_t C, int3
     hipLaunchKernelGGL(ghr::k_sds_bwd_texel, dim3(sds_blocks(GG)), dim3(GHR_SDS_BLOCK), 0, s, a);
     hipLaunchKernelGGL(ghr::k_sds_bwd_gather, dim3(sds_blocks(N)), dim3(GHR_SDS_BLOCK), 0, s, a);
     if (d_v) hipLaunchKernelGGL(ghr::k_sds_bwd_v, dim3(sds_blocks(N)), dim3(GHR_SDS_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+}  // extern "C"
+
+// ---- the textured strand generator between its networks: texture fetch, local frames (include/ghr.h; csrc/ghr_texstrands.h) ----
+namespace {
+inline unsigned ts_blocks(int64_t waves) { return (unsigned)((waves + GHR_TS_BLOCK / GHR_TS_WAVE - 1) / (GHR_TS_BLOCK / GHR_TS_WAVE)); }
+
+// the sizes every entry shares, before anything touches the runtime; a size of -1 is not checked by that entry
+const char* ts_sizes(int64_t Smax, int64_t S, int64_t T, int64_t C, int64_t n)
+{
+    if (S < 1) return "S < 1";
+    if (S > Smax) return "S > Smax";
+    if (T != -1 && T < 1) return "T < 1";
+    if (C != -1 && C < 1) return "C < 1";
+    if (n != -1 && n < 1) return "n < 1";
+    if (Smax > (1 << 28) || T > 16384 || (T > 0 && C * T * T >= (1ll << 31)) || (C > 0 && S * C >= (1ll << 31)) ||
+        (n > 0 && S * (n + 1) * 3 >= (1ll << 31)))
+        return "sizes exceed the kernels' 32-bit indexing";
+    return nullptr;
+}
+}  // namespace
+
+extern "C" {
+
+int ghr_ts_fetch(void* stream, int32_t Smax, int32_t S, int32_t T, int32_t C, const float* texture, const int32_t* x0,
+                 const int32_t* y0, const float* fx, const float* fy, const int64_t* idx, float* z)
+{
+    static const char* fn = "ghr_ts_fetch: %s";
+    if (const char* why = ts_sizes(Smax, S, T, C, -1)) return lt_bad(fn, why);
+    if (!texture) return lt_bad(fn, "texture is NULL");
+    if (!x0 || !y0 || !fx || !fy) return lt_bad(fn, "a tap buffer is NULL");
+    if (!idx) return lt_bad(fn, "idx is NULL");
+    if (!z) return lt_bad(fn, "z is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::TsFetchArgs a{};
+    a.Smax = Smax; a.S = S; a.T = T; a.C = C; a.texture = texture; a.x0 = x0; a.y0 = y0; a.fx = fx; a.fy = fy; a.idx = idx; a.z = z;
+    hipLaunchKernelGGL(ghr::k_ts_fetch, dim3(ts_blocks(S)), dim3(GHR_TS_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+int ghr_ts_fetch_backward(void* stream, int32_t Smax, int32_t S, int32_t T, int32_t C, const float* fx, const float* fy,
+                          const int32_t* start, const int32_t* list, int32_t list_len, const int64_t* idx, const float* d_z,
+                          int32_t* pos, float* d_texture)
+{
+    static const char* fn = "ghr_ts_fetch_backward: %s";
+    if (const char* why = ts_sizes(Smax, S, T, C, -1)) return lt_bad(fn, why);
+    if (list_len < 0 || (int64_t)list_len > 4ll * Smax) return lt_bad(fn, "list_len outside 0 .. 4 Smax");
+    if (!fx || !fy) return lt_bad(fn, "a tap buffer is NULL");
+    if (!start || (!list && list_len > 0)) return lt_bad(fn, "start or list is NULL");
+    if (!idx) return lt_bad(fn, "idx is NULL");
+    if (!d_z) return lt_bad(fn, "d_z is NULL");
+    if (!pos) return lt_bad(fn, "pos is NULL");
+    if (!d_texture) return lt_bad(fn, "d_texture is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::TsFetchArgs a{};
+    a.Smax = Smax; a.S = S; a.T = T; a.C = C; a.list_len = list_len; a.fx = fx; a.fy = fy; a.start = start; a.list = list;
+    a.idx = idx; a.d_z = d_z; a.pos = pos; a.d_texture = d_texture;
+    const int64_t TT = (int64_t)T * T;
+    GHR_HIP(hipMemsetAsync(pos, 0xff, sizeof(int32_t) * (size_t)Smax, s));  // -1: not in this draw
+    hipLaunchKernelGGL(ghr::k_ts_positions, dim3((unsigned)((S + GHR_TS_BLOCK - 1) / GHR_TS_BLOCK)), dim3(GHR_TS_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_ts_texgrad, dim3((unsigned)((TT + GHR_TS_TEXELS - 1) / GHR_TS_TEXELS)), dim3(GHR_TS_GRAD_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+int ghr_ts_world(void* stream, int32_t Smax, int32_t S, int32_t n, const float* v, const float* local2world, const float* origins,
+                 const int64_t* idx, float inv_scale, float* p, float* p_local)
+{
+    static const char* fn = "ghr_ts_world: %s";
+    if (const char* why = ts_sizes(Smax, S, -1, -1, n)) return lt_bad(fn, why);
+    if (!v) return lt_bad(fn, "v is NULL");
+    if (!local2world || !origins) return lt_bad(fn, "local2world or origins is NULL");
+    if (!idx) return lt_bad(fn, "idx is NULL");
+    if (!p) return lt_bad(fn, "p is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::TsWorldArgs a{};
+    a.Smax = Smax; a.S = S; a.n = n; a.inv_scale = inv_scale; a.v = v; a.frames = local2world; a.origins = origins; a.idx = idx;
+    a.p = p; a.p_local = p_local;
+    hipLaunchKernelGGL(ghr::k_ts_world, dim3(ts_blocks(S)), dim3(GHR_TS_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+int ghr_ts_world_backward(void* stream, int32_t Smax, int32_t S, int32_t n, const float* local2world, const int64_t* idx,
+                          float inv_scale, const float* d_p, const float* d_p_local, float* d_v)
+{
+    static const char* fn = "ghr_ts_world_backward: %s";
+    if (const char* why = ts_sizes(Smax, S, -1, -1, n)) return lt_bad(fn, why);
+    if (!local2world) return lt_bad(fn, "local2world is NULL");
+    if (!idx) return lt_bad(fn, "idx is NULL");
+    if (!d_p && !d_p_local) return lt_bad(fn, "d_p and d_p_local are both NULL");
+    if (!d_v) return lt_bad(fn, "d_v is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::TsWorldArgs a{};
+    a.Smax = Smax; a.S = S; a.n = n; a.inv_scale = inv_scale; a.frames = local2world; a.idx = idx; a.d_p = d_p; a.d_pl = d_p_local;
+    a.d_v = d_v;
+    hipLaunchKernelGGL(ghr::k_ts_world_bwd, dim3(ts_blocks(S)), dim3(GHR_TS_BLOCK), 0, s, a);
     return finish(s, 0);
 }
 

@@ -3,7 +3,8 @@
 ``GaussianModelCurves`` is the class of ``gaussian_model_strands.py``).
 
 The Gaussian side of the latent-strand stage.  The strand prior that decodes a latent texture into polylines is out of scope
-(DESIGN 8): here it is any callable ``generator(iteration) -> dict``.  What the reference does with the generator's
+(DESIGN 8): here it is any callable ``generator(iteration) -> dict`` (``strand_generator.TexturedStrands`` is one, with
+the networks left to the caller: DESIGN 8p).  What the reference does with the generator's
 output at the top of every iteration (:451-499) is in scope and fused (csrc/ghr_latent.h):
   * points ``p [S, L, 3]`` -> ``_xyz / _rotation / _scaling / _dir`` of the ``S (L - 1)`` segment Gaussians, one kernel each way;
   * per-strand appearance ``repeat``-ed over the segments, one kernel each way (the backward sums a strand's rows in order).

@@ -2,7 +2,8 @@
 ``src/scene/gaussian_model_strands.py`` (:230-452).  Each strand is a polyline of ``n_seg`` direction vectors; every
 segment becomes one Gaussian (mid-point, longest axis = half the segment length along the segment, parallel-transport
 quaternion; ``initialize_gaussians_hair`` :435-452).  The learned strand *generators* of the reference depend on the
-un-vendored NeuralHaircut checkpoints and are out of scope; strands here are explicit tensors.
+un-vendored NeuralHaircut checkpoints and are out of scope; strands here are explicit tensors, made by hand
+(``create_from_strands``) or out of ``strand_generator.TexturedStrands`` (``create_from_generator``).
 """
 from __future__ import annotations
 
@@ -102,6 +103,27 @@ class GaussianModelStrands(GaussianModel):
                                           else torch.zeros(P, 1, device=dev)).float().requires_grad_(True))
         self.initialize_gaussians_hair()
         return self
+
+    def create_from_generator(self, generator, num_strands: int, spatial_lr_scale: float = 1.0):
+        """The reference's ``create_from_pcd`` (gaussian_model_strands.py:537-574) without its checkpoint loading: ``num_strands``
+        strands out of ``generator.forward_inference`` (``strand_generator.TexturedStrands``) become the explicit parameters of
+        this model -- origins ``pts[:, :1]``, directions ``diff(pts)``, SH features and orientation confidence from the
+        generator's colour decoder, one row per strand repeated over its segments (:465-467).  ``uvs``, ``local2world``,
+        ``z_geom`` and ``p_local`` stay on the model: they are what ``StrandPrior`` is built from."""
+        dec = getattr(generator, "color_decoder", None)
+        if dec is None:
+            raise ValueError("create_from_generator needs a generator with a colour decoder")
+        with torch.no_grad():
+            pts, uvs, local2world, p_local, z_geom, z = generator.forward_inference(num_strands)
+            K = (self.max_sh_degree + 1) ** 2
+            dc, rest, conf = dec(z[:, 1:]).split([3, 3 * (K - 1), 1], dim=-1)
+            S, n_seg = int(pts.shape[0]), int(pts.shape[1]) - 1
+            features = torch.cat([dc, rest], dim=-1).view(S, 1, K, 3).repeat(1, n_seg, 1, 1).reshape(S * n_seg, K, 3)
+            conf = conf.view(S, 1, 1).repeat(1, n_seg, 1).reshape(S * n_seg, 1)
+            self.uvs, self.local2world, self.z_geom, self.p_local = uvs, local2world, z_geom, p_local
+            self.num_strands, self.strand_length = S, n_seg + 1
+            origins, dirs = pts[:, :1], pts[:, 1:] - pts[:, :-1]
+        return self.create_from_strands(origins, dirs, features, conf, spatial_lr_scale)
 
     def initialize_gaussians_hair(self, prior: bool = True, collision: bool = True):
         """gaussian_model_strands.py:435-515.  On a ROCm device one HIP kernel each way (``ghr_strand_build``, csrc/ghr_strands.h)

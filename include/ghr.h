@@ -1011,6 +1011,36 @@ int ghr_cmp_over_white(void* stream, int64_t n_pixels, const uint8_t* rgba, uint
 int ghr_cmp_strip(void* stream, int32_t w, int32_t h, const uint8_t* gt, const uint8_t* preview, int32_t pw, int32_t ph,
                   int32_t pad_left, int32_t pad_top, int32_t crop_left, int32_t crop_top, const uint8_t* render, uint8_t* out);
 
+/* ---- the textured strand generator between its networks (csrc/ghr_texstrands.h)
+ * Smax roots on the scalp with, per root r, the bilinear taps of its UV in a T x T texture made once on the host in float64:
+ * x0, y0 [Smax] int32 and fx, fy [Smax] float32.  Tap k = 0..3 is texel (x0 + (k & 1), y0 + (k >> 1)) with weight (1-fx)(1-fy),
+ * fx(1-fy), (1-fx)fy, fx fy; a tap outside 0..T-1 is dropped (padding "zeros"), an in-range tap with weight 0 stays a tap.
+ * idx [S] int64 is this call's draw of S <= Smax roots, none twice.  float32, no contraction, the operand order written.
+ *
+ * ghr_ts_fetch: z [S][C], z[s][c] = ((w0 t0 + w1 t1) + w2 t2) + w3 t3 with t_k = texture[c][y_k][x_k] of root idx[s], the dropped
+ *   taps skipped (none left: 0).  texture is [C][T][T].  An idx outside 0..Smax-1 reads nothing and makes its row NaN.
+ * ghr_ts_fetch_backward: d_texture [C][T][T], EVERY element assigned (no zero fill by the caller):
+ *   d_texture[c][q] = sum, in list order, over list[start[q] .. start[q + 1]) of w_k d_z[pos[r]][c], entry = 4 r + k, skipping
+ *   roots with pos[r] = -1.  start [T T + 1] and list [list_len <= 4 Smax] are the static inverted lists: for texel q = y T + x the
+ *   (root, tap) pairs that touch it, ascending.  pos [Smax] int32 is scratch the call fills: -1, then pos[idx[s]] = s.  No
+ *   floating-point atomics: two calls, or a permuted idx with d_z permuted to match, give the same bits.
+ * ghr_ts_world: v [S][n][3] decoded local segments -> p [S][n + 1][3] world points and (p_local may be NULL) the local ones:
+ *   p_local[s][j] = (sum_{i < j} v[s][i]) inv_scale, p[s][j] = origins[idx[s]] + M p_local[s][j], M = local2world[idx[s]] row-major,
+ *   the product bracketed ((M0 x + M1 y) + M2 z); the sum in the chunked scan order of ghr_sds_local.
+ * ghr_ts_world_backward: d_v[s][i] = (M^T sum_{j > i} d_p[s][j] + sum_{j > i} d_p_local[s][j]) inv_scale; either cotangent may be
+ *   NULL, not both.
+ * All refuse, with GHR_E_INVALID and a ghr_last_error() text before the runtime is touched: a NULL pointer, S < 1, S > Smax,
+ * T < 1, C < 1, n < 1, list_len outside 0 .. 4 Smax, sizes beyond 32-bit indexing. */
+int ghr_ts_fetch(void* stream, int32_t Smax, int32_t S, int32_t T, int32_t C, const float* texture, const int32_t* x0,
+                 const int32_t* y0, const float* fx, const float* fy, const int64_t* idx, float* z);
+int ghr_ts_fetch_backward(void* stream, int32_t Smax, int32_t S, int32_t T, int32_t C, const float* fx, const float* fy,
+                          const int32_t* start, const int32_t* list, int32_t list_len, const int64_t* idx, const float* d_z,
+                          int32_t* pos, float* d_texture);
+int ghr_ts_world(void* stream, int32_t Smax, int32_t S, int32_t n, const float* v, const float* local2world, const float* origins,
+                 const int64_t* idx, float inv_scale, float* p, float* p_local);
+int ghr_ts_world_backward(void* stream, int32_t Smax, int32_t S, int32_t n, const float* local2world, const int64_t* idx,
+                          float inv_scale, const float* d_p, const float* d_p_local, float* d_v);
+
 /* Introspection for tests (device pointers into the workspaces; layout is otherwise private). */
 typedef struct ghr_ws_view {
     const float* rec;          /* [P][16]: x, y, conic a, b, c, opacity, features[10] */
