@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GHR_LIB_PATH") or os.path.join(CSRC, "libghr_hip.so")  # override: kernel experiments
 SOURCES = ["ghr_capi.hip"]
 HEADERS = ["ghr_device.h", "ghr_preprocess.h", "ghr_binning.h", "ghr_render_fwd.h", "ghr_render_bwd.h", "ghr_render_bwd2.h", "ghr_render_bwd3.h",
-           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_products.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_meshdist.h", "ghr_tilelists.h", "ghr_visibility.h", "ghr_strandview.h", "ghr_sds.h", "ghr_nn.h", "ghr_compare.h", "ghr_texstrands.h"]
+           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_products.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_meshdist.h", "ghr_tilelists.h", "ghr_visibility.h", "ghr_strandview.h", "ghr_sds.h", "ghr_nn.h", "ghr_compare.h", "ghr_texstrands.h", "ghr_guides.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-fPIC",
                "-shared"]
 
@@ -241,7 +241,8 @@ EXPORTS = ["ghr_last_error", "ghr_abi_version", "ghr_forward_sizes", "ghr_binnin
            "ghr_sds_local", "ghr_sds_local_backward", "ghr_sds_texture", "ghr_sds_texture_backward",
            "ghr_nn_workspace_size", "ghr_nn_search", "ghr_chamfer_point", "ghr_chamfer_point_backward",
            "ghr_cmp_over_white", "ghr_cmp_strip",
-           "ghr_ts_fetch", "ghr_ts_fetch_backward", "ghr_ts_world", "ghr_ts_world_backward"]
+           "ghr_ts_fetch", "ghr_ts_fetch_backward", "ghr_ts_world", "ghr_ts_world_backward",
+           "ghr_guides_blend", "ghr_guides_blend_backward"]
 
 _lib = None
 
@@ -370,6 +371,8 @@ def lib() -> ctypes.CDLL:
     L.ghr_ts_fetch_backward.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     L.ghr_ts_world.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, f32, vp, vp]
     L.ghr_ts_world_backward.argtypes = [vp, i32, i32, i32, vp, vp, f32, vp, vp, vp]
+    L.ghr_guides_blend.argtypes = [vp, i32, i32, i32, i32] + [vp] * 13
+    L.ghr_guides_blend_backward.argtypes = [vp, i32, i32, i32, i32] + [vp] * 13
     L.ghr_ws_inspect.argtypes = [i32, i32, i32, i32, u32, vp, vp, vp, ctypes.POINTER(WsView)]
     for name in EXPORTS:
         fn = getattr(L, name)

@@ -39,6 +39,7 @@
 #include "ghr_strandview.h"
 #include "ghr_sds.h"
 #include "ghr_texstrands.h"
+#include "ghr_guides.h"
 
 namespace {
 
@@ -2769,6 +2770,72 @@ int ghr_ts_world_backward(void* stream, int32_t Smax, int32_t S, int32_t n, cons
     a.Smax = Smax; a.S = S; a.n = n; a.inv_scale = inv_scale; a.frames = local2world; a.idx = idx; a.d_p = d_p; a.d_pl = d_p_local;
     a.d_v = d_v;
     hipLaunchKernelGGL(ghr::k_ts_world_bwd, dim3(ts_blocks(S)), dim3(GHR_TS_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+}  // extern "C"
+
+// ---- guiding strands of the textured generator: neighbours, lists, the HAAR blend (include/ghr.h; csrc/ghr_guides.h) ----------
+namespace {
+inline unsigned gd_blocks(int64_t waves) { return (unsigned)((waves + GHR_GD_BLOCK / GHR_SDS_WAVE - 1) / (GHR_GD_BLOCK / GHR_SDS_WAVE)); }
+
+// the sizes both entries share, before anything touches the runtime
+const char* gd_sizes(int64_t S, int64_t N, int64_t n, int64_t C)
+{
+    if (N < GHR_SDS_K) return "N < 4: a strand needs four guides";
+    if (S < N) return "S < N: the guides are the first N of the S drawn roots";
+    if (n < 1) return "n < 1";
+    if (C < 1) return "C < 1";
+    if (S > (1 << 28) || S * C >= (1ll << 31) || N * n * 3 >= (1ll << 31)) return "sizes exceed the kernels' 32-bit indexing";
+    return nullptr;
+}
+}  // namespace
+
+extern "C" {
+
+int ghr_guides_blend(void* stream, int32_t S, int32_t N, int32_t n, int32_t C, const float* uvs, const float* z_g, const float* v_g,
+                     int32_t* nbr, float* w, float* csim, float* alpha, float* alpha_s, int32_t* count, int32_t* start,
+                     int32_t* unsorted, int32_t* list, float* z)
+{
+    static const char* fn = "ghr_guides_blend: %s";
+    if (const char* why = gd_sizes(S, N, n, C)) return lt_bad(fn, why);
+    if (!uvs || !z_g || !v_g) return lt_bad(fn, "uvs, z_g or v_g is NULL");
+    if (!nbr || !w || !csim || !alpha || !alpha_s || !count || !start || !unsorted || !list) return lt_bad(fn, "a saved-state buffer is NULL");
+    if (!z) return lt_bad(fn, "z is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::GdArgs a{};
+    a.S = S; a.N = N; a.n = n; a.C = C; a.uvs = uvs; a.z_g = z_g; a.v_g = v_g;
+    a.nbr = nbr; a.w = w; a.csim = csim; a.alpha = alpha; a.alpha_s = alpha_s; a.count = count; a.start = start;
+    a.unsorted = unsorted; a.list = list; a.z = z;
+    GHR_HIP(hipMemsetAsync(count, 0, sizeof(int32_t) * (size_t)N, s));
+    hipLaunchKernelGGL(ghr::k_gd_knn, dim3(gd_blocks(S)), dim3(GHR_GD_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_gd_blend, dim3(gd_blocks(S)), dim3(GHR_GD_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_gd_start, dim3(1), dim3(GHR_SDS_WAVE), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_gd_fill, dim3((unsigned)((4ll * S + GHR_GD_BLOCK - 1) / GHR_GD_BLOCK)), dim3(GHR_GD_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_gd_lists, dim3(gd_blocks(N)), dim3(GHR_GD_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+int ghr_guides_blend_backward(void* stream, int32_t S, int32_t N, int32_t n, int32_t C, const float* z_g, const float* v_g,
+                              const int32_t* nbr, const float* w, const float* csim, const float* alpha_s, const int32_t* start,
+                              const int32_t* list, const float* d_z, float* dalpha_s, float* d_csim, float* d_zg, float* d_vg)
+{
+    static const char* fn = "ghr_guides_blend_backward: %s";
+    if (const char* why = gd_sizes(S, N, n, C)) return lt_bad(fn, why);
+    if (!z_g || !v_g) return lt_bad(fn, "z_g or v_g is NULL");
+    if (!nbr || !w || !csim || !alpha_s || !start || !list) return lt_bad(fn, "a saved-state buffer is NULL");
+    if (!d_z) return lt_bad(fn, "d_z is NULL");
+    if (!dalpha_s || !d_csim) return lt_bad(fn, "dalpha_s or d_csim is NULL");
+    if (!d_zg) return lt_bad(fn, "d_zg is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    ghr::GdArgs a{};
+    a.S = S; a.N = N; a.n = n; a.C = C; a.z_g = z_g; a.v_g = v_g;
+    a.nbr = const_cast<int32_t*>(nbr); a.w = const_cast<float*>(w); a.csim = const_cast<float*>(csim);
+    a.alpha_s = const_cast<float*>(alpha_s); a.start = const_cast<int32_t*>(start); a.list = const_cast<int32_t*>(list);
+    a.d_z = d_z; a.dalpha_s = dalpha_s; a.d_csim = d_csim; a.d_zg = d_zg; a.d_vg = d_vg;
+    hipLaunchKernelGGL(ghr::k_gd_dalpha, dim3(gd_blocks(S)), dim3(GHR_GD_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_gd_gather, dim3(gd_blocks(N)), dim3(GHR_GD_BLOCK), 0, s, a);
+    if (d_vg) hipLaunchKernelGGL(ghr::k_gd_bwd_v, dim3(gd_blocks(N)), dim3(GHR_GD_BLOCK), 0, s, a);
     return finish(s, 0);
 }
 

@@ -120,8 +120,11 @@ class GaussianModelLatentStrands(GaussianModelStrands):
     ``color_decoder`` is whatever module the caller wants in the checkpoint next to the generator (it may be None)."""
 
     def __init__(self, sh_degree: int, generator=None, color_decoder=None, scale: float = 1e-3, fused: bool = True,
-                 shared_appearance: bool = False):
+                 shared_appearance: bool = False, num_guiding_strands=None):
         super().__init__(sh_degree, scale=scale)
+        if num_guiding_strands is None:  # the generator's own setting (strand_generator.TexturedStrands has one), else none
+            num_guiding_strands = getattr(generator, "num_guiding_strands", 0)
+        self.num_guiding_strands = int(num_guiding_strands or 0)
         self.shared_appearance = bool(shared_appearance) or SHARED_FEATURES
         self.feature_rows_per_strand = 0  # > 1: _features_dc / _features_rest hold one row per STRAND (set by _split)
         self.active_sh_degree = self.max_sh_degree  # the reference's constructor (:64)
@@ -160,6 +163,24 @@ class GaussianModelLatentStrands(GaussianModelStrands):
             conf = expand_rows(conf.reshape(S, 1), n_seg, fused)
         self._orient_conf = conf.reshape(S * n_seg, 1)
 
+    def _split_guiding(self):
+        """:456-461, :477-482: the first ``num_guiding_strands`` strands' rows as views (the full tensors without guiding);
+        per-strand feature storage keeps one row per guide."""
+        N = min(self.num_guiding_strands, self.num_strands)
+        if N == 0:
+            self._xyz_gdn, self._dir_gdn = self._xyz, self._dir
+            self._features_dc_gdn, self._features_rest_gdn = self._features_dc, self._features_rest
+            return
+        n_seg = self.strand_length - 1
+        self._xyz_gdn, self._dir_gdn = self._xyz[:N * n_seg], self._dir[:N * n_seg]
+        rows = N if self.feature_rows_per_strand > 1 else N * n_seg
+        self._features_dc_gdn, self._features_rest_gdn = self._features_dc[:rows], self._features_rest[:rows]
+
+    @property
+    def get_features_gdn(self):
+        """:132-135: ``[rows, K, 3]`` of the guiding strands, in the storage ``_features_dc_gdn`` has"""
+        return torch.cat((self._features_dc_gdn, self._features_rest_gdn), dim=1)
+
     @property
     def get_features(self):
         """[P, K, 3] whatever the storage: per-strand rows are ``repeat``-ed (:465-467) for the generic render path and any
@@ -182,6 +203,7 @@ class GaussianModelLatentStrands(GaussianModelStrands):
         self._pts = p
         self._xyz, self._rotation, self._scaling, self._dir = build_from_points(p, self.scale, self.fused and FUSED_LATENT_BUILD)
         self._split(out)
+        self._split_guiding()
         self.LDiff = out.get("L_diff")
         return out
 

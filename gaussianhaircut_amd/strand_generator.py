@@ -10,6 +10,10 @@ running sum of the decoded local segments taken through each root's frame (``str
 and their backward are HIP (csrc/ghr_texstrands.h): the texture's gradient is assigned whole, in a fixed order, without atomics.
 ``fused=False`` is the PyTorch-composed comparator -- the SAME stored taps, an index gather, the weighted sum in the same order,
 ``cumsum`` and ``matmul`` -- and the only form for CPU tensors.
+
+With ``num_guiding_strands`` only the draw's first ``N`` roots are fetched from the texture; every other root's
+latent row is blended from its four nearest guides in UV by HAAR's cosine-similarity rule (``blend_from_guides``,
+csrc/ghr_guides.h), as the reference's generator is configured by ``arguments/hair_strands_textured.yaml``.
 """
 from __future__ import annotations
 
@@ -282,22 +286,126 @@ def strands_to_world(v, local2world, origins, idx, scale_decoder: float = 1.0, f
     return (p, pl) if return_local else p
 
 
+# ---- per iteration: the other strands from the guides ------------------------------------------------------------------------------
+GUIDE_K = 4
+GUIDE_STATE = ("nbr", "w", "csim", "alpha", "alpha_s", "start", "list")
+
+
+def guide_neighbours_composed(uvs, N: int):
+    """``(nbr [S, 4] int64, w [S, 4])``: every drawn root's four nearest of the first ``N`` roots under a STABLE sort of the
+    squared UV distances (ties: the lower guide first) and their normalised inverse-distance weights."""
+    from .strand_prior import DIST_EPS
+    dist = ((uvs.view(-1, 1, 2) - uvs[:N].view(1, -1, 2)) ** 2).sum(-1)
+    knn_dist, knn_idx = torch.sort(dist, dim=1, stable=True)
+    w = 1 / (knn_dist[:, :GUIDE_K] + DIST_EPS)
+    return knn_idx[:, :GUIDE_K], w / w.sum(dim=-1, keepdim=True)
+
+
+def _blend_composed(uvs, z_g, v_g):
+    from .strand_prior import csim_alpha_composed, inverted_lists
+    N = int(z_g.shape[0])
+    nbr, w = guide_neighbours_composed(uvs.detach(), N)
+    csim, alpha = csim_alpha_composed(v_g, nbr)  # of the guides s < N: their own neighbourhoods
+    alpha_s = (alpha[nbr] * w).sum(dim=1)
+    a, nb, wi = alpha_s[N:, None], nbr[N:], w[N:]
+    z_i = z_g[nb[:, 0]] * a + (z_g[nb] * wi[:, :, None]).sum(dim=1) * (1 - a)
+    start, lst = inverted_lists(nbr, N)
+    state = (nbr.to(torch.int32), w, csim.detach(), alpha.detach(), alpha_s.detach(), start, lst)
+    return torch.cat([z_g, z_i], dim=0), state
+
+
+class _GuidesBlend(torch.autograd.Function):
+    """-> z and, not differentiable, the saved state (nbr, w, csim, alpha, alpha_s, start, list) for inspection."""
+
+    @staticmethod
+    def forward(ctx, uvs, z_g, v_g):
+        from .diff_gaussian_rasterization import _on_device, _ptr, _stream
+        dev = z_g.device
+        S, N, C, n = int(uvs.shape[0]), int(z_g.shape[0]), int(z_g.shape[1]), int(v_g.shape[1])
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        nbr, w = torch.empty((S, GUIDE_K), **i32), torch.empty((S, GUIDE_K), **f32)
+        csim, alpha, alpha_s = torch.empty(N, **f32), torch.empty(N, **f32), torch.empty(S, **f32)
+        ints = torch.empty(2 * N + 1 + 2 * GUIDE_K * S, **i32)  # count | start | list | the lists in arrival order
+        count, start = ints[:N], ints[N:2 * N + 1]
+        lst, unsorted = ints[2 * N + 1:2 * N + 1 + GUIDE_K * S], ints[2 * N + 1 + GUIDE_K * S:]
+        z = torch.empty((S, C), **f32)
+        with _on_device(dev):
+            _lib.check(_lib.lib().ghr_guides_blend(_stream(), S, N, n, C, _ptr(uvs), _ptr(z_g), _ptr(v_g), _ptr(nbr), _ptr(w), _ptr(csim),
+                                                   _ptr(alpha), _ptr(alpha_s), _ptr(count), _ptr(start), _ptr(unsorted), _ptr(lst),
+                                                   _ptr(z)))
+        ctx.save_for_backward(z_g, v_g, nbr, w, csim, alpha_s, start, lst)
+        ctx.meta = (S, N, n, C)
+        ctx.mark_non_differentiable(nbr, w, csim, alpha, alpha_s, start, lst)
+        ctx.set_materialize_grads(False)  # (or autograd zero-fills a cotangent for each of the seven state outputs)
+        return z, nbr, w, csim, alpha, alpha_s, start, lst
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_z, *_):
+        from .diff_gaussian_rasterization import _on_device, _ptr, _stream
+        if d_z is None or not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
+            return None, None, None
+        z_g, v_g, nbr, w, csim, alpha_s, start, lst = ctx.saved_tensors
+        S, N, n, C = ctx.meta
+        dev = z_g.device
+        d_z = d_z.contiguous().float()
+        scratch = torch.empty(S + N, dtype=torch.float32, device=dev)
+        d_zg = torch.empty_like(z_g)
+        d_vg = torch.empty_like(v_g) if ctx.needs_input_grad[2] else None
+        with _on_device(dev):
+            _lib.check(_lib.lib().ghr_guides_blend_backward(_stream(), S, N, n, C, _ptr(z_g), _ptr(v_g), _ptr(nbr), _ptr(w), _ptr(csim),
+                                                            _ptr(alpha_s), _ptr(start), _ptr(lst), _ptr(d_z), _ptr(scratch[:S]),
+                                                            _ptr(scratch[S:]), _ptr(d_zg), None if d_vg is None else _ptr(d_vg)))
+        return None, d_zg if ctx.needs_input_grad[1] else None, d_vg
+
+
+def blend_from_guides(uvs, z_g, v_g, fused=None, return_state: bool = False):
+    """``z [S, C]``: the latent rows of one draw whose first ``N = z_g.shape[0]`` roots are the guides.  ``uvs [S, 2]`` are the
+    drawn roots' UVs (guides first), ``z_g [N, C]`` the guides' fetched rows, ``v_g [N, n, 3]`` their decoded local segments.
+    ``z[:N] = z_g``; a row ``s >= N`` is ``z_g[nbr_0] alpha_s + (sum_k w_k z_g[nbr_k]) (1 - alpha_s)`` over its four nearest
+    guides in UV, ``alpha_s = sum_k w_k alpha[nbr_k]`` and ``alpha[g]`` HAAR's coefficient of the cosine similarity among guide
+    ``g``'s own four neighbours.  Gradients flow to ``z_g`` and, through the coefficients, to ``v_g``; the UVs carry none.
+    ``return_state``: also the dict of neighbour indices, weights, similarities and the guides' inverted lists."""
+    if z_g.dim() != 2 or z_g.shape[1] < 1 or v_g.dim() != 3 or v_g.shape[-1] != 3 or v_g.shape[1] < 1 or v_g.shape[0] != z_g.shape[0]:
+        raise ValueError("z_g must be [N, C] and v_g [N, n, 3] with C, n >= 1")
+    N = int(z_g.shape[0])
+    if uvs.dim() != 2 or uvs.shape[1] != 2 or uvs.shape[0] < N:
+        raise ValueError("uvs must be [S, 2] with S >= N, the guides first")
+    if N < GUIDE_K:
+        raise ValueError("N = %d guiding strands: a strand needs %d" % (N, GUIDE_K))
+    if not _use_fused(fused, z_g):
+        z, state = _blend_composed(uvs, z_g, v_g)
+    else:
+        if z_g.dtype != torch.float32 or v_g.dtype != torch.float32:
+            raise RuntimeError("strand_generator: the HIP form takes float32")
+        _check_on(z_g.device, None, uvs=uvs, v_g=v_g)
+        z, *state = _GuidesBlend.apply(uvs.detach().float().contiguous(), z_g.contiguous(), v_g.contiguous())
+    return (z, dict(zip(GUIDE_STATE, state))) if return_state else z
+
+
 # ---- the generator -----------------------------------------------------------------------------------------------------------------
 class TexturedStrands(torch.nn.Module):
     """``generator(iteration) -> {"points", "features", "orient_conf", "L_diff"}``, the contract ``GaussianModelLatentStrands``
     reads.  Its one own parameter is ``texture [1, Cg + Ca, T, T]`` (zeros); roots, frames, taps and lists are buffers; the
     decoders and ``prior_loss`` are the caller's and, where they are Modules, submodules.  ``features`` / ``orient_conf`` come
-    from ``color_decoder(z_app[:, 1:])`` split ``3 | 3 ((deg + 1)^2 - 1) | 1``; ``L_diff = prior_loss(texture[:, :Cg])``."""
+    from ``color_decoder(z_app[:, 1:])`` split ``3 | 3 ((deg + 1)^2 - 1) | 1``; ``L_diff = prior_loss(texture[:, :Cg])``.
+    ``num_guiding_strands`` (``None`` / ``0``: none; else at least 4): the first ``min(num_guiding_strands, S)`` roots of a draw are
+    the guides, the only rows fetched from the texture; the others are ``blend_from_guides`` of them and the decoder runs on the
+    two groups in turn.  ``last_num_guiding`` is the ``N`` of the last call (0 when every strand was fetched)."""
 
     def __init__(self, scalp, strand_decoder: Callable, color_decoder: Optional[Callable] = None, prior_loss: Optional[Callable] = None,
                  num_strands: int = 10_000, max_num_strands: int = 50_000, texture_size: int = 256, geometry_channels: int = 64,
-                 appearance_channels: int = 65, scale_decoder: float = 1.0, sh_degree: int = 3, generator=None, fused: bool = True):
+                 appearance_channels: int = 65, scale_decoder: float = 1.0, sh_degree: int = 3, generator=None, fused: bool = True,
+                 num_guiding_strands: Optional[int] = None):
         super().__init__()
         S, Smax, Cg, Ca = int(num_strands), int(max_num_strands), int(geometry_channels), int(appearance_channels)
         if not 1 <= S <= Smax:
             raise ValueError("num_strands must be in 1 .. max_num_strands")
         if Cg < 1 or Ca < 0:
             raise ValueError("geometry_channels < 1 or appearance_channels < 0")
+        Ng = 0 if num_guiding_strands is None else int(num_guiding_strands)
+        if Ng < 0 or 0 < Ng < GUIDE_K:
+            raise ValueError("num_guiding_strands must be None, 0 or at least %d: a strand is blended from %d guides" % (GUIDE_K, GUIDE_K))
         vertices, faces, vertex_uvs = scalp
         roots = sample_roots(vertices, faces, vertex_uvs, Smax, generator)
         taps = texture_taps(roots["uvs"], texture_size)
@@ -311,6 +419,8 @@ class TexturedStrands(torch.nn.Module):
             self.register_buffer(name, roots[name])
         for name in Taps._fields[:6]:
             self.register_buffer("tap_" + name, getattr(taps, name))
+        self.num_guiding_strands, self.last_num_guiding = Ng, 0
+        self.guides_fused = None  # None: the blend takes the form the fetch takes; False: the composed blend beside the HIP fetch
         self.last_idx = None
 
     @property
@@ -327,11 +437,23 @@ class TexturedStrands(torch.nn.Module):
 
     def _strands(self, idx, want_local):
         fused = self.fused and self.texture.is_cuda
-        z = sample_texture(self.texture, self.taps, idx, fused=fused, validate=False)
-        z_geom, z_app = z[:, :self.geometry_channels], z[:, self.geometry_channels:]
-        v = self.strand_decoder(z_geom)
+        S, Cg = int(idx.shape[0]), self.geometry_channels
+        N = min(self.num_guiding_strands, S)
+        if N == 0 or S <= N:  # no guiding, or every strand is a guide
+            N = 0
+            z = sample_texture(self.texture, self.taps, idx, fused=fused, validate=False)
+            v = self.strand_decoder(z[:, :Cg])
+        else:  # the first N roots are fetched and decoded; the others' rows are blended from them, then decoded
+            z_g = sample_texture(self.texture, self.taps, idx[:N], fused=fused, validate=False)
+            v_g = self.strand_decoder(z_g[:, :Cg])
+            if v_g.dim() != 3 or v_g.shape[0] != N or v_g.shape[-1] != 3:
+                raise ValueError("strand_decoder must return [S, n, 3], got %s" % (tuple(v_g.shape),))
+            z = blend_from_guides(self.uvs[idx], z_g, v_g, fused=fused if self.guides_fused is None else fused and self.guides_fused)
+            v = torch.cat([v_g, self.strand_decoder(z[N:, :Cg])], dim=0)
+        z_geom, z_app = z[:, :Cg], z[:, Cg:]
         if v.dim() != 3 or v.shape[0] != idx.shape[0] or v.shape[-1] != 3:
             raise ValueError("strand_decoder must return [S, n, 3], got %s" % (tuple(v.shape),))
+        self.last_num_guiding = N
         out = strands_to_world(v, self.local2world, self.origins, idx, self.scale_decoder, fused=fused, return_local=want_local)
         self.last_idx = idx
         return out, z_geom, z_app

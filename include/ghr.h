@@ -1041,6 +1041,27 @@ int ghr_ts_world(void* stream, int32_t Smax, int32_t S, int32_t n, const float* 
 int ghr_ts_world_backward(void* stream, int32_t Smax, int32_t S, int32_t n, const float* local2world, const int64_t* idx,
                           float inv_scale, const float* d_p, const float* d_p_local, float* d_v);
 
+/* ---- guiding strands of the textured generator (csrc/ghr_guides.h)
+ * uvs [S][2] are the UVs of one draw's roots, the N guides first; z_g [N][C] the guides' fetched latent rows, v_g [N][n][3] their
+ * decoded local segments.  float32, no contraction, the operand order of csrc/ghr_sds.h's per-element functions.
+ *
+ * ghr_guides_blend: for every s < S the four nearest guides g < N in UV under (d2 ascending, g ascending) -> nbr [S][4], and
+ *   their normalised inverse-distance weights w [S][4]; for every guide its csim / alpha [N] from its OWN four neighbours'
+ *   segment vectors; alpha_s [S] = sum_k w_k alpha[nbr_k]; z [S][C] row-major: z[s] = z_g[s] for s < N, else
+ *   z_g[nbr_0] alpha_s + (sum_k w_k z_g[nbr_k]) (1 - alpha_s).  start [N + 1] / list [4 S]: per guide the 4 s + k that chose
+ *   it, ASCENDING.  count [N] and unsorted [4 S] are scratch the call fills (count is zero again on return).
+ * ghr_guides_blend_backward: from the forward's buffers and d_z [S][C]: d_zg [N][C] (the guide's own row first, then the
+ *   interpolated rows of its list in order) and, unless NULL, d_vg [N][n][3] (through alpha_s, alpha and csim).  dalpha_s [S]
+ *   and d_csim [N] are scratch.  No floating-point atomics: two calls give the same bits.
+ * Both refuse, with GHR_E_INVALID and a ghr_last_error() text before the runtime is touched: N < 4, S < N, n < 1, C < 1, a NULL
+ * pointer (d_vg excepted), sizes beyond 32-bit indexing. */
+int ghr_guides_blend(void* stream, int32_t S, int32_t N, int32_t n, int32_t C, const float* uvs, const float* z_g, const float* v_g,
+                     int32_t* nbr, float* w, float* csim, float* alpha, float* alpha_s, int32_t* count, int32_t* start,
+                     int32_t* unsorted, int32_t* list, float* z);
+int ghr_guides_blend_backward(void* stream, int32_t S, int32_t N, int32_t n, int32_t C, const float* z_g, const float* v_g,
+                              const int32_t* nbr, const float* w, const float* csim, const float* alpha_s, const int32_t* start,
+                              const int32_t* list, const float* d_z, float* dalpha_s, float* d_csim, float* d_zg, float* d_vg);
+
 /* Introspection for tests (device pointers into the workspaces; layout is otherwise private). */
 typedef struct ghr_ws_view {
     const float* rec;          /* [P][16]: x, y, conic a, b, c, opacity, features[10] */

@@ -4,6 +4,7 @@ of gaussianhaircut_amd/strand_generator.py, fused=False) against F.grid_sample, 
     python tools/genstep.py check
     python tools/genstep.py time [out-file, default profiles/textured_strands.txt]
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o ts -- python tools/genstep.py kernels
+    python tools/genstep.py guiding [out-file, default profiles/textured_strands_guiding.txt]
 
 ``check``: at a small size, both forms against the float64 form under |got - f64| <= 1e-5 max|f64| + 3 |composed - f64|, two
 backward passes bit-equal, a permuted draw bit-equal; prints the figures, exits non-zero on a miss.
@@ -13,7 +14,10 @@ events.  Launch counts come from torch.profiler over one call.  The decoders are
 in every form alike.  The whole latent_strand_training_step is timed with each form of the generator.
 ``kernels``: the four HIP pieces at the same sizes, ITERS calls each and nothing else: the run a kernel trace is taken of (a call's
 time between events includes the host's enqueue, which at these sizes is most of it); its per-kernel times are kept in
-profiles/textured_strands_kernels.txt, which ``time`` does not touch."""
+profiles/textured_strands_kernels.txt, which ``time`` does not touch.
+``guiding``: with num_guiding_strands = 1 000 of the 10 000 drawn, the blend alone (csrc/ghr_guides.h against the
+composed form of ``blend_from_guides``), forward and backward, and the whole latent_strand_training_step with the blend in HIP,
+with the blend composed and without guiding strands -- alternated in one call as ``time`` alternates its forms."""
 import os
 import statistics
 import sys
@@ -76,13 +80,14 @@ class GridSampleStrands(sg.TexturedStrands):
         return out, z_geom, z_app
 
 
-def make_generator(dev, form, sizes=None, seed=7):
+def make_generator(dev, form, sizes=None, seed=7, num_guiding=None):
     smax, s, t, cg, ca, length = sizes or (SMAX, S, T, CG, CA, L)
     target = torch.rand(1, cg, t, t, generator=torch.Generator().manual_seed(seed + 1)).to(dev)
     cls = GridSampleStrands if form == "grid_sample" else sg.TexturedStrands
     gen = cls(scalp(), Decoder(cg, (length - 1, 3), seed + 2, 0.02), Decoder(ca - 1, (49,), seed + 3, 0.1),
               lambda tex: ((tex - target) ** 2).mean(), num_strands=s, max_num_strands=smax, texture_size=t, geometry_channels=cg,
-              appearance_channels=ca, scale_decoder=2.0, generator=torch.Generator().manual_seed(seed), fused=(form == "HIP"))
+              appearance_channels=ca, scale_decoder=2.0, generator=torch.Generator().manual_seed(seed), fused=(form == "HIP"),
+              num_guiding_strands=num_guiding)
     with torch.no_grad():
         gen.texture.copy_(torch.rand(gen.texture.shape, generator=torch.Generator().manual_seed(seed + 4)) * 2 - 1)
     return gen.to(dev)
@@ -109,7 +114,7 @@ def launches(fn):
         torch.cuda.synchronize()
     ev = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
     moves = sum(1 for e in ev if any(s in e.name.lower() for s in ("memcpy", "memset")))
-    own = sum(1 for e in ev if "k_ts_" in e.name)
+    own = sum(1 for e in ev if "k_ts_" in e.name or "k_gd_" in e.name)
     return len(ev) - moves, own, moves
 
 
@@ -279,12 +284,128 @@ def main_time(out_path):
     print(text)
 
 
+NG = 1_000  # arguments/hair_strands_textured.yaml: extra_args.num_guiding_strands
+
+
+def main_guiding(out_path):
+    dev = torch.device("cuda:0")
+    C, n = CG + CA, L - 1
+    base = make_generator(dev, "HIP", num_guiding=NG)
+    idx = base.draw()
+    uvs = base.uvs[idx].contiguous()
+    with torch.no_grad():
+        z0 = sg.sample_texture(base.texture, base.taps, idx[:NG], validate=False)
+        v0 = base.strand_decoder(z0[:, :CG])
+    z_g, v_g = z0.clone().requires_grad_(True), v0.clone().requires_grad_(True)
+    d_z = torch.randn(S, C, device=dev)
+    forms = ("HIP", "composed")
+    pieces = {}
+    for form in forms:
+        z = sg.blend_from_guides(uvs, z_g, v_g, fused=(form == "HIP"))
+        pieces["blend forward", form] = lambda form=form: sg.blend_from_guides(uvs, z_g, v_g, fused=(form == "HIP"))
+        pieces["blend backward", form] = lambda z=z: torch.autograd.grad(z, (z_g, v_g), d_z, retain_graph=True)
+    rounds = {k: [] for k in pieces}
+    for fn in pieces.values():
+        for _ in range(3):
+            fn()
+    for _ in range(ROUNDS):
+        for k, fn in pieces.items():
+            rounds[k].append(timed_median(fn, ITERS))
+    counts = {k: launches(fn) for k, fn in pieces.items()}
+    agree = {}
+    outs = {form: sg.blend_from_guides(uvs, z_g, v_g, fused=(form == "HIP"), return_state=True) for form in forms}
+    agree["nbr"] = bool(torch.equal(outs["HIP"][1]["nbr"], outs["composed"][1]["nbr"]))
+    agree["list"] = bool(torch.equal(outs["HIP"][1]["list"], outs["composed"][1]["list"]))
+    agree["z"] = float((outs["HIP"][0] - outs["composed"][0]).detach().abs().max())
+    lens = (outs["HIP"][1]["start"][1:] - outs["HIP"][1]["start"][:-1]).float()
+    del pieces, outs
+
+    # the whole latent-strand iteration: the blend in HIP, the blend composed beside the HIP fetch, no guiding strands
+    from gaussianhaircut_amd.gaussian_renderer import render_hair
+    from gaussianhaircut_amd.scene.cameras import ring_cameras
+    from gaussianhaircut_amd.scene.gaussian_model_latent_strands import GaussianModelLatentStrands
+    from gaussianhaircut_amd.trainer import latent_strand_training_step
+    from gaussianhaircut_amd.utils import synthetic as syn
+    spec = syn.CONFIGS["cfg3"]
+    bg = syn.background(dev)
+    n_head = 100_000
+    head = syn.make_model(spec, dev)
+    with torch.no_grad():
+        head._label[:n_head] = -4.0
+        head._label[n_head:] = 4.0
+    head.precompute_head()
+    cam = ring_cameras(1, spec.W, spec.H, device=dev)[0]
+    opt = SimpleNamespace(lambda_dl1=1.0, lambda_dmask=0.1, lambda_dorient=0.1, lambda_dsds=0.001, use_gt_orient_conf=True,
+                          train_orient_conf=True, iterations=10 ** 6, latent_lr=1e-3)
+    with torch.no_grad():
+        gt = GaussianModelLatentStrands(3, make_generator(dev, "HIP", seed=21), None)
+        gt.initialize_gaussians_hair(0)
+        pk = render_hair(cam, head, gt, PIPE, bg)
+        cam.original_image, cam.original_mask = pk["render"].clamp(0, 1).detach(), pk["mask"].clamp(0, 1).detach()
+        cam.original_orient_angle = pk["orient_angle"].detach()
+        cam.original_orient_conf = torch.ones_like(pk["orient_conf"]).detach()
+        del gt, pk
+    gens = {"guiding, blend in HIP": base, "guiding, blend composed": make_generator(dev, "HIP", num_guiding=NG),
+            "no guiding strands": make_generator(dev, "HIP")}
+    gens["guiding, blend composed"].guides_fused = False
+    steps, it = {}, [0]
+    for name, gen in gens.items():
+        hair = GaussianModelLatentStrands(3, gen, None)
+        hair.training_setup(opt)
+
+        def step(hair=hair):
+            it[0] += 1
+            latent_strand_training_step(head, hair, [cam], bg, opt, it[0], pipe=PIPE)
+        steps[name] = step
+    step_rounds = {name: [] for name in steps}
+    for fn in steps.values():
+        for _ in range(4):
+            fn()
+    for _ in range(ROUNDS):
+        for name, fn in steps.items():
+            step_rounds[name].append(timed_median(fn, ITERS))
+    step_counts = {name: launches(fn) for name, fn in steps.items()}
+
+    med = statistics.median
+    fmt_rounds = lambda xs: " / ".join("%.4f" % x for x in xs)  # noqa: E731
+    fmt_count = lambda c: "%d kernels (%d of them k_ts_* / k_gd_*) + %d fills and copies" % c  # noqa: E731
+    lines = ["guiding strands of the textured generator: S = %d drawn roots of which N = %d guides, n = %d segments, C = %d + %d channels" % (
+                 S, NG, n, CG, CA),
+             "(sizes of the reference's arguments/hair_strands_textured.yaml; Smax = %d, T = %d; the decoders are one linear layer each)" % (SMAX, T),
+             "device: %s, torch %s; each round = the median of %d calls, each between two device events; %d alternating rounds" % (
+                 torch.cuda.get_device_name(0), torch.__version__, ITERS, ROUNDS),
+             "",
+             "the blend alone, ms: median of the rounds | rounds | launches of one call"]
+    for (piece, form), xs in rounds.items():
+        lines.append("  %-16s %-10s %8.4f | %s | %s" % (piece, form, med(xs), fmt_rounds(xs), fmt_count(counts[piece, form])))
+    for piece in ("blend forward", "blend backward"):
+        lines.append("%s: composed / HIP = %.2fx" % (piece, med(rounds[piece, "composed"]) / med(rounds[piece, "HIP"])))
+    lines += ["the two forms on this draw: nbr equal %s, lists equal %s, max |z HIP - z composed| = %.3e" % (agree["nbr"], agree["list"], agree["z"]),
+              "inverted lists: %d choices over %d guides, mean %.1f, longest %d (k_gd_lists ranks each list: work sum L^2 = %.2e compares)" % (
+                  4 * S, NG, float(lens.mean()), int(lens.max()), float((lens * lens).sum())),
+              "",
+              "latent_strand_training_step, %d strands x %d segments + %d head Gaussians, 1 view %dx%d, ms per iteration" % (S, n, n_head, spec.W, spec.H)]
+    for name in steps:
+        lines.append("  %-26s median %.3f   rounds %s   launches: %s" % (name, med(step_rounds[name]), fmt_rounds(step_rounds[name]),
+                                                                        fmt_count(step_counts[name])))
+    lines += ["the figures include the host's enqueue of a call; the decoder runs on N and on S - N rows with guiding strands, on S rows without",
+              "not profiled: a kernel trace of the k_gd_* kernels; counters (--pmc); other sizes; real decoders"]
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write(text)
+    print(text)
+
+
 if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else ""
     if mode == "check":
         sys.exit(check())
     if mode == "kernels":
         sys.exit(main_kernels())
+    if mode == "guiding":
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        sys.exit(main_guiding(sys.argv[2] if len(sys.argv) > 2 else os.path.join(root, "profiles", "textured_strands_guiding.txt")))
     if mode == "time":
         root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
         main_time(sys.argv[2] if len(sys.argv) > 2 else os.path.join(root, "profiles", "textured_strands.txt"))
