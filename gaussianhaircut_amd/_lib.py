@@ -148,6 +148,15 @@ class ViewStepArgs(ctypes.Structure):
                 ("count_event", ctypes.c_void_p), ("acc_wait_event", ctypes.c_void_p), ("acc_record_event", ctypes.c_void_p)]
 
 
+class ViewCameraArgs(ctypes.Structure):
+    """``ghr_view_camera_args`` (include/ghr.h): the bank row a ``ghr_view_step_camera`` view composes and back-propagates into."""
+    _fields_ = [("parametrisation", ctypes.c_int32), ("rows", ctypes.c_int32), ("index", ctypes.c_int32),
+                ("const_stride", ctypes.c_int32), ("consts", ctypes.c_void_p), ("params", ctypes.c_void_p),
+                ("param_stride", ctypes.c_int32), ("grad_stride", ctypes.c_int32), ("grads", ctypes.c_void_p),
+                ("touched", ctypes.c_void_p), ("train_mask", ctypes.c_int32), ("out_row", ctypes.c_void_p),
+                ("d_cam", ctypes.c_void_p)]
+
+
 class EvalArgs(ctypes.Structure):
     """``ghr_eval_args`` (include/ghr.h)."""
     _fields_ = [("W", ctypes.c_int32), ("H", ctypes.c_int32)] + \
@@ -227,6 +236,7 @@ EXPORTS = ["ghr_last_error", "ghr_abi_version", "ghr_forward_sizes", "ghr_binnin
            "ghr_adam_step_range", "ghr_adam_step_range_to", "ghr_adam_nan_scan", "ghr_adam_relay_rows", "ghr_adam_fused_finish",
            "ghr_knn_workspace_size", "ghr_knn_keys", "ghr_knn_mean_dist2",
            "ghr_camera_compose", "ghr_camera_compose_backward", "ghr_camera_adam_step",
+           "ghr_view_step_camera", "ghr_camera_pack_row_message", "ghr_camera_merge_ranks",
            "ghr_eval_scratch_floats", "ghr_eval_metrics", "ghr_eval_products",
            "ghr_orient_dog_scratch_bytes", "ghr_orient_dog", "ghr_orient_bank_floats", "ghr_orient_gabor",
            "ghr_resample_scratch_bytes", "ghr_resample_u8", "ghr_gt_assemble", "ghr_gt_resize_variance", "ghr_gt_from_render",
@@ -312,6 +322,9 @@ def lib() -> ctypes.CDLL:
     L.ghr_camera_compose_backward.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, i32] + [vp] * 6 + [vp, i32, vp, i32]
     L.ghr_camera_adam_step.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, f32, f32, f32, ctypes.c_double, ctypes.c_double,
                                        f32, i32]
+    L.ghr_view_step_camera.argtypes = [vp, ctypes.POINTER(ViewStepArgs), ctypes.POINTER(ViewCameraArgs)]
+    L.ghr_camera_pack_row_message.argtypes = [vp, i32, i32, vp, i32, vp, vp]
+    L.ghr_camera_merge_ranks.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp]
     L.ghr_eval_scratch_floats.argtypes = [i32, i32]
     L.ghr_eval_metrics.argtypes = [vp, ctypes.POINTER(EvalArgs), vp, vp]
     L.ghr_eval_products.argtypes = [vp, i32, i32, vp, vp, vp]

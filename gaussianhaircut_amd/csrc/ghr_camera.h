@@ -445,4 +445,43 @@ __global__ void __launch_bounds__(GHR_CAM_ADAM_THREADS) k_cam_adam(int param, in
     }
 }
 
+// ---- a replicated bank: the gradient rows of G ranks (scene.cameras.CameraBank.exchange_gradients) ---------------------------------
+// One thread per (row, column) of the message [n][W + 1]: a touched row travels as its W gradient floats and 1.0f, an untouched one
+// as zeros -- what its gradient row holds (a stale NaN: the backward kernel ASSIGNS to an untouched row, nobody clears it before)
+// is not read.
+#define GHR_CAM_XCHG_THREADS 256
+__global__ void __launch_bounds__(GHR_CAM_XCHG_THREADS) k_cam_pack(int n, int W, const float* __restrict__ g, int stride,
+                                                                   const int* __restrict__ touched, float* __restrict__ msg)
+{
+    const size_t i = (size_t)blockIdx.x * GHR_CAM_XCHG_THREADS + threadIdx.x;
+    if (i >= (size_t)n * (size_t)(W + 1)) return;
+    const int r = (int)(i / (size_t)(W + 1)), k = (int)(i % (size_t)(W + 1));
+    float x = 0.f;
+    if (touched[r]) x = k < W ? g[(size_t)r * stride + k] : 1.f;
+    msg[i] = x;
+}
+
+// One thread per (row, column) of the gradient rows; `all` [G][n][W + 1] holds the ranks' messages in rank order.  The first rank
+// that touched the row assigns, the later ones add, in ascending rank order: every rank computes the same bits, and a row that one
+// rank alone touched keeps that rank's.  A row nobody touched is left exactly as it is (gradient row and mark).
+__global__ void __launch_bounds__(GHR_CAM_XCHG_THREADS) k_cam_merge(int n, int W, int G, const float* __restrict__ all,
+                                                                    float* __restrict__ g, int stride, int* __restrict__ touched)
+{
+    const size_t i = (size_t)blockIdx.x * GHR_CAM_XCHG_THREADS + threadIdx.x;
+    if (i >= (size_t)n * (size_t)W) return;
+    const int r = (int)(i / (size_t)W), k = (int)(i % (size_t)W);
+    const size_t row = (size_t)r * (size_t)(W + 1), rank = (size_t)n * (size_t)(W + 1);
+    bool any = false;
+    float acc = 0.f;
+    for (int q = 0; q < G; q++) {
+        const float* m = all + (size_t)q * rank + row;
+        if (m[W] == 0.f) continue;
+        acc = any ? acc + m[k] : m[k];
+        any = true;
+    }
+    if (!any) return;
+    g[(size_t)r * stride + k] = acc;
+    if (k == 0) touched[r] = 1;
+}
+
 }  // namespace ghr

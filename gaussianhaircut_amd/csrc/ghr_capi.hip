@@ -1074,7 +1074,8 @@ int vs_bad(const char* what) { return fail(GHR_E_INVALID, "ghr_view_step: %s", w
 // Everything ghr_view_step refuses, asked before the first launch.  First what the call itself does not cover, and the rules
 // of the six calls in its own words: a NULL buffer by the name of its field, the others with the predicate their owner asks
 // too.  Then the six calls' own checks, in call order: what they refuse is refused here, whether or not it has words above.
-int check_view_step(const ghr_view_step_args* v, const ghr_view_args* va, const ghr_loss_args* lr, const ProjGrads& pg)
+// `camera`: the view of ghr_view_step_camera, whose model carries the camera-gradient table and the device FoV (checked there).
+int check_view_step(const ghr_view_step_args* v, const ghr_view_args* va, const ghr_loss_args* lr, const ProjGrads& pg, bool camera)
 {
     const ghr_model_args* m = &v->model;
     if (m->P <= 0) return vs_bad("model.P must be > 0");
@@ -1084,8 +1085,9 @@ int check_view_step(const ghr_view_step_args* v, const ghr_view_args* va, const 
     if (m->mode != 0) return vs_bad("model.mode must be 0");
     if (m->row0 != 0) return vs_bad("model.row0 must be 0");
     if (m->debug != 0) return vs_bad("model.debug must be 0 (the call never waits for the device)");
-    if (m->cam_partial || m->cam_only || m->detach_means2D) return vs_bad("model.cam_partial / cam_only / detach_means2D: camera gradients are not part of the call");
-    if (m->fovx_dev || m->fovy_dev) return vs_bad("model.fovx_dev / fovy_dev must be NULL");
+    if ((!camera && m->cam_partial) || m->cam_only || m->detach_means2D)
+        return vs_bad("model.cam_partial / cam_only / detach_means2D: camera gradients are not part of the call");
+    if (!camera && (m->fovx_dev || m->fovy_dev)) return vs_bad("model.fovx_dev / fovy_dev must be NULL");
     if (!sh_degree_ok(m->sh_degree)) return vs_bad("model.sh_degree must be 0 .. 3");
     if (!sh_coeffs_ok(m->sh_coeffs) || !sh_covers(m->sh_degree, m->sh_coeffs))
         return vs_bad("model.sh_coeffs must be (max_sh_degree + 1)^2 and cover model.sh_degree");
@@ -1144,27 +1146,39 @@ int check_view_step(const ghr_view_step_args* v, const ghr_view_args* va, const 
             return rc;
     return check_backward_segment(m, nullptr, m->P, v->radii, v->geom_ws, pg, v->accumulate, v->nan_flag, v->bin_ws, v->R, &a, &mg);
 }
-}  // namespace
 
-int ghr_view_step(void* stream, const ghr_view_step_args* v)
+
+// what the six calls take that is no field of `v`: stage 2's view struct, the loss struct over the rendered planes of the
+// packed output (include/ghr.h, ghr_loss_args), the gradient pointers
+struct ViewStepPlan {
+    ghr_view_args va;
+    ghr_loss_args l;
+    ProjGrads pg;
+};
+
+int plan_view_step(const ghr_view_step_args* v, bool camera, ViewStepPlan* p)
 {
     if (!v) return vs_bad("the argument struct is NULL");
     const ghr_model_args* m = &v->model;
     const size_t n = (size_t)m->W * m->H;
-    // what the six calls take that is no field of `v`: stage 2's view struct, the loss struct over the rendered planes of the
-    // packed output (include/ghr.h, ghr_loss_args), the gradient pointers
-    ghr_view_args va;
-    std::memset(&va, 0, sizeof(va));
-    va.P = m->P; va.W = m->W; va.H = m->H; va.C = GHR_NUM_CHANNELS; va.background = m->background;
-    ghr_loss_args l = v->loss;
-    l.image = v->render; l.mask = v->render + 3 * n; l.dir2d = v->render + 5 * n; l.orient_conf = v->render + 8 * n;
-    const ProjGrads pg{v->d_means2D, v->d_xyz, v->d_log_scales, v->d_rotations, v->d_opacity_logit, v->d_label_logit,
-                       v->d_orient_conf_log, v->d_features_dc, v->d_features_rest, nullptr};
-    if (int rc = check_view_step(v, &va, &l, pg)) return rc;
+    std::memset(&p->va, 0, sizeof(p->va));
+    p->va.P = m->P; p->va.W = m->W; p->va.H = m->H; p->va.C = GHR_NUM_CHANNELS; p->va.background = m->background;
+    p->l = v->loss;
+    p->l.image = v->render; p->l.mask = v->render + 3 * n; p->l.dir2d = v->render + 5 * n; p->l.orient_conf = v->render + 8 * n;
+    p->pg = ProjGrads{v->d_means2D, v->d_xyz, v->d_log_scales, v->d_rotations, v->d_opacity_logit, v->d_label_logit,
+                      v->d_orient_conf_log, v->d_features_dc, v->d_features_rest, nullptr};
+    return check_view_step(v, &p->va, &p->l, p->pg, camera);
+}
+
+int run_view_step(void* stream, const ghr_view_step_args* v, ViewStepPlan& p)
+{
+    const ghr_model_args* m = &v->model;
+    const size_t n = (size_t)m->W * m->H;
+    ghr_loss_args& l = p.l;
     hipStream_t s = (hipStream_t)stream;
     if (int rc = ghr_model_forward_stage1(stream, m, v->geom_ws, v->img_ws, v->radii, v->means2D_out, v->R_host)) return rc;
     if (v->count_event) GHR_HIP(hipEventRecord((hipEvent_t)v->count_event, s));
-    if (int rc = ghr_forward_stage2(stream, &va, v->R, v->geom_ws, v->img_ws, v->bin_ws, v->render,
+    if (int rc = ghr_forward_stage2(stream, &p.va, v->R, v->geom_ws, v->img_ws, v->bin_ws, v->render,
                                     v->prezero ? v->grad_scratch : nullptr))
         return rc;
     if (int rc = ghr_loss_forward(stream, &l, v->maps, v->sums, v->loss_out)) return rc;
@@ -1182,11 +1196,19 @@ int ghr_view_step(void* stream, const ghr_view_step_args* v)
                                             f->g_views, f->view_stride, f->d_features_dc, f->d_features_rest, f->accumulate,
                                             nullptr, 0))
             return rc;
-    if (int rc = backward_segment(m, nullptr, nullptr, stream, m->P, v->radii, v->geom_ws, v->grad_scratch, pg, v->accumulate,
+    if (int rc = backward_segment(m, nullptr, nullptr, stream, m->P, v->radii, v->geom_ws, v->grad_scratch, p.pg, v->accumulate,
                                   v->nan_flag, v->R, v->bin_ws, v->R))
         return rc;
     if (v->acc_record_event) GHR_HIP(hipEventRecord((hipEvent_t)v->acc_record_event, s));
     return GHR_OK;
+}
+}  // namespace
+
+int ghr_view_step(void* stream, const ghr_view_step_args* v)
+{
+    ViewStepPlan p;
+    if (int rc = plan_view_step(v, false, &p)) return rc;
+    return run_view_step(stream, v, p);
 }
 
 // ---- evaluation pass (ghr_eval.h) ------------------------------------------------------------------------------------
@@ -1833,6 +1855,88 @@ int ghr_camera_adam_step(void* stream, int32_t parametrisation, int32_t n, float
     hipLaunchKernelGGL(ghr::k_cam_adam, dim3(1), dim3(GHR_CAM_ADAM_THREADS), 0, (hipStream_t)stream, parametrisation, n, params,
                        grads, exp_avg, exp_avg_sq, stride, steps, touched, lr_rotation, lr_translation, lr_fov, beta1, beta2, eps,
                        train_mask);
+    return finish((hipStream_t)stream, 0);
+}
+
+// ---- a training view with a bank camera (include/ghr.h, ghr_view_step_camera) and the exchange of a replicated bank's rows ---------
+namespace {
+int vc_bad(const char* what) { return fail(GHR_E_INVALID, "ghr_view_step_camera: %s", what); }
+}  // namespace
+
+int ghr_view_step_camera(void* stream, const ghr_view_step_args* v, const ghr_view_camera_args* c)
+{
+    if (!v) return vc_bad("the view's argument struct is NULL");
+    if (!c) return vc_bad("the camera's argument struct (c) is NULL");
+    // the camera's side first, in its own words; then everything ghr_view_step refuses; nothing is launched before both passed
+    if (c->rows < 0 || c->index < 0 || c->index >= c->rows) return vc_bad("index outside rows");
+    if (int rc = check_camera_rows("ghr_view_step_camera", c->parametrisation, c->rows, c->index, 1, c->consts, c->const_stride,
+                                   c->params, c->param_stride))
+        return rc;
+    if (c->train_mask == 0) return vc_bad("train_mask is 0: a bank with both groups frozen is a constant camera (ghr_view_step)");
+    if (c->train_mask & ~(GHR_CAM_TRAIN_POSE | GHR_CAM_TRAIN_FOV)) return vc_bad("bad train_mask");
+    if (!c->grads) return vc_bad("grads is NULL");
+    if (!c->touched) return vc_bad("touched is NULL");
+    if (c->grad_stride < ghr::cam_row(c->parametrisation)) return vc_bad("grad_stride is smaller than the row");
+    if (!c->out_row) return vc_bad("out_row is NULL");
+    if (!c->d_cam) return vc_bad("d_cam is NULL");
+    const ghr_model_args* m = &v->model;
+    if (!m->cam_partial) return vc_bad("model.cam_partial is NULL");
+    if (m->cam_slot0 != 0 || m->cam_slots != ghr_camera_slots(m->P))
+        return vc_bad("model.cam_slots must be ghr_camera_slots(model.P) (and model.cam_slot0 0): the view has one segment");
+    if (!m->fovx_dev || !m->fovy_dev) return vc_bad("model.fovx_dev / fovy_dev is NULL");
+    if (m->viewmatrix != c->out_row) return vc_bad("model.viewmatrix must be out_row");
+    if (m->projmatrix != c->out_row + 16) return vc_bad("model.projmatrix must be out_row + 16");
+    if (m->campos != c->out_row + 48) return vc_bad("model.campos must be out_row + 48");
+    if (m->fovx_dev != c->out_row + 51) return vc_bad("model.fovx_dev must be out_row + 51");
+    if (m->fovy_dev != c->out_row + 52) return vc_bad("model.fovy_dev must be out_row + 52");
+    ViewStepPlan p;
+    if (int rc = plan_view_step(v, true, &p)) return rc;
+    if (int rc = ghr_camera_compose(stream, c->parametrisation, c->rows, c->index, 1, c->consts, c->const_stride, c->params,
+                                    c->param_stride, c->out_row, GHR_CAM_OUT))
+        return rc;
+    if (int rc = run_view_step(stream, v, p)) return rc;
+    if (int rc = ghr_camera_grad_fold(stream, m->cam_partial, m->cam_slots, c->d_cam, m->fovx_dev, m->fovy_dev)) return rc;
+    const float* d = c->d_cam;
+    return ghr_camera_compose_backward(stream, c->parametrisation, c->rows, c->index, 1, c->consts, c->const_stride, c->params,
+                                       c->param_stride, d, d + 16, nullptr, d + 32, d + 35, d + 36, c->grads, c->grad_stride,
+                                       c->touched, c->train_mask);
+}
+
+static int check_camera_exchange(const char* who, int32_t n, int32_t width, int32_t grad_stride)
+{
+    if (n < 0) return fail(GHR_E_INVALID, "%s: n < 0", who);
+    if (width != ghr::cam_row(GHR_CAM_SE3) && width != ghr::cam_row(GHR_CAM_ORTHO6D))
+        return fail(GHR_E_INVALID, "%s: width must be 8 (se(3)) or 11 (ortho-6D)", who);
+    if (grad_stride < width) return fail(GHR_E_INVALID, "%s: grad_stride is smaller than the row", who);
+    return GHR_OK;
+}
+
+int ghr_camera_pack_row_message(void* stream, int32_t n, int32_t width, const float* grads, int32_t grad_stride,
+                                const int32_t* touched, float* message)
+{
+    if (int rc = check_camera_exchange("ghr_camera_pack_row_message", n, width, grad_stride)) return rc;
+    if (!grads) return fail(GHR_E_INVALID, "ghr_camera_pack_row_message: grads is NULL");
+    if (!touched) return fail(GHR_E_INVALID, "ghr_camera_pack_row_message: touched is NULL");
+    if (!message) return fail(GHR_E_INVALID, "ghr_camera_pack_row_message: message is NULL");
+    if (n == 0) return GHR_OK;
+    const size_t total = (size_t)n * (size_t)(width + 1);
+    hipLaunchKernelGGL(ghr::k_cam_pack, dim3((unsigned)((total + GHR_CAM_XCHG_THREADS - 1) / GHR_CAM_XCHG_THREADS)),
+                       dim3(GHR_CAM_XCHG_THREADS), 0, (hipStream_t)stream, n, width, grads, grad_stride, touched, message);
+    return finish((hipStream_t)stream, 0);
+}
+
+int ghr_camera_merge_ranks(void* stream, int32_t n, int32_t width, int32_t G, const float* gathered, float* grads,
+                           int32_t grad_stride, int32_t* touched)
+{
+    if (int rc = check_camera_exchange("ghr_camera_merge_ranks", n, width, grad_stride)) return rc;
+    if (G < 1) return fail(GHR_E_INVALID, "ghr_camera_merge_ranks: G < 1");
+    if (!gathered) return fail(GHR_E_INVALID, "ghr_camera_merge_ranks: gathered is NULL");
+    if (!grads) return fail(GHR_E_INVALID, "ghr_camera_merge_ranks: grads is NULL");
+    if (!touched) return fail(GHR_E_INVALID, "ghr_camera_merge_ranks: touched is NULL");
+    if (n == 0) return GHR_OK;
+    const size_t total = (size_t)n * (size_t)width;
+    hipLaunchKernelGGL(ghr::k_cam_merge, dim3((unsigned)((total + GHR_CAM_XCHG_THREADS - 1) / GHR_CAM_XCHG_THREADS)),
+                       dim3(GHR_CAM_XCHG_THREADS), 0, (hipStream_t)stream, n, width, G, gathered, grads, grad_stride, touched);
     return finish((hipStream_t)stream, 0);
 }
 

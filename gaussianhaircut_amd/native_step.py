@@ -1,5 +1,7 @@
 """The native view step: render + stage-1 loss + backward of one training view as ONE library call (``ghr_view_step``,
-include/ghr.h) on buffers that are allocated once.
+include/ghr.h) on buffers that are allocated once.  A view whose camera is a row of a training ``scene.cameras.CameraBank`` is
+``ghr_view_step_camera``: the same call with the camera's compose in front and the fold of its gradients and the compose's
+backward behind, as ``_BankCompose`` and ``fused._camera_grads`` chain them on the Python path.
 
 ``trainer.training_step(native=True)`` (or ``GHR_NATIVE_STEP=1``) routes the views of an eligible step through here instead of
 through the two ``autograd.Function`` round trips of ``render()`` / ``view_loss()`` / ``backward()``: the same kernels with the
@@ -41,43 +43,58 @@ def _plain_f32(t) -> bool:
 
 
 class _CamFields:
-    """Pointers of a constant camera and of its ground truth, remade when one of the tensors is replaced."""
-    __slots__ = ("tensors", "ptrs", "W", "H")
+    """Pointers of a constant camera and of its ground truth, remade when one of the tensors is replaced.  ``bank``: the camera is a
+    row of this TRAINING bank -- it has no tensors of its own (the first three are None), the view composes them."""
+    __slots__ = ("tensors", "ptrs", "W", "H", "bank", "fov")
 
-    def __init__(self, tensors, W, H):
-        self.tensors, self.W, self.H = tensors, W, H
-        self.ptrs = tuple(t.data_ptr() for t in tensors)
-
-
-def _cam_tensors(cam):
-    return (cam.world_view_transform, cam.full_proj_transform, cam.camera_center, cam.original_image, cam.original_mask,
-            cam.original_orient_angle, cam.original_orient_conf)
+    def __init__(self, tensors, W, H, bank, fov):
+        self.tensors, self.W, self.H, self.bank, self.fov = tensors, W, H, bank, fov
+        self.ptrs = tuple(None if t is None else t.data_ptr() for t in tensors)
 
 
-def _cam_fields(cam) -> Optional[_CamFields]:
-    """None: this camera's view cannot take the native path (its tensors are composed per access or trained, it belongs to
-    a camera bank, or its ground truth is not plain contiguous fp32 device data)."""
-    if hasattr(cam, "tensors") or getattr(cam, "bank", None) is not None:
+def _cam_fields(cam, dev=None) -> Optional[_CamFields]:
+    """None: this camera's view cannot take the native path (its tensors are trained leaves or composed per access by PyTorch, it
+    belongs to a bank that is not fused or not on ``dev``, or its ground truth is not plain contiguous fp32 device data).  A camera
+    of a fused bank is a constant camera while the bank does not train (``BankCamera.tensors()`` caches them then)."""
+    bank = getattr(cam, "bank", None)
+    live = None
+    if bank is not None:
+        if not bank.fused or (dev is not None and bank.params.device != dev):
+            return None
+        live = bank if (bank.live and bank.train_mask) else None
+    elif hasattr(cam, "tensors"):
         return None
     try:
-        ts = _cam_tensors(cam)
+        gt = (cam.original_image, cam.original_mask, cam.original_orient_angle, cam.original_orient_conf)
+        if live is not None:
+            ts, fov = (None, None, None) + gt, None
+        elif bank is not None:
+            t = cam.tensors()
+            ts, fov = (t[0], t[1], t[2]) + gt, (t[3], t[4])
+        else:
+            ts, fov = (cam.world_view_transform, cam.full_proj_transform, cam.camera_center) + gt, (cam.FoVx, cam.FoVy)
     except AttributeError:
         return None
     c = cam.__dict__.get("_ghr_native_fields")
-    if c is not None and all(a is b for a, b in zip(c.tensors, ts)):
+    if c is not None and c.bank is live and all(a is b for a, b in zip(c.tensors, ts)):
+        if live is not None:
+            return c
+        c.fov = fov
         # (the same tensors: still constants?  requires_grad_() does not replace the object)
-        live = ts[0].requires_grad or ts[1].requires_grad or ts[2].requires_grad or \
-            any(isinstance(f, torch.Tensor) and f.requires_grad for f in (cam.FoVx, cam.FoVy))
-        return None if live else c
+        trained = ts[0].requires_grad or ts[1].requires_grad or ts[2].requires_grad or \
+            any(isinstance(f, torch.Tensor) and f.requires_grad for f in fov)
+        return None if trained else c
     W, H = int(cam.image_width), int(cam.image_height)
-    if not all(_plain_f32(t) for t in ts):
+    if not all(_plain_f32(t) for t in ts if live is None or t is not None):
         return None
-    if any(isinstance(f, torch.Tensor) and f.requires_grad for f in (cam.FoVx, cam.FoVy)):
+    if live is None:
+        if any(isinstance(f, torch.Tensor) and f.requires_grad for f in fov):
+            return None
+        if ts[0].numel() != 16 or ts[1].numel() != 16 or ts[2].numel() != 3:
+            return None
+    if tuple(ts[3].shape) != (3, H, W) or tuple(ts[4].shape) != (2, H, W) or ts[5].numel() != H * W or ts[6].numel() != H * W:
         return None
-    if ts[0].numel() != 16 or ts[1].numel() != 16 or ts[2].numel() != 3 or tuple(ts[3].shape) != (3, H, W) or \
-            tuple(ts[4].shape) != (2, H, W) or ts[5].numel() != H * W or ts[6].numel() != H * W:
-        return None
-    c = _CamFields(ts, W, H)
+    c = _CamFields(ts, W, H, live, fov)
     cam.__dict__["_ghr_native_fields"] = c
     return c
 
@@ -97,8 +114,6 @@ def ineligible(plan, gaussians, cams, background, pipe, bucket, banks) -> Option
         return "data-parallel steps take the Python path"
     if getattr(pipe, "debug", False):
         return "pipe.debug"
-    if banks:
-        return "a camera bank among the views"
     if plan.factored == "gathered":
         return "gathered view tables"
     if not cams or gaussians._xyz.shape[0] == 0:
@@ -107,9 +122,12 @@ def ineligible(plan, gaussians, cams, background, pipe, bucket, banks) -> Option
         return "grad mode is off"
     if not _fused._grads_in_place(_leaves(gaussians)):
         return "a parameter's .grad does not alias the optimizer's gradient buffer"
+    dev = gaussians._xyz.device
     for c in cams:
-        if _cam_fields(c) is None:
-            return "a camera whose tensors are trained or composed per access, or ground truth that is not plain fp32 device data"
+        if _cam_fields(c, dev) is None:
+            return ("a camera that is neither constant nor a camera of a fused bank on the model's device (a bank with "
+                    "fused=False or on another device, a TrainableCamera, leaf tensors that require grad), or ground truth "
+                    "that is not plain fp32 device data")
     return None
 
 
@@ -140,6 +158,15 @@ class _Slot:
         self.maps = torch.empty((9, H, W), **f32)
         self.sums = torch.empty(_lib.loss_sums_floats(W, H), **f32)
         self.cap, self.bin, self.scratch = None, None, None
+        # a view through a training bank camera (ghr_view_step_camera): its composed row, its folded gradients, its partial table
+        self.cam_slots = int(_lib.lib().ghr_camera_slots(P))
+        self.out_row = torch.empty((_lib.CAMERA_OUT,), **f32)
+        self.d_cam = torch.empty((_lib.CAM_GRADS,), **f32)
+        self.cam_partial = torch.empty((_lib.CAM_PARTIALS, self.cam_slots), **f32)
+        self.campos = self.out_row[48:51]
+        c = self.cam_args = _lib.ViewCameraArgs()
+        c.out_row, c.d_cam = self.out_row.data_ptr(), self.d_cam.data_ptr()
+        c.const_stride = _lib.CAMERA_CONST
         a = self.args = _lib.ViewStepArgs()
         m = a.model
         m.P, m.W, m.H, m.sh_coeffs = P, W, H, K
@@ -149,6 +176,25 @@ class _Slot:
         a.render, a.d_pix = self.render.data_ptr(), self.d_pix.data_ptr()
         a.maps, a.sums = self.maps.data_ptr(), self.sums.data_ptr()
         self.step_id = -1
+
+    def set_camera(self, ptrs, bank, index):
+        """Where the view's model reads its camera: the three constant tensors, or -- a training bank's row -- this slot's
+        ``out_row``, with the partial table its backward fills."""
+        m = self.args.model
+        if bank is None:
+            m.viewmatrix, m.projmatrix, m.campos = ptrs
+            m.fovx_dev = m.fovy_dev = m.cam_partial = None
+            m.cam_slots = 0
+            return
+        row = self.out_row.data_ptr()
+        m.viewmatrix, m.projmatrix, m.campos = row, row + 4 * 16, row + 4 * 48
+        m.fovx_dev, m.fovy_dev = row + 4 * 51, row + 4 * 52
+        m.cam_partial, m.cam_slot0, m.cam_slots = self.cam_partial.data_ptr(), 0, self.cam_slots
+        m.tan_fovx = m.tan_fovy = 1.0  # (ignored: the kernels take tan(FoV / 2) of the device scalars)
+        c = self.cam_args
+        c.parametrisation, c.rows, c.index = bank.parametrisation, len(bank), index
+        c.consts, c.params, c.param_stride = bank.consts.data_ptr(), bank.params.data_ptr(), bank.width
+        c.grads, c.grad_stride, c.touched, c.train_mask = bank.grads.data_ptr(), bank.width, bank.touched.data_ptr(), bank.train_mask
 
     def set_capacity(self, cap, dev):
         """Binning workspace and gradient lines on the capacity grid: re-made only when the guess moves to another grid point."""
@@ -258,7 +304,7 @@ class NativeViews:
             for i, (cam, ctx) in enumerate(zip(cams, on_stream)):
                 with ctx:
                     stream = _dgr._stream()
-                    cf = _cam_fields(cam)
+                    cf = _cam_fields(cam, dev)
                     slot = self._slot(stream.value or 0, P, cf.W, cf.H, K)
                     slot.set_capacity(cap, dev)
                     a = slot.args
@@ -278,8 +324,10 @@ class NativeViews:
                         a.grad_loss, a.prezero = self.one.data_ptr(), prezero
                     # ---- this view: camera, ground truth (+ its cached SSIM moments), where its outputs go
                     pv, pp, pc, gi, gm, ga, gc = cf.ptrs
-                    m.viewmatrix, m.projmatrix, m.campos = pv, pp, pc
-                    m.tan_fovx, m.tan_fovy = _tan_half(cam.FoVx), _tan_half(cam.FoVy)
+                    bank = cf.bank
+                    slot.set_camera((pv, pp, pc), bank, getattr(cam, "index", None))
+                    if bank is None:
+                        m.tan_fovx, m.tan_fovy = _tan_half(cf.fov[0]), _tan_half(cf.fov[1])
                     l.gt_image, l.gt_mask = gi, gm
                     l.gt_orient_angle, l.gt_orient_conf = (ga, gc) if orient else (None, None)
                     stats = _gt_stats(cam, cf.tensors[3], cf.tensors[4], True)
@@ -289,6 +337,7 @@ class NativeViews:
                     a.loss_out = row_ptr + 4 * i
                     a.count_event = int(self.count_events[i].cuda_event)
                     # ---- the optimizer's side of a direct backward (the last view's applies the update of a fused step)
+                    # (a bank camera's centre does not exist yet: the call composes it)
                     h = sink.open_view(bool(fuse) and i == n - 1, cf.tensors[2])
                     # a step whose LAST backward carries the update: every view checks its instance count on the device
                     m.dens_img_ws = a.img_ws if h.check_overflow or dens_ptrs is not None else None
@@ -302,7 +351,16 @@ class NativeViews:
                     acc_event = self.acc_events[i] if sink.concurrent else None
                     a.acc_wait_event = None if h.wait_event is None else int(h.wait_event.cuda_event)
                     a.acc_record_event = None if acc_event is None else int(acc_event.cuda_event)
-                    _lib.check(lib.ghr_view_step(stream, ctypes.byref(a)))
+                    if bank is None:
+                        _lib.check(lib.ghr_view_step(stream, ctypes.byref(a)))
+                    else:
+                        _lib.check(lib.ghr_view_step_camera(stream, ctypes.byref(a), ctypes.byref(slot.cam_args)))
+                        if h.d_rgb is not None:
+                            # the centre behind the view's dL/d(rgb) table, now that it is composed; whoever folds the table
+                            # waits for the event behind it
+                            sink.write_view_campos(slot.campos)
+                            if acc_event is not None:
+                                acc_event.record()
                     slot.img_complete = True
                     sink.close_view(h, acc_event)
                     losses.append(row[i])

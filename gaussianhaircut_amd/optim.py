@@ -397,15 +397,22 @@ class FusedAdam:
     def views_open(self) -> bool:  # a direct backward is to leave its SH gradients in a view slot (next_view_slot)
         return self._views is not None
 
-    def next_view_slot(self, campos: torch.Tensor):
-        """Device pointer of the next free d_rgb table of the step; the view's camera centre goes behind it."""
+    def next_view_slot(self, campos: Optional[torch.Tensor]):
+        """Device pointer of the next free d_rgb table of the step; the view's camera centre goes behind it (``campos`` None: the
+        caller writes it with ``write_view_campos`` once it exists)."""
         v = self._views
         i = v["next"]
         if i >= v["buf"].shape[0]:
             raise RuntimeError("FusedAdam: more backward passes than view slots in this step (%d)" % v["buf"].shape[0])
         v["next"] = i + 1
-        v["buf"][i, 3 * v["P"]: 3 * v["P"] + 3].copy_(campos.detach().reshape(3).to(torch.float32))
+        if campos is not None:
+            self.write_view_campos(campos)
         return ctypes.c_void_p(v["buf"].data_ptr() + 4 * i * v["stride"])
+
+    def write_view_campos(self, campos: torch.Tensor):
+        """The camera centre of the view slot handed out last, behind its table (a copy on the current stream)."""
+        v = self._views
+        v["buf"][v["next"] - 1, 3 * v["P"]: 3 * v["P"] + 3].copy_(campos.detach().reshape(3).to(torch.float32))
 
     def fold_own_views(self):
         """``gather=False``: this rank's filled slots folded into the SH ranges of the gradient buffer (no-op without any)."""
@@ -477,7 +484,10 @@ class FusedAdam:
     def set_concurrent(self, on: bool):
         self.concurrent = bool(on)
 
-    def open_view(self, carries: bool, campos: torch.Tensor) -> ViewHandOff:
+    def open_view(self, carries: bool, campos: Optional[torch.Tensor]) -> ViewHandOff:
+        """``campos`` None: the view composes its camera centre itself, after this call (a bank camera of the native step).  When
+        the hand-off carries a ``d_rgb`` table the caller then writes the centre with ``write_view_campos`` behind the view's
+        kernels, in front of the event it passes to ``close_view``."""
         adam_fuse = self.fused_step_args()
         carries = bool(carries) and adam_fuse is not None
         # the step's first gradients into a buffer that is known to hold zeros are assigned, not added

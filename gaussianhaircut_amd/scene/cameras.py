@@ -161,6 +161,29 @@ def compose_camera_torch(use_barf, consts, rotation_res, translation_res, fov_re
     return view, full, center, fov[0], fov[1], proj
 
 
+@torch.no_grad()
+def pack_row_message_torch(grads, touched, message):
+    """``k_cam_pack`` in PyTorch ops: ``message [N, width + 1]`` from ``grads [N, width]`` and ``touched [N]``."""
+    W = grads.shape[1]
+    t = touched != 0
+    message[:, :W] = torch.where(t[:, None], grads, torch.zeros_like(grads))   # (selected, not multiplied: a stale NaN is dropped)
+    message[:, W] = t.to(message.dtype)
+    return message
+
+
+@torch.no_grad()
+def merge_ranks_torch(gathered, grads, touched):
+    """``k_cam_merge`` in PyTorch ops: the ranks' messages ``gathered [G, N, width + 1]`` into ``grads`` / ``touched``, in place."""
+    W = grads.shape[1]
+    acc, seen = grads.clone(), torch.zeros_like(touched, dtype=torch.bool)
+    for q in range(gathered.shape[0]):
+        val, tq = gathered[q, :, :W], gathered[q, :, W] != 0
+        acc = torch.where(tq[:, None], torch.where(seen[:, None], acc + val, val), acc)
+        seen |= tq
+    grads.copy_(acc)
+    touched.copy_(torch.where(seen, torch.ones_like(touched), touched))
+
+
 class _BankCompose(torch.autograd.Function):
     """``BankCamera.tensors()`` on a ROCm device: forward = one ghr_camera_compose of the camera's row, backward = one
     ghr_camera_compose_backward that writes into the bank's gradient row.  The only autograd input is the bank's anchor (a
@@ -286,6 +309,7 @@ class CameraBank:
         self._version, self.live = 0, True
         self.opt = None
         self._lr = (0.0, 0.0, 0.0)
+        self.replicated, self._group, self._message = False, None, None
 
     def __len__(self):
         return len(self._cams)
@@ -403,7 +427,9 @@ class CameraBank:
         if self.opt is None:
             raise RuntimeError("CameraBank.training_setup(opt, spatial_lr_scale) has not been called")
         if iteration >= self.iterations_cam or not self.train_mask or not len(self):
-            return
+            return  # (decided from the iteration and the configuration alone: every rank of a replicated bank returns alike)
+        if self.replicated:
+            self.exchange_gradients()
         lr = tuple(float(x) for x in (lrs if lrs is not None else self.learning_rates(iteration)))
         self._lr = lr
         if self.fused:
@@ -441,6 +467,74 @@ class CameraBank:
         self.steps.copy_(steps)
         self.grads.copy_(torch.where(t[:, None], torch.zeros_like(g), g))
         self.touched.zero_()
+
+    # ---- one bank on every rank (view-parallel training) ---------------------------------------------------------------------------
+    def replicate(self, group=None):
+        """Makes this bank one replica of a bank that every rank of ``group`` holds; returns ``self``.  One small object collective
+        checks that all ranks hold the same number of cameras, parametrisation, ``train_mask`` and image names (``ValueError``
+        otherwise); then rank 0's ``params``, ``exp_avg``, ``exp_avg_sq`` and ``steps`` are broadcast (DDP's rule).  From here on
+        ``step()`` starts with ``exchange_gradients()`` and ``trainer.training_step(camera_bank=...)`` takes the bank on more than
+        one rank.  Every rank then calls ``step()`` in every iteration, also a rank without a view."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            raise RuntimeError("CameraBank.replicate: torch.distributed is not initialised")
+        G = dist.get_world_size(group)
+        mine = (len(self), self.parametrisation, self.train_mask, [c.image_name for c in self._cams])
+        every = [None] * G
+        dist.all_gather_object(every, mine, group=group)
+        for r, other in enumerate(every):
+            if other != every[0]:
+                what = [n for n, a, b in zip(("number of cameras", "parametrisation", "train_mask", "image names"), other, every[0])
+                        if a != b]
+                raise ValueError("CameraBank.replicate: rank %d's bank differs from rank 0's in %s" % (r, ", ".join(what)))
+        src = 0 if group is None else dist.get_global_rank(group, 0)
+        with torch.no_grad():
+            for t in (self.params, self.exp_avg, self.exp_avg_sq, self.steps):
+                dist.broadcast(t, src=src, group=group)
+        self.replicated, self._group, self._message = True, group, None
+        self._version += 1
+        return self
+
+    @torch.no_grad()
+    def exchange_gradients(self):
+        """The gradient rows of all ranks of a replicated bank, merged into every replica's ``grads`` / ``touched``; a collective:
+        every rank calls it (``step()`` does, first thing), also one whose views touched no row.
+
+        *Pack*: ``[N, width + 1]``: a touched row is its gradient row followed by ``1.0``, an untouched row all zeros -- stale
+        contents of ``grads``, a stale NaN included, never travel.  *Gather*: one ``all_gather_into_tensor`` to ``[G, N, width +
+        1]`` (at most 48 B per camera and rank).  *Merge*: per row and column the ranks are walked in ascending order; the first
+        touched rank's value is assigned, later touched ranks' values are added in that order; ``touched[row]`` becomes 1 if any
+        rank touched the row; rows no rank touched are left exactly as they are.  Pack and merge are one launch each on a fused
+        bank (``k_cam_pack``, ``k_cam_merge``), the same rule in PyTorch ops otherwise.
+
+        Consequences: a row touched by exactly one rank arrives with that rank's bits, so the viewed cameras of a step from equal
+        state equal a one-rank step over the same global views bit for bit.  The same camera viewed on two ranks is DEFINED as the
+        sum in rank order (on one rank two views of one camera stay refused -- two streams would race for the row; across ranks
+        there is no race).  ``step()``'s NaN rule sees the same rows on every rank, so all ranks skip or step alike, and replicas
+        that were bit-identical stay so."""
+        import torch.distributed as dist
+        if not self.replicated:
+            raise RuntimeError("CameraBank.exchange_gradients: the bank is not replicated (CameraBank.replicate)")
+        N, W = len(self), self.width
+        if N == 0:
+            return
+        G = dist.get_world_size(self._group)
+        if self._message is None or self._message[1].shape[0] != G:
+            self._message = (torch.empty(N, W + 1, device=self.params.device), torch.empty(G, N, W + 1, device=self.params.device))
+        msg, gathered = self._message
+        if self.fused:
+            from .. import _lib
+            from ..diff_gaussian_rasterization import _on_device, _stream
+            vp = lambda t: ctypes.c_void_p(t.data_ptr())
+            with _on_device(self.params.device):
+                _lib.check(_lib.lib().ghr_camera_pack_row_message(_stream(), N, W, vp(self.grads), W, vp(self.touched), vp(msg)))
+                dist.all_gather_into_tensor(gathered.view(-1), msg.view(-1), group=self._group)
+                _lib.check(_lib.lib().ghr_camera_merge_ranks(_stream(), N, W, G, vp(gathered), vp(self.grads), W,
+                                                             vp(self.touched)))
+            return
+        pack_row_message_torch(self.grads, self.touched, msg)
+        dist.all_gather_into_tensor(gathered.view(-1), msg.view(-1), group=self._group)
+        merge_ranks_torch(gathered, self.grads, self.touched)
 
     # ---- persistence --------------------------------------------------------------------------------------------------------
     def state_dict(self):

@@ -354,7 +354,9 @@ def training_step(gaussians, cams: List, background, opt, iteration: int, bucket
     view, all-gathered; ``FusedAdam.begin_factored_views``) instead of summing 192 B per Gaussian: every rank opens that many
     slots, and a rank with more views than slots fails loudly before any collective.
 
-    ``camera_bank`` (a ``scene.cameras.CameraBank`` after ``training_setup``; one rank): the step's views are cameras of the bank
+    ``camera_bank`` (a ``scene.cameras.CameraBank`` after ``training_setup``; on more than one rank a bank that every rank
+    ``replicate()``-d: its ``step`` merges the ranks' gradient rows first, on every rank, also one without views -- a bank that was
+    not replicated raises ``NotImplementedError`` there): the step's views are cameras of the bank
     and the cameras are trained with the Gaussians, in the reference's order (src/train_gaussians.py:183-196): every view's
     backward leaves dL/d(residuals) in its camera's gradient row, and after the Gaussians' update -- every stream of the step
     joined -- ``camera_bank.step(iteration)`` steps the viewed cameras in one launch.  The views must be DISTINCT cameras (their
@@ -367,7 +369,9 @@ def training_step(gaussians, cams: List, background, opt, iteration: int, bucket
     struct that are allocated once (``native_step``), instead of two ``autograd.Function`` round trips, six calls and a dozen
     ``torch.empty`` per view.  Same parameters, moments, flags, statistics and loss, bit for bit.  Eligible is a step on one rank
     whose views all take the fused renderer's direct backward with deferred counts (the default of this function on a ROCm
-    device), through constant cameras (no trained camera tensor, no camera bank), without ``pipe.debug``; streams, the per-view SH
+    device), through constant cameras or cameras of a fused ``CameraBank`` on the model's device (while the bank trains such a view
+    is ``ghr_view_step_camera``: compose, the view, the camera gradients' fold and the compose's backward in one call; no trained
+    camera tensor, no ``TrainableCamera``, no bank with ``fused=False``), without ``pipe.debug``; streams, the per-view SH
     tables, ``densify_stats`` and the update inside the last backward work as they do here.  Anything else takes the path above
     untouched -- with ``native=True`` it raises instead.  A step without a capacity guess yet (the first one, or the first after
     the model changed size) has to wait for its instance count and runs the Python way, whatever ``native`` says;
@@ -387,7 +391,8 @@ def training_step(gaussians, cams: List, background, opt, iteration: int, bucket
 
 
 def last_step_path() -> str:
-    """``"native"`` when the views of the last ``training_step`` ran as ``ghr_view_step`` calls, ``"python"`` otherwise."""
+    """``"native"`` when the views of the last ``training_step`` ran as ``ghr_view_step`` / ``ghr_view_step_camera`` calls,
+    ``"python"`` otherwise."""
     return _LAST_STEP_PATH
 
 
@@ -450,10 +455,11 @@ def _training_step(gaussians, cams, background, opt, iteration, bucket, global_v
 def _check_bank_views(bank, cams):
     """The banks among a step's views (``bank``, the one to be stepped, first).  Views that are cameras of a bank must be DISTINCT
     cameras of it, whether the step also steps that bank or not: two views of one camera would read-modify-write the same gradient
-    row and touched mark from two streams.  With ``bank``: one rank, and every view is a camera of it."""
-    if bank is not None and _world_size() > 1:
+    row and touched mark from two streams.  With ``bank``: every view is a camera of it; on more than one rank it must be a
+    replicated bank (``CameraBank.replicate``: its ``step`` merges the ranks' gradient rows first)."""
+    if bank is not None and _world_size() > 1 and not getattr(bank, "replicated", False):
         raise NotImplementedError("training_step(camera_bank=...) on more than one rank: replicating the camera updates across "
-                                  "ranks is not implemented")
+                                  "ranks is not implemented for a bank that was not replicated (CameraBank.replicate)")
     banks, seen = ([] if bank is None else [bank]), set()
     for c in cams:
         b = getattr(c, "bank", None)

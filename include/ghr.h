@@ -426,7 +426,8 @@ typedef struct ghr_sh_fold_args {   /* the arguments of ghr_sh_grad_from_views w
     int32_t accumulate;
 } ghr_sh_fold_args;
 typedef struct ghr_view_step_args {
-    /* mode 0, row0 0, P > 0, debug 0, no camera gradients (cam_partial, fovx_dev / fovy_dev NULL).  Forward fields and backward
+    /* mode 0, row0 0, P > 0, debug 0, no camera gradients (cam_partial, fovx_dev / fovy_dev NULL) -- ghr_view_step_camera below
+     * takes the same struct WITH them, for a camera that is a row of a bank.  Forward fields and backward
      * fields both filled: dens_* / dens_img_ws / overflow_raises_flag / adam_fuse / d_rgb / img_ws_recycled mean what they mean
      * for the single calls (dens_img_ws, when set, must be img_ws below). */
     ghr_model_args model;
@@ -635,6 +636,47 @@ int ghr_camera_compose_backward(void* stream, int32_t parametrisation, int32_t r
 int ghr_camera_adam_step(void* stream, int32_t parametrisation, int32_t n, float* params, float* grads, float* exp_avg,
                          float* exp_avg_sq, int32_t stride, int32_t* steps, int32_t* touched, float lr_rotation,
                          float lr_translation, float lr_fov, double beta1, double beta2, float eps, int32_t train_mask);
+
+/* ---- a training view whose camera is a row of a bank: ghr_view_step with the camera chain around it -----------------------------
+ * Added without an ABI_VERSION bump: three new functions and one new struct, no existing struct or signature changed.
+ * ghr_view_step_camera enqueues, on the caller's one stream, in this order:
+ *   1. ghr_camera_compose(index, 1) into out_row;
+ *   2. what ghr_view_step enqueues for `v`, whose model reads the camera from out_row and writes the camera-gradient partial table:
+ *      v->model.viewmatrix = out_row, projmatrix = out_row + 16, campos = out_row + 48, fovx_dev = out_row + 51, fovy_dev =
+ *      out_row + 52 (the row layout above); cam_partial set, cam_slot0 = 0 ... cam_slots == ghr_camera_slots(P);
+ *   3. ghr_camera_grad_fold of that table into d_cam;
+ *   4. ghr_camera_compose_backward(index, 1) with d view = d_cam, d full = d_cam + 16, d centre = d_cam + 32, d FoVx = d_cam + 35,
+ *      d FoVy = d_cam + 36 and d proj NULL: the row's gradient in `grads`, its touched mark up.
+ * It calls those functions -- the same kernels, launch shapes and arguments as the four calls one after the other.  Both structs
+ * are validated first: a refused call has launched nothing and ghr_last_error() names the field.  ghr_view_step itself keeps
+ * refusing camera gradients.  Views that may run concurrently must be distinct rows of the bank. */
+typedef struct ghr_view_camera_args {
+    int32_t parametrisation;   /* GHR_CAMERA_ORTHO6D / GHR_CAMERA_SE3 */
+    int32_t rows;              /* cameras the bank's buffers hold */
+    int32_t index;             /* this view's camera: 0 .. rows - 1 */
+    int32_t const_stride;
+    const float* consts;
+    const float* params;
+    int32_t param_stride;
+    int32_t grad_stride;
+    float* grads;
+    int32_t* touched;
+    int32_t train_mask;        /* != 0: a bank with both groups frozen is a constant camera (ghr_view_step) */
+    float* out_row;            /* caller-owned, GHR_CAMERA_OUT floats: the composed camera the view reads */
+    float* d_cam;              /* caller-owned, GHR_CAM_GRADS floats: the folded camera gradients */
+} ghr_view_camera_args;
+int ghr_view_step_camera(void* stream, const ghr_view_step_args* v, const ghr_view_camera_args* c);
+
+/* The exchange of a replicated bank's gradient rows between G ranks (width: 8 (se(3)) or 11 (ortho-6D) floats of gradient per row).
+ * ghr_camera_pack_row_message: message [n][width + 1]: a touched row is its gradient row followed by 1.0f, an untouched row all
+ * zeros (whatever `grads` holds there -- a stale NaN included -- does not travel).
+ * ghr_camera_merge_ranks: gathered [G][n][width + 1], the ranks' messages in ascending rank order.  Per row and column the first
+ * touched rank's value is ASSIGNED to `grads`, later touched ranks' values are added in that order; touched[row] = 1 if any rank
+ * touched it; a row no rank touched is neither read nor written.  A row touched by exactly one rank arrives with that rank's bits. */
+int ghr_camera_pack_row_message(void* stream, int32_t n, int32_t width, const float* grads, int32_t grad_stride,
+                                const int32_t* touched, float* message);
+int ghr_camera_merge_ranks(void* stream, int32_t n, int32_t width, int32_t G, const float* gathered, float* grads,
+                           int32_t grad_stride, int32_t* touched);
 
 /* ---- ground-truth orientation maps from an image (src/preprocessing/calc_orientation_maps.py; loader: src/utils/camera_utils.py:66-68)
  * Added without an ABI_VERSION bump: five new functions, no existing struct or signature changed.

@@ -1,10 +1,12 @@
 """One mode of the configs[2] step, alone, for rocprofv3 --kernel-trace --stats (round 6):
-    python tools/camstep.py plain|leaf|residual|fixed|bank [steps]
+    python tools/camstep.py plain|leaf|residual|fixed|bank|bank-native [steps]
 plain = bench.py's headline (16 cycling cameras), fixed = camera 0 only, leaf = the five camera tensors are leaves that
 require grad, residual = scene.cameras.TrainableCamera + torch.optim.Adam over the camera parameters, bank = the same 16 ring
-cameras as one scene.cameras.CameraBank(use_barf=True) and training_step(camera_bank=bank).
+cameras as one scene.cameras.CameraBank(use_barf=True) and training_step(camera_bank=bank) on the Python path (native=False),
+bank-native = the same with native=True (one ghr_view_step_camera per view).
     python tools/camstep.py compare [steps]
-runs leaf, residual, bank, bank alternately in ONE process, twice: the first pass of each is warm-up, the second is printed."""
+runs the four forms leaf, residual, bank, bank-native alternately in ONE process: a warm-up pass of each, then three printed
+rounds (the spread between the rounds of one form is the noise a difference between two forms has to exceed)."""
 import copy
 import os
 import sys
@@ -25,14 +27,14 @@ def main():
     mode = sys.argv[1] if len(sys.argv) > 1 else "plain"
     K = int(sys.argv[2]) if len(sys.argv) > 2 else 30
     if mode == "compare":
-        for rep in range(2):
-            for m in ("leaf", "residual", "bank", "bank"):
-                run(m, K, report=rep == 1)
+        for rep in range(4):
+            for m in ("leaf", "residual", "bank", "bank-native"):
+                run(m, K, report=rep > 0, tag=" round %d" % rep)
         return
     run(mode, K)
 
 
-def run(mode, K, report=True):
+def run(mode, K, report=True, tag=""):
     dev = torch.device("cuda:0")
     spec = syn.CONFIGS[os.environ.get("CAMSTEP_CFG", "cfg3")]
     opt = OptimizationParams()
@@ -48,9 +50,9 @@ def run(mode, K, report=True):
         del gt
     model.training_setup(opt)
     after, kw = None, {}
-    if mode == "bank":
+    if mode in ("bank", "bank-native"):
         bank = CameraBank(pool, use_barf=True, device=dev).training_setup(opt)
-        pool, kw = list(bank), dict(camera_bank=bank)
+        pool, kw = list(bank), dict(camera_bank=bank, native=mode == "bank-native")
     if mode == "fixed":
         pool = pool[:1]
     if mode == "leaf":
@@ -90,7 +92,8 @@ def run(mode, K, report=True):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     if report:
-        print("CAMSTEP %s: %.4f ms per step over %d steps (host issue time %.4f ms per step)" % (mode, 1e3 * dt / K, K, 1e3 * t_issue / K))
+        print("CAMSTEP %s%s: %.4f ms per step over %d steps (host issue time %.4f ms per step)" %
+              (mode, tag, 1e3 * dt / K, K, 1e3 * t_issue / K))
 
 
 if __name__ == "__main__":
