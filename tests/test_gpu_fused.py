@@ -8,11 +8,10 @@ import torch
 
 from gaussianhaircut_amd.gaussian_renderer import render
 from gaussianhaircut_amd.utils import synthetic as syn
+from tests.projection_shared import FUSED, GENERIC, _pixel_mask, _trainable_camera
 
 pytestmark = pytest.mark.gpu
 
-FUSED = SimpleNamespace(debug=False, fused_projection=True)
-GENERIC = SimpleNamespace(debug=False, fused_projection=False)
 
 
 def _model(spec, dev, deg, max_deg=3):
@@ -36,20 +35,6 @@ def _run(spec, pipe, dev, weights, deg, max_deg=3):
         grads[n] = t.grad.detach().cpu().numpy()
     grads["viewspace"] = pkg["viewspace_points"].grad.detach().cpu().numpy()
     return pkg, grads
-
-
-def _pixel_mask(state, H, W, radii_a, radii_b, means2d):
-    """Pixels left out of a comparison between two chains, EXPLICITLY: the oracle's fragile pixels (a discrete decision
-    -- alpha >= 1/255, T < 1e-4 -- within 2e-5 of its threshold) and a box around every Gaussian whose radius differs
-    between the chains (differently rounded projection arithmetic may flip the ceil): its 3-sigma square + one tile.
-    Returns (mask [H, W] bool, number of flipped Gaussians)."""
-    mask = np.asarray(state.fragile).reshape(H, W).astype(bool).copy()
-    flipped = np.nonzero(np.asarray(radii_a) != np.asarray(radii_b))[0]
-    for i in flipped:
-        r = int(max(radii_a[i], radii_b[i])) + 17
-        x, y = float(means2d[i, 0]), float(means2d[i, 1])
-        mask[max(0, int(y) - r):int(y) + r + 1, max(0, int(x) - r):int(x) + r + 1] = True
-    return mask, int(flipped.size)
 
 
 def _assert_rows_close(name, a, b, tol=1e-4, floor=1e-5):
@@ -672,18 +657,6 @@ def test_sh_gradients_rebuilt_from_per_view_factors_equal_the_accumulated_ones(c
         assert int(o.state_dev[1]) == 1
     finally:
         _lib.lib().ghr_set_deterministic(0)
-
-
-def _trainable_camera(spec, dev):
-    """A camera whose pose and FoV are being optimised, like the reference's (src/scene/cameras.py:83-151): the view
-    matrix is a leaf, the full projection / centre are functions of it, the FoV tensors are leaves."""
-    cam = syn.make_view(spec, dev)
-    cam.world_view_transform = cam.world_view_transform.clone().requires_grad_(True)
-    cam.full_proj_transform = cam.world_view_transform @ cam.projection_matrix
-    cam.camera_center = torch.inverse(cam.world_view_transform)[3, :3]
-    cam.FoVx = cam.FoVx.clone().requires_grad_(True)
-    cam.FoVy = cam.FoVy.clone().requires_grad_(True)
-    return cam
 
 
 def test_trainable_camera_takes_the_fused_path_and_keeps_its_gradients(monkeypatch):

@@ -16,7 +16,6 @@ K1 state bit for bit (depth keys, pixel means) or to 1e-5 (conic, opacity), the 
 (oracle/ghr_oracle64.c): |HIP - f64| <= 3 |oracle32 - f64| + the row criterion, for every element.
 """
 import math
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -25,19 +24,9 @@ import torch
 from gaussianhaircut_amd.gaussian_renderer import _package, render
 from gaussianhaircut_amd.utils import synthetic as syn
 from tests import helpers as hp
+from tests.projection_shared import FLOOR, FUSED, GENERIC, PARAMS, _row_close
 
 pytestmark = pytest.mark.gpu
-
-FUSED = SimpleNamespace(debug=False, fused_projection=True)
-GENERIC = SimpleNamespace(debug=False, fused_projection=False)
-PARAMS = ("_xyz", "_scaling", "_rotation", "_opacity", "_label", "_orient_conf", "_features_dc", "_features_rest")
-FLOOR = 2e-6  # of the tensor's largest |ref|: fp32 cancellation noise of rows whose own gradient is ~0
-
-
-def _row_close(a, b, tol=hp.TOL, floor=FLOOR):
-    a, b = a.reshape(len(a), -1), b.reshape(len(b), -1)
-    rows = np.abs(b).max(axis=1, keepdims=True)
-    return np.abs(a - b) <= tol * (np.abs(b) + rows) + floor * np.abs(b).max()
 
 
 def _assert_rows(name, a, b, tol=hp.TOL, floor=FLOOR):
