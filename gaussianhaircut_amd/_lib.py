@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GHR_LIB_PATH") or os.path.join(CSRC, "libghr_hip.so")  # override: kernel experiments
 SOURCES = ["ghr_capi.hip"]
 HEADERS = ["ghr_device.h", "ghr_preprocess.h", "ghr_binning.h", "ghr_render_fwd.h", "ghr_render_bwd.h", "ghr_render_bwd2.h", "ghr_render_bwd3.h",
-           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_products.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_meshdist.h", "ghr_tilelists.h", "ghr_visibility.h", "ghr_strandview.h", "ghr_sds.h", "ghr_nn.h", "ghr_compare.h", "ghr_texstrands.h", "ghr_guides.h"]
+           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_products.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_meshdist.h", "ghr_tilelists.h", "ghr_visibility.h", "ghr_strandview.h", "ghr_sds.h", "ghr_nn.h", "ghr_compare.h", "ghr_texstrands.h", "ghr_guides.h", "ghr_haar.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-fPIC",
                "-shared"]
 

@@ -2679,6 +2679,7 @@ int ghr_strandview_shade_shadowed(void* stream, int32_t S, int32_t L, const floa
 
 // ---- the strand stage's prior term: guiding strands' local frames and the latent texture (include/ghr.h; csrc/ghr_sds.h) ------
 namespace {
+// one wave per item, here and for the guiding strands of the generator below (both launch csrc/ghr_haar.h's kernels)
 inline unsigned sds_blocks(int64_t waves) { return (unsigned)((waves + GHR_SDS_BLOCK / GHR_SDS_WAVE - 1) / (GHR_SDS_BLOCK / GHR_SDS_WAVE)); }
 
 // the sizes every entry shares, before anything touches the runtime; S < 0: not checked (the texture has no S)
@@ -2743,15 +2744,14 @@ int ghr_sds_texture(void* stream, int32_t N, int32_t n, int32_t C, int32_t G, co
     if (!nbr || !w || !csim || !alpha || !alpha_q || !count || !start || !list) return lt_bad(fn, "a saved-state buffer is NULL");
     if (!texture) return lt_bad(fn, "texture is NULL");
     hipStream_t s = (hipStream_t)stream;
-    ghr::SdsTexArgs a{};
-    a.N = N; a.n = n; a.C = C; a.G = G; a.uvg = uvg; a.centres = centres; a.z = z; a.v = v;
+    ghr::HaarArgs a{};
+    a.Q = G * G; a.N = N; a.n = n; a.C = C; a.G = G; a.uvg = uvg; a.centres = centres; a.z = z; a.v = v;
     a.nbr = nbr; a.w = w; a.csim = csim; a.alpha = alpha; a.alpha_q = alpha_q; a.count = count; a.start = start; a.list = list;
-    a.texture = texture;
-    const int64_t GG = (int64_t)G * G;
+    a.out = texture;
     GHR_HIP(hipMemsetAsync(count, 0, sizeof(int32_t) * (size_t)N, s));
-    hipLaunchKernelGGL(ghr::k_sds_knn, dim3(sds_blocks(GG)), dim3(GHR_SDS_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_haar_knn<ghr::HaarTexels>, dim3(sds_blocks(a.Q)), dim3(GHR_SDS_BLOCK), 0, s, a);
     hipLaunchKernelGGL(ghr::k_sds_lists, dim3(sds_blocks(N)), dim3(GHR_SDS_BLOCK), 0, s, a);
-    hipLaunchKernelGGL(ghr::k_sds_blend, dim3(sds_blocks(GG)), dim3(GHR_SDS_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_haar_blend<ghr::HaarTexels>, dim3(sds_blocks(a.Q)), dim3(GHR_SDS_BLOCK), 0, s, a);
     return finish(s, 0);
 }
 
@@ -2768,15 +2768,14 @@ int ghr_sds_texture_backward(void* stream, int32_t N, int32_t n, int32_t C, int3
     if (!dalpha_q || !d_csim) return lt_bad(fn, "dalpha_q or d_csim is NULL");
     if (!d_z) return lt_bad(fn, "d_z is NULL");
     hipStream_t s = (hipStream_t)stream;
-    ghr::SdsTexArgs a{};
-    a.N = N; a.n = n; a.C = C; a.G = G; a.z = z; a.v = v;
+    ghr::HaarArgs a{};
+    a.Q = G * G; a.N = N; a.n = n; a.C = C; a.G = G; a.z = z; a.v = v;
     a.nbr = const_cast<int32_t*>(nbr); a.w = const_cast<float*>(w); a.csim = const_cast<float*>(csim);
     a.alpha_q = const_cast<float*>(alpha_q); a.start = const_cast<int32_t*>(start); a.list = const_cast<int32_t*>(list);
-    a.d_texture = d_texture; a.dalpha_q = dalpha_q; a.d_csim = d_csim; a.d_z = d_z; a.d_v = d_v;
-    const int64_t GG = (int64_t)G * G;
-    hipLaunchKernelGGL(ghr::k_sds_bwd_texel, dim3(sds_blocks(GG)), dim3(GHR_SDS_BLOCK), 0, s, a);
-    hipLaunchKernelGGL(ghr::k_sds_bwd_gather, dim3(sds_blocks(N)), dim3(GHR_SDS_BLOCK), 0, s, a);
-    if (d_v) hipLaunchKernelGGL(ghr::k_sds_bwd_v, dim3(sds_blocks(N)), dim3(GHR_SDS_BLOCK), 0, s, a);
+    a.d_out = d_texture; a.dalpha_q = dalpha_q; a.d_csim = d_csim; a.d_z = d_z; a.d_v = d_v;
+    hipLaunchKernelGGL(ghr::k_haar_dalpha<ghr::HaarTexels>, dim3(sds_blocks(a.Q)), dim3(GHR_SDS_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_haar_gather<ghr::HaarTexels>, dim3(sds_blocks(N)), dim3(GHR_SDS_BLOCK), 0, s, a);
+    if (d_v) hipLaunchKernelGGL(ghr::k_haar_bwd_v<ghr::HaarTexels>, dim3(sds_blocks(N)), dim3(GHR_SDS_BLOCK), 0, s, a);
     return finish(s, 0);
 }
 
@@ -2881,8 +2880,6 @@ int ghr_ts_world_backward(void* stream, int32_t Smax, int32_t S, int32_t n, cons
 
 // ---- guiding strands of the textured generator: neighbours, lists, the HAAR blend (include/ghr.h; csrc/ghr_guides.h) ----------
 namespace {
-inline unsigned gd_blocks(int64_t waves) { return (unsigned)((waves + GHR_GD_BLOCK / GHR_SDS_WAVE - 1) / (GHR_GD_BLOCK / GHR_SDS_WAVE)); }
-
 // the sizes both entries share, before anything touches the runtime
 const char* gd_sizes(int64_t S, int64_t N, int64_t n, int64_t C)
 {
@@ -2907,16 +2904,16 @@ int ghr_guides_blend(void* stream, int32_t S, int32_t N, int32_t n, int32_t C, c
     if (!nbr || !w || !csim || !alpha || !alpha_s || !count || !start || !unsorted || !list) return lt_bad(fn, "a saved-state buffer is NULL");
     if (!z) return lt_bad(fn, "z is NULL");
     hipStream_t s = (hipStream_t)stream;
-    ghr::GdArgs a{};
-    a.S = S; a.N = N; a.n = n; a.C = C; a.uvs = uvs; a.z_g = z_g; a.v_g = v_g;
-    a.nbr = nbr; a.w = w; a.csim = csim; a.alpha = alpha; a.alpha_s = alpha_s; a.count = count; a.start = start;
-    a.unsorted = unsorted; a.list = list; a.z = z;
+    ghr::HaarArgs a{};
+    a.Q = S; a.N = N; a.n = n; a.C = C; a.uvg = uvs; a.z = z_g; a.v = v_g;
+    a.nbr = nbr; a.w = w; a.csim = csim; a.alpha = alpha; a.alpha_q = alpha_s; a.count = count; a.start = start;
+    a.unsorted = unsorted; a.list = list; a.out = z;
     GHR_HIP(hipMemsetAsync(count, 0, sizeof(int32_t) * (size_t)N, s));
-    hipLaunchKernelGGL(ghr::k_gd_knn, dim3(gd_blocks(S)), dim3(GHR_GD_BLOCK), 0, s, a);
-    hipLaunchKernelGGL(ghr::k_gd_blend, dim3(gd_blocks(S)), dim3(GHR_GD_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_haar_knn<ghr::HaarRoots>, dim3(sds_blocks(S)), dim3(GHR_SDS_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_haar_blend<ghr::HaarRoots>, dim3(sds_blocks(S)), dim3(GHR_SDS_BLOCK), 0, s, a);
     hipLaunchKernelGGL(ghr::k_gd_start, dim3(1), dim3(GHR_SDS_WAVE), 0, s, a);
-    hipLaunchKernelGGL(ghr::k_gd_fill, dim3((unsigned)((4ll * S + GHR_GD_BLOCK - 1) / GHR_GD_BLOCK)), dim3(GHR_GD_BLOCK), 0, s, a);
-    hipLaunchKernelGGL(ghr::k_gd_lists, dim3(gd_blocks(N)), dim3(GHR_GD_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_gd_fill, dim3((unsigned)((4ll * S + GHR_SDS_BLOCK - 1) / GHR_SDS_BLOCK)), dim3(GHR_SDS_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_gd_lists, dim3(sds_blocks(N)), dim3(GHR_SDS_BLOCK), 0, s, a);
     return finish(s, 0);
 }
 
@@ -2932,14 +2929,14 @@ int ghr_guides_blend_backward(void* stream, int32_t S, int32_t N, int32_t n, int
     if (!dalpha_s || !d_csim) return lt_bad(fn, "dalpha_s or d_csim is NULL");
     if (!d_zg) return lt_bad(fn, "d_zg is NULL");
     hipStream_t s = (hipStream_t)stream;
-    ghr::GdArgs a{};
-    a.S = S; a.N = N; a.n = n; a.C = C; a.z_g = z_g; a.v_g = v_g;
+    ghr::HaarArgs a{};
+    a.Q = S; a.N = N; a.n = n; a.C = C; a.z = z_g; a.v = v_g;
     a.nbr = const_cast<int32_t*>(nbr); a.w = const_cast<float*>(w); a.csim = const_cast<float*>(csim);
-    a.alpha_s = const_cast<float*>(alpha_s); a.start = const_cast<int32_t*>(start); a.list = const_cast<int32_t*>(list);
-    a.d_z = d_z; a.dalpha_s = dalpha_s; a.d_csim = d_csim; a.d_zg = d_zg; a.d_vg = d_vg;
-    hipLaunchKernelGGL(ghr::k_gd_dalpha, dim3(gd_blocks(S)), dim3(GHR_GD_BLOCK), 0, s, a);
-    hipLaunchKernelGGL(ghr::k_gd_gather, dim3(gd_blocks(N)), dim3(GHR_GD_BLOCK), 0, s, a);
-    if (d_vg) hipLaunchKernelGGL(ghr::k_gd_bwd_v, dim3(gd_blocks(N)), dim3(GHR_GD_BLOCK), 0, s, a);
+    a.alpha_q = const_cast<float*>(alpha_s); a.start = const_cast<int32_t*>(start); a.list = const_cast<int32_t*>(list);
+    a.d_out = d_z; a.dalpha_q = dalpha_s; a.d_csim = d_csim; a.d_z = d_zg; a.d_v = d_vg;
+    hipLaunchKernelGGL(ghr::k_haar_dalpha<ghr::HaarRoots>, dim3(sds_blocks(S)), dim3(GHR_SDS_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_haar_gather<ghr::HaarRoots>, dim3(sds_blocks(N)), dim3(GHR_SDS_BLOCK), 0, s, a);
+    if (d_vg) hipLaunchKernelGGL(ghr::k_haar_bwd_v<ghr::HaarRoots>, dim3(sds_blocks(N)), dim3(GHR_SDS_BLOCK), 0, s, a);
     return finish(s, 0);
 }
 

@@ -2,34 +2,15 @@
 //
 // Compiles gaussianhaircut_amd/csrc/ghr_sds.h as plain C++ for the host and walks the kernels' loops with a 64-lane wave kept in
 // arrays: the same GHR_HD arithmetic, the same split of the work over lanes, the same butterfly and Hillis-Steele orders.
-// Every index a walk forms is checked (SDS_CHECK aborts with the expression).  tests/test_strand_prior_cpu.py loads this as a
-// shared library; ghr_sds_selfcheck.cpp includes it and adds a main().
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+// The texture's neighbours, blend and backward are ghr_hostsim_haar.h's shared walk over the texels; the local frames and
+// k_sds_lists are walked here.  Every index a walk forms is checked (GHR_HAAR_CHECK aborts with the expression).
+// tests/test_strand_prior_cpu.py loads this as a shared library; ghr_sds_selfcheck.cpp includes it and adds a main().
+#include "ghr_hostsim_haar.h"
 #include "../../gaussianhaircut_amd/csrc/ghr_sds.h"
-
-#define SDS_CHECK(cond)                                                                          \
-    do {                                                                                         \
-        if (!(cond)) {                                                                           \
-            std::fprintf(stderr, "ghr_hostsim_sds.cpp:%d: check failed: %s\n", __LINE__, #cond); \
-            std::abort();                                                                        \
-        }                                                                                        \
-    } while (0)
 
 namespace {
 
-constexpr int WV = GHR_SDS_WAVE;
-
-void wave_sum(float* x)  // sds_wave_sum
-{
-    for (int m = 1; m < WV; m <<= 1) {
-        float t[WV];
-        for (int l = 0; l < WV; l++) t[l] = x[l] + x[l ^ m];
-        std::memcpy(x, t, sizeof(t));
-    }
-}
+using ghrsim::WV;
 
 void wave_excl(float* x, int dir)  // sds_wave_excl
 {
@@ -79,7 +60,7 @@ void ghrsim_sds_local(int S, int N, int n, const float* dirs, const float* frame
 {
     for (int g = 0; g < N; g++) {
         const long long s = idx[g];
-        SDS_CHECK(s >= 0 && s < S);
+        GHR_HAAR_CHECK(s >= 0 && s < S);
         float M[9];
         frame(frames, inverse, s, M);
         const float* d = dirs + (size_t)s * n * 3;
@@ -87,12 +68,12 @@ void ghrsim_sds_local(int S, int N, int n, const float* dirs, const float* frame
         int lo[WV], hi[WV];
         for (int l = 0; l < WV; l++) {
             ghr::sds_chunk(n, l, &lo[l], &hi[l]);
-            SDS_CHECK(0 <= lo[l] && lo[l] <= hi[l] && hi[l] <= n && (l == 0 ? lo[l] == 0 : lo[l] == hi[l - 1]));
+            GHR_HAAR_CHECK(0 <= lo[l] && lo[l] <= hi[l] && hi[l] <= n && (l == 0 ? lo[l] == 0 : lo[l] == hi[l - 1]));
             for (int c = 0; c < 3; c++) run[c][l] = 0.f;
             for (int i = lo[l]; i < hi[l]; i++)
                 for (int c = 0; c < 3; c++) run[c][l] += d[i * 3 + c];
         }
-        SDS_CHECK(hi[WV - 1] == n);
+        GHR_HAAR_CHECK(hi[WV - 1] == n);
         for (int c = 0; c < 3; c++) wave_excl(run[c], +1);
         float* eg = e + (size_t)g * (n + 1) * 3;
         float* vg = v + (size_t)g * n * 3;
@@ -117,16 +98,16 @@ void ghrsim_sds_local_backward(int S, int N, int n, const float* frames, int inv
     if (!d_e && !d_v) return;
     for (int p = 0; p < N; p++) {
         const long long s = sidx[p];
-        SDS_CHECK(s >= 0 && s < S);
-        if (p > 0) SDS_CHECK(sidx[p - 1] <= s);
+        GHR_HAAR_CHECK(s >= 0 && s < S);
+        if (p > 0) GHR_HAAR_CHECK(sidx[p - 1] <= s);
         if (p > 0 && sidx[p - 1] == s) continue;
         float M[9];
         frame(frames, inverse, s, M);
         float* out = d_dirs + (size_t)s * n * 3;
         for (int r = p; r < N && sidx[r] == s; r++) {
             const long long g = order[r];
-            SDS_CHECK(g >= 0 && g < N);
-            if (r > p) SDS_CHECK(order[r - 1] < g);  // the sort was stable: ascending g within a run
+            GHR_HAAR_CHECK(g >= 0 && g < N);
+            if (r > p) GHR_HAAR_CHECK(order[r - 1] < g);  // the sort was stable: ascending g within a run
             const float* de = d_e ? d_e + (size_t)g * (n + 1) * 3 : nullptr;
             const float* dv = d_v ? d_v + (size_t)g * n * 3 : nullptr;
             float run[3][WV];
@@ -161,47 +142,11 @@ void ghrsim_sds_texture(int N, int n, int C, int G, const float* uvg, const floa
                         int32_t* list, float* texture)
 {
     const int GG = G * G, total = GHR_SDS_K * GG;
-    SDS_CHECK(N >= GHR_SDS_K && GG >= N && n >= 1 && C >= 1);
-    for (int g = 0; g < N; g++) count[g] = 0;
-    // k_sds_knn
-    for (int q = 0; q < GG; q++) {
-        const float cx = centres[q % G], cy = centres[q / G];
-        std::vector<ghr::SdsTop> t(WV);
-        for (int l = 0; l < WV; l++) {
-            ghr::sds_top_init(t[l]);
-            for (int g = l; g < N; g += WV) ghr::sds_top_insert(t[l], ghr::sds_dist2(cx, cy, uvg[2 * g], uvg[2 * g + 1]), g);
-        }
-        for (int m = 1; m < WV; m <<= 1) {
-            std::vector<ghr::SdsTop> o(t);
-            for (int l = 0; l < WV; l++)
-                for (int k = 0; k < GHR_SDS_K; k++) ghr::sds_top_insert(t[l], o[l ^ m].d[k], o[l ^ m].g[k]);
-        }
-        for (int l = 1; l < WV; l++) SDS_CHECK(std::memcmp(&t[l], &t[0], sizeof(ghr::SdsTop)) == 0);  // every lane holds the answer
-        float wq[GHR_SDS_K];
-        ghr::sds_weights(t[0].d, wq);
-        for (int k = 0; k < GHR_SDS_K; k++) {
-            SDS_CHECK(t[0].g[k] >= 0 && t[0].g[k] < N);
-            nbr[q * GHR_SDS_K + k] = t[0].g[k];
-            w[q * GHR_SDS_K + k] = wq[k];
-            count[t[0].g[k]]++;
-        }
-        if (q >= N) continue;
-        float acc[GHR_SDS_PAIRS][WV];
-        for (int l = 0; l < WV; l++) {
-            float a[GHR_SDS_PAIRS];
-            for (int p = 0; p < GHR_SDS_PAIRS; p++) a[p] = 0.f;
-            for (int i = l; i < n; i += WV) {
-                float x[GHR_SDS_K][3];
-                for (int m = 0; m < GHR_SDS_K; m++) std::memcpy(x[m], v + ((size_t)t[0].g[m] * n + i) * 3, 3 * sizeof(float));
-                ghr::sds_pair_cos(x, a);
-            }
-            for (int p = 0; p < GHR_SDS_PAIRS; p++) acc[p][l] = a[p];
-        }
-        float a0[GHR_SDS_PAIRS];
-        for (int p = 0; p < GHR_SDS_PAIRS; p++) { wave_sum(acc[p]); a0[p] = acc[p][0]; }
-        csim[q] = ghr::sds_csim(a0, n);
-        alpha[q] = ghr::sds_alpha(csim[q]);
-    }
+    ghr::HaarArgs a{};
+    a.Q = GG; a.N = N; a.n = n; a.C = C; a.G = G; a.uvg = uvg; a.centres = centres; a.z = z; a.v = v;
+    a.nbr = nbr; a.w = w; a.csim = csim; a.alpha = alpha; a.alpha_q = alpha_q; a.count = count; a.start = start; a.list = list;
+    a.out = texture;
+    ghrsim::haar_knn<ghr::HaarTexels>(a);
     // k_sds_lists: the 64-strided count sums with their butterfly, then the ballot-prefix placement chunk by chunk
     for (int g = 0; g < N; g++) {
         int part[WV];
@@ -215,7 +160,7 @@ void ghrsim_sds_texture(int N, int n, int C, int G, const float* uvg, const floa
             std::memcpy(part, t, sizeof(t));
         }
         const int base = part[0];
-        for (int l = 1; l < WV; l++) SDS_CHECK(part[l] == base);
+        for (int l = 1; l < WV; l++) GHR_HAAR_CHECK(part[l] == base);
         start[g] = base;
         if (g == N - 1) start[N] = base + count[g];
         int pos = base;
@@ -226,85 +171,27 @@ void ghrsim_sds_texture(int N, int n, int C, int G, const float* uvg, const floa
             for (int l = 0; l < WV; l++) {
                 if (!((mask >> l) & 1ull)) continue;
                 const int at = pos + __builtin_popcountll(mask & ((1ull << l) - 1ull));
-                SDS_CHECK(at >= 0 && at < total);
+                GHR_HAAR_CHECK(at >= 0 && at < total);
                 list[at] = e0 + l;
             }
             pos += __builtin_popcountll(mask);
         }
-        SDS_CHECK(pos == base + count[g]);
+        GHR_HAAR_CHECK(pos == base + count[g]);
     }
-    SDS_CHECK(start[N] == total);
-    // k_sds_blend
-    for (int q = 0; q < GG; q++) {
-        float wq[GHR_SDS_K], al[GHR_SDS_K];
-        const int32_t* g = nbr + q * GHR_SDS_K;
-        for (int k = 0; k < GHR_SDS_K; k++) { wq[k] = w[q * GHR_SDS_K + k]; al[k] = alpha[g[k]]; }
-        const float aq = ghr::sds_mix4(wq, al);
-        alpha_q[q] = aq;
-        for (int c = 0; c < C; c++) {
-            float zk[GHR_SDS_K];
-            for (int k = 0; k < GHR_SDS_K; k++) zk[k] = z[(size_t)g[k] * C + c];
-            texture[(size_t)c * GG + q] = ghr::sds_blend(zk[0], ghr::sds_mix4(wq, zk), aq);
-        }
-    }
+    GHR_HAAR_CHECK(start[N] == total);
+    ghrsim::haar_blend<ghr::HaarTexels>(a);
 }
 
 void ghrsim_sds_texture_backward(int N, int n, int C, int G, const float* z, const float* v, const int32_t* nbr, const float* w,
                                  const float* csim, const float* alpha_q, const int32_t* start, const int32_t* list,
                                  const float* d_texture, float* dalpha_q, float* d_csim, float* d_z, float* d_v)
 {
-    const int GG = G * G, total = GHR_SDS_K * GG;
-    for (int q = 0; q < GG; q++) {  // k_sds_bwd_texel
-        const int32_t* g = nbr + q * GHR_SDS_K;
-        const float* wq = w + q * GHR_SDS_K;
-        float part[WV];
-        for (int l = 0; l < WV; l++) {
-            part[l] = 0.f;
-            for (int c = l; c < C; c += WV) {
-                float zk[GHR_SDS_K];
-                for (int k = 0; k < GHR_SDS_K; k++) { SDS_CHECK(g[k] >= 0 && g[k] < N); zk[k] = z[(size_t)g[k] * C + c]; }
-                part[l] += d_texture[(size_t)c * GG + q] * ghr::sds_blend_dalpha(zk[0], ghr::sds_mix4(wq, zk));
-            }
-        }
-        wave_sum(part);
-        dalpha_q[q] = part[0];
-    }
-    for (int g = 0; g < N; g++) {  // k_sds_bwd_gather
-        const int beg = start[g], end = start[g + 1];
-        SDS_CHECK(0 <= beg && beg <= end && end <= total);
-        float dal = 0.f;
-        for (int t = beg; t < end; t++) {
-            const int e = list[t];
-            SDS_CHECK(e >= 0 && e < total && nbr[e] == g && (t == beg || list[t - 1] < e));
-            dal += dalpha_q[e >> 2] * w[e];
-        }
-        d_csim[g] = dal * ghr::sds_alpha_dc(csim[g]);
-        for (int c = 0; c < C; c++) {
-            float acc = 0.f;
-            for (int t = beg; t < end; t++) {
-                const int e = list[t], q = e >> 2;
-                acc += d_texture[(size_t)c * GG + q] * ghr::sds_blend_dz(e & 3, w[e], alpha_q[q]);
-            }
-            d_z[(size_t)g * C + c] = acc;
-        }
-    }
-    if (!d_v) return;
-    for (int g = 0; g < N; g++) {  // k_sds_bwd_v
-        const int beg = start[g], end = start[g + 1];
-        for (int i = 0; i < n; i++) {
-            float acc[3] = {0.f, 0.f, 0.f};
-            for (int t = beg; t < end; t++) {
-                const int e = list[t], q = e >> 2;
-                if (q >= N) break;
-                const float dc = (d_csim[q] / (float)GHR_SDS_PAIRS) / (float)n;
-                float x[GHR_SDS_K][3], da[3];
-                for (int m = 0; m < GHR_SDS_K; m++) std::memcpy(x[m], v + ((size_t)nbr[q * GHR_SDS_K + m] * n + i) * 3, 3 * sizeof(float));
-                ghr::sds_pair_cos_vjp(x, e & 3, dc, da);
-                for (int c = 0; c < 3; c++) acc[c] += da[c];
-            }
-            for (int c = 0; c < 3; c++) d_v[((size_t)g * n + i) * 3 + c] = acc[c];
-        }
-    }
+    ghr::HaarArgs a{};
+    a.Q = G * G; a.N = N; a.n = n; a.C = C; a.G = G; a.z = z; a.v = v;
+    a.nbr = const_cast<int32_t*>(nbr); a.w = const_cast<float*>(w); a.csim = const_cast<float*>(csim);
+    a.alpha_q = const_cast<float*>(alpha_q); a.start = const_cast<int32_t*>(start); a.list = const_cast<int32_t*>(list);
+    a.d_out = d_texture; a.dalpha_q = dalpha_q; a.d_csim = d_csim; a.d_z = d_z; a.d_v = d_v;
+    ghrsim::haar_backward<ghr::HaarTexels>(a);
 }
 
 }  // extern "C"

@@ -107,7 +107,7 @@ def test_python_refusals():
 
 
 # ---- 2 ------------------------------------------------------------------------------------------------------------------------
-DEPS = ["ghr_hostsim_guides.cpp", "ghr_guides.h", "ghr_sds.h"]
+DEPS = ["ghr_hostsim_guides.cpp", "ghr_hostsim_haar.h", "ghr_guides.h", "ghr_haar.h"]
 
 
 @pytest.fixture(scope="module")

@@ -117,7 +117,7 @@ def test_draw_and_size_refusals():
 
 
 # ---- 2 ------------------------------------------------------------------------------------------------------------------------
-DEPS = ["ghr_hostsim_sds.cpp", "ghr_sds.h"]
+DEPS = ["ghr_hostsim_sds.cpp", "ghr_hostsim_haar.h", "ghr_sds.h", "ghr_haar.h"]
 
 
 @pytest.fixture(scope="module")

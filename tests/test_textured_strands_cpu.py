@@ -173,7 +173,7 @@ def test_composed_form_against_the_arbiter(name):
 
 
 # ---- 3 ------------------------------------------------------------------------------------------------------------------------
-DEPS = ["ghr_hostsim_texstrands.cpp", "ghr_texstrands.h", "ghr_sds.h"]
+DEPS = ["ghr_hostsim_texstrands.cpp", "ghr_texstrands.h", "ghr_sds.h", "ghr_haar.h"]
 
 
 @pytest.fixture(scope="module")

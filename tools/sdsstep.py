@@ -47,7 +47,7 @@ def launches(fn):
         torch.cuda.synchronize()
     ev = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
     moves = sum(1 for e in ev if any(s in e.name.lower() for s in ("memcpy", "memset")))
-    own = sum(1 for e in ev if "k_sds_" in e.name)
+    own = sum(1 for e in ev if "k_sds_" in e.name or "k_haar_" in e.name)  # (the texture's kernels: csrc/ghr_haar.h)
     return len(ev) - moves, own, moves
 
 
