@@ -419,7 +419,13 @@ int ghr_forward_stage2(void* stream, const ghr_view_args* a, uint32_t R, void* g
                            order_ptr(im.tile_order, 0));
     }
     if (g_ev[0]) GHR_HIP(hipEventRecord(g_ev[0], s));
-    hipLaunchKernelGGL(ghr::k_render_fwd, dim3(ghr::xcd_grid((uint32_t)T)), dim3(GHR_BLOCK), 0, s, a->W, a->H, gx,
+    // GHR_K7_WALK=mask: test / measurement knob (read per call) -- the cells walk their hits bit by bit from the 64-bit masks
+    // instead of from hit lists; same outputs bit for bit.  The list walk carries list positions times 16 in 32 bits; a
+    // tile's list holds a Gaussian at most once, so below 2^28 Gaussians that cannot wrap (beyond: the mask walk).
+    const char* walk = std::getenv("GHR_K7_WALK");
+    const bool lists = a->P < (1 << 28) && !(walk != nullptr && std::strcmp(walk, "mask") == 0);
+    const auto k7 = lists ? ghr::k_render_fwd<true> : ghr::k_render_fwd<false>;
+    hipLaunchKernelGGL(k7, dim3(ghr::xcd_grid((uint32_t)T)), dim3(GHR_BLOCK), 0, s, a->W, a->H, gx,
                        (uint32_t)T, im.tile_start, b.point_list, g.rec, a->background, out_color, im.final_T,
                        im.n_contrib, R, b.cell_mask, im.cell_last, order_ptr(im.tile_order, 1), grad_scratch);
     if (g_ev[1]) GHR_HIP(hipEventRecord(g_ev[1], s));

@@ -532,19 +532,32 @@ GHR_HD bool cell_hit(const f4& bb, const f4& ep, const f4& r0, float X0, float Y
 // Per-lane 64-bit list of the batch entries sub..sub+63 whose alpha >= 1/255 region can touch this lane's cell: lane L
 // tests entry sub+L against the wave's four cells (X0 = wx0 + 4g, shared band Y0 = cy0 .. cy0+3): one band extent,
 // four interval overlaps, four ballots; every lane keeps the ballot of its own group.
-__device__ __forceinline__ unsigned long long cell_masks(const f4& bb, const f4& ep, const f4& r0, bool valid, float wx0,
-                                                         float cy0, int grp)
+// cell_masks4 hands back all four ballots (wave-uniform) and the lane's own four predicates (h[g]: entry sub+L can touch
+// cell g), for callers that build per-cell hit lists from them (k_render_fwd).
+__device__ __forceinline__ void cell_masks4(const f4& bb, const f4& ep, const f4& r0, bool valid, float wx0, float cy0,
+                                            unsigned long long m[4], bool h[4])
 {
-    const bool yhit = valid && !(bb.w < cy0 || bb.z > cy0 + 3.0f);
+    // (plain & on the comparisons, no short circuit: the predicates stay lane masks in scalar registers, which is what the
+    // ballots and the callers' branches on h[g] are)
+    const bool yhit = valid & !(bb.w < cy0) & !(bb.z > cy0 + 3.0f);
     float lo, hi;
     ellipse_band_extent(r0.w, ep, r0.y - (cy0 + 3.0f), r0.y - cy0, lo, hi);
     // pixel-space x-interval of the band-restricted ellipse, intersected with the box
     const float xl = fmaxf(bb.x, r0.x - hi), xr = fminf(bb.y, r0.x - lo);
-    const unsigned long long m0 = __builtin_amdgcn_ballot_w64(yhit && !(xr < wx0 || xl > wx0 + 3.0f));
-    const unsigned long long m1 = __builtin_amdgcn_ballot_w64(yhit && !(xr < wx0 + 4.0f || xl > wx0 + 7.0f));
-    const unsigned long long m2 = __builtin_amdgcn_ballot_w64(yhit && !(xr < wx0 + 8.0f || xl > wx0 + 11.0f));
-    const unsigned long long m3 = __builtin_amdgcn_ballot_w64(yhit && !(xr < wx0 + 12.0f || xl > wx0 + 15.0f));
-    return grp == 0 ? m0 : (grp == 1 ? m1 : (grp == 2 ? m2 : m3));
+    h[0] = yhit & !(xr < wx0) & !(xl > wx0 + 3.0f);
+    h[1] = yhit & !(xr < wx0 + 4.0f) & !(xl > wx0 + 7.0f);
+    h[2] = yhit & !(xr < wx0 + 8.0f) & !(xl > wx0 + 11.0f);
+    h[3] = yhit & !(xr < wx0 + 12.0f) & !(xl > wx0 + 15.0f);
+#pragma unroll
+    for (int g = 0; g < 4; g++) m[g] = __builtin_amdgcn_ballot_w64(h[g]);
+}
+__device__ __forceinline__ unsigned long long cell_masks(const f4& bb, const f4& ep, const f4& r0, bool valid, float wx0,
+                                                         float cy0, int grp)
+{
+    unsigned long long m[4];
+    bool h[4];
+    cell_masks4(bb, ep, r0, valid, wx0, cy0, m, h);
+    return grp == 0 ? m[0] : (grp == 1 ? m[1] : (grp == 2 ? m[2] : m[3]));
 }
 #endif
 

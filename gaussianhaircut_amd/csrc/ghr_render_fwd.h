@@ -5,7 +5,8 @@
 // its four 16-lane DPP rows ("groups") owns one 4x4-pixel CELL of that strip.  The reference visits every pixel of
 // every tile in the 3-sigma SQUARE of a splat; strand-aligned (needle) Gaussians cover a few dozen pixels of it, so a
 // whole-wave visit of one splat keeps ~15 % of the lanes busy.  Here every group walks its OWN ordered list of the
-// batch entries whose alpha >= 1/255 box touches its cell (a per-lane 64-bit mask built from four ballots), so the
+// batch entries whose alpha >= 1/255 box touches its cell (per 64-entry word: four ballots, turned once into four hit
+// lists in wave-private LDS), so the
 // four groups of a wave composite four different splats in the same instruction stream (measured on cfg3: 1.7x fewer
 // wave passes than per-wave strips).  Skipped entries would have been rejected by every pixel of the cell, so the
 // result is bit-identical to visiting everything.
@@ -58,6 +59,10 @@ GHR_HD bool fwd_step(PixFwd& s, bool live, float pxf, float pyf, const f4& r0, c
     return false;
 }
 
+// LISTS selects how a cell's hits of a 64-entry word are walked: from per-cell hit lists in LDS (the product) or bit by
+// bit from the 64-bit mask (the form before, kept for the bit-for-bit test and the A/B: GHR_K7_WALK=mask, ghr_capi.hip).
+// Everything else -- staging, cull, the words stored for K8, the early exits -- is one body.
+template <bool LISTS>
 __global__ void __launch_bounds__(GHR_BLOCK) k_render_fwd(int W, int H, int gx, uint32_t T_tiles,
                                                           const uint32_t* __restrict__ tile_start,
                                                           const uint32_t* __restrict__ point_list,
@@ -69,7 +74,15 @@ __global__ void __launch_bounds__(GHR_BLOCK) k_render_fwd(int W, int H, int gx, 
                                                           const uint32_t* __restrict__ tile_order, float* ginst)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    __shared__ f4 s_r0[GHR_BLOCK], s_r1[GHR_BLOCK], s_r2[GHR_BLOCK], s_r3[GHR_BLOCK], s_bb[GHR_BLOCK], s_ep[GHR_BLOCK];
+    // (entry GHR_BLOCK of the record planes is the NULL record of the list walk: all zero -- power = 0, alpha = 0 < 1/255)
+    __shared__ f4 s_r0[GHR_BLOCK + 1], s_r1[GHR_BLOCK + 1], s_r2[GHR_BLOCK + 1], s_r3[GHR_BLOCK + 1], s_bb[GHR_BLOCK], s_ep[GHR_BLOCK];
+    // per (wave, cell) the LDS byte offsets of the current word's hits, in list order (+ pad entries: the walk reads ahead);
+    // 24,640 + 2,064 + 16 B = 26,720 B per workgroup
+    __shared__ uint16_t s_hit[LISTS ? GHR_BLOCK * 4 + 8 : 1];
+    // "is any pixel of wave w still live": the tile's early exit.  (__syncthreads_count costs 256 B of LDS for its reduction;
+    // with them the list walk's 26.7 KB would take 22 of the CU's 128 LDS granules of 1280 B instead of 21: five workgroups
+    // per CU, not six.)
+    __shared__ __attribute__((aligned(16))) uint32_t s_live[GHR_BLOCK / 64];
 
     const uint32_t tile = tile_order ? tile_order[blockIdx.x] : xcd_tile(blockIdx.x, T_tiles);  // heaviest first (k_tile_scan)
     if (tile >= T_tiles) return;  // grid padding
@@ -106,11 +119,20 @@ __global__ void __launch_bounds__(GHR_BLOCK) k_render_fwd(int W, int H, int gx, 
         }                                                     \
     } while (0)
     if (n > 0) GHR_GATHER(0u);
+    if (LISTS && threadIdx.x == 0) {  // (visible behind the batch loop's barriers)
+        s_r0[GHR_BLOCK] = zero4; s_r1[GHR_BLOCK] = zero4; s_r2[GHR_BLOCK] = zero4; s_r3[GHR_BLOCK] = zero4;
+    }
 
     for (uint32_t base = 0; base < n; base += GHR_BLOCK) {
         // forward.cu:335-337: stop when the whole tile is done.  The barrier also protects the LDS planes.
         GHR_PROF(0);
-        if (__syncthreads_count(done) == GHR_BLOCK) break;
+        {   // (written before this barrier, read behind it, next written behind the staging barrier: no second buffer)
+            const bool wave_live = __builtin_amdgcn_ballot_w64(!done) != 0;
+            if (lane == 0) s_live[wave] = wave_live;
+            __syncthreads();
+            const uint4 lv = *reinterpret_cast<const uint4*>(s_live);
+            if ((lv.x | lv.y | lv.z | lv.w) == 0) break;
+        }
         GHR_PROF(1);
         s_r0[tid] = g0; s_r1[tid] = g1; s_r2[tid] = g2; s_r3[tid] = g3;
         s_bb[tid] = alpha_bbox(g0, g1);
@@ -125,32 +147,99 @@ __global__ void __launch_bounds__(GHR_BLOCK) k_render_fwd(int W, int H, int gx, 
             if (alive == 0) break;  // wave-uniform: all 64 pixels finished
             const uint32_t e = sub + lane;
             const uint32_t ec = e < cnt ? e : 0;
-            unsigned long long todo = cell_masks(s_bb[ec], s_ep[ec], s_r0[ec], e < cnt, wx0, cy0, grp);
+            unsigned long long m4[4];
+            bool hit[4];
+            cell_masks4(s_bb[ec], s_ep[ec], s_r0[ec], e < cnt, wx0, cy0, m4, hit);
             GHR_PROF(3);
             // word (base + sub) / 64 of this cell: every position a pixel of the cell can count in n_contrib lies in a
             // word written here (a cell that is finished, or a tile that stops early, has all its n_contrib behind it)
             // (uniform base + 32-bit byte offset: one address register; the kernel sits at the 80-VGPR occupancy step)
-            if (l == 0)
-                *reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(cell_mask) +
-                    (128u * (uint32_t)(mask_word0(beg, tile) + ((base + sub) >> 6)) + 8u * (uint32_t)(4 * wave + grp))) = todo;
-            if (((alive >> (16 * grp)) & 0xffffull) == 0) todo = 0;  // this cell is finished
-            while (todo) {  // divergent per GROUP (all 16 lanes of a DPP row share `todo`)
-                // (the entry's LDS byte offset straight from the bit index -- (ctz << 4) + 16 sub is ONE v_lshl_add -- and its
-                // list position from the scalar base + sub + 1: the kernel is VALU-bound, +8 VALU per step = +17 %)
-                const uint32_t bit = (uint32_t)__builtin_ctzll(todo);
-                todo &= todo - 1;
-                uint32_t off;  // (written out: the compiler turns (bit << 4) + 16 sub back into an OR and a shift)
-                asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(off) : "v"(bit), "s"(16u * sub));
-                done |= fwd_step(st, !done, pxf, pyf, *reinterpret_cast<const f4*>(reinterpret_cast<const char*>(s_r0) + off),
-                                 *reinterpret_cast<const f4*>(reinterpret_cast<const char*>(s_r1) + off),
-                                 *reinterpret_cast<const f4*>(reinterpret_cast<const char*>(s_r2) + off),
-                                 *reinterpret_cast<const f4*>(reinterpret_cast<const char*>(s_r3) + off), (base + sub + 1u) + bit);
+            if constexpr (LISTS) {
+                // (the wave's four words are consecutive and uniform: lane 0 stores them as two 16-B pieces straight from the
+                // scalar registers, no per-lane selection of "my cell's word")
+                if (lane == 0) {
+                    char* const mw = reinterpret_cast<char*>(cell_mask) +
+                        (128u * (uint32_t)(mask_word0(beg, tile) + ((base + sub) >> 6)) + 32u * (uint32_t)wave);
+                    *reinterpret_cast<ulonglong2*>(mw) = make_ulonglong2(m4[0], m4[1]);
+                    *reinterpret_cast<ulonglong2*>(mw + 16) = make_ulonglong2(m4[2], m4[3]);
+                }
+                // The four ballots are wave-uniform: their set bits are enumerated ONCE per word -- lane L appends its entry
+                // to the list of every cell it hits, at the rank v_mbcnt gives it -- instead of once per step and lane
+                // (ffbl, clear-lowest-bit and a 64-bit compare: ten of the mask walk's 36 VALU).  The lists hold the entries'
+                // LDS byte offsets 16 (sub + L) in ascending L, i.e. in list order; they are private to the wave, whose LDS
+                // operations execute in program order: no barrier.  First every list is filled with the offset of the
+                // null record (one 8-B store per lane = the wave's 512 B), so a list that is shorter than the wave's longest
+                // needs no "k < my count" test and no EXEC bookkeeping per step: past its end a cell composites the null
+                // record, which fwd_step rejects for every pixel.
+                char* const wl = reinterpret_cast<char*>(s_hit) + 512u * (uint32_t)__builtin_amdgcn_readfirstlane(wave);
+                // (lane number and fill value are made opaque per word: held across the kernel, the address terms and the
+                // constant the compiler derives from them are the registers that take the kernel over the 80-VGPR step)
+                uint32_t lq = (uint32_t)lane, nul = 0x00010001u * (16u * GHR_BLOCK);
+                asm volatile("" : "+v"(lq), "+v"(nul));
+                *reinterpret_cast<uint32_t*>(wl + 8u * lq) = nul;
+                *reinterpret_cast<uint32_t*>(wl + 8u * lq + 4) = nul;
+#pragma unroll
+                for (int g = 0; g < 4; g++)
+                    if (hit[g]) {
+                        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m4[g] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m4[g], 0u));
+                        *reinterpret_cast<uint16_t*>(wl + 128 * g + 2u * rank) = (uint16_t)(16u * e);
+                    }
+                __builtin_amdgcn_wave_barrier();
+                // The trip count (scalar) is the longest list of the wave's cells that are not finished -- what the divergent
+                // mask walk runs for; a finished cell's pixels are not live and reject whatever its list still holds.
+                uint32_t trips = 0;
+                GHR_PROF_COUNT(7, 1);
+#pragma unroll
+                for (int g = 0; g < 4; g++)
+                    trips = max(trips, ((alive >> (16 * g)) & 0xffffull) == 0 ? 0u : (uint32_t)__builtin_popcountll(m4[g]));
+                trips = (uint32_t)__builtin_amdgcn_readfirstlane((int)trips);
+                // Two steps per trip: every offset is read one whole step before its use (off the step's dependency chain) into
+                // the register its predecessor has just left -- no copy, no second pair of registers; the list address of a
+                // trip is one add for both.  The reads run up to two positions past a list: the next list, or the pad behind
+                // the last one.
+                // Positions are carried as 16 pos1 = off + 16 (base + 1) (one add per blend), converted once at the end.
+                const char* lp = wl + ((lq & 0x30u) << 3);
+                const uint32_t pos16 = 16u * (base + 1u);
+                uint32_t oa = *reinterpret_cast<const uint16_t*>(lp), ob = *reinterpret_cast<const uint16_t*>(lp + 2);
+#define GHR_K7_STEP(off_)                                                                                                               \
+    done |= fwd_step(st, !done, pxf, pyf, *reinterpret_cast<const f4*>(reinterpret_cast<const char*>(s_r0) + (off_)),                     \
+                     *reinterpret_cast<const f4*>(reinterpret_cast<const char*>(s_r1) + (off_)),                                          \
+                     *reinterpret_cast<const f4*>(reinterpret_cast<const char*>(s_r2) + (off_)),                                          \
+                     *reinterpret_cast<const f4*>(reinterpret_cast<const char*>(s_r3) + (off_)), pos16 + (off_))
+                for (uint32_t k = 0; k < trips; k += 2) {
+                    lp += 4;
+                    GHR_K7_STEP(oa);
+                    oa = *reinterpret_cast<const uint16_t*>(lp);
+                    if (k + 1 < trips) GHR_K7_STEP(ob);  // (uniform)
+                    ob = *reinterpret_cast<const uint16_t*>(lp + 2);
+                }
+#undef GHR_K7_STEP
+                __builtin_amdgcn_wave_barrier();
+            } else {
+                unsigned long long todo = grp == 0 ? m4[0] : (grp == 1 ? m4[1] : (grp == 2 ? m4[2] : m4[3]));
+                if (l == 0)
+                    *reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(cell_mask) +
+                        (128u * (uint32_t)(mask_word0(beg, tile) + ((base + sub) >> 6)) + 8u * (uint32_t)(4 * wave + grp))) = todo;
+                if (((alive >> (16 * grp)) & 0xffffull) == 0) todo = 0;  // this cell is finished
+                while (todo) {  // divergent per GROUP (all 16 lanes of a DPP row share `todo`)
+                    // (the entry's LDS byte offset straight from the bit index -- (ctz << 4) + 16 sub is ONE v_lshl_add -- and its
+                    // list position from the scalar base + sub + 1: the kernel is VALU-bound, +8 VALU per step = +17 %)
+                    const uint32_t bit = (uint32_t)__builtin_ctzll(todo);
+                    todo &= todo - 1;
+                    uint32_t off;  // (written out: the compiler turns (bit << 4) + 16 sub back into an OR and a shift)
+                    asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(off) : "v"(bit), "s"(16u * sub));
+                    done |= fwd_step(st, !done, pxf, pyf, *reinterpret_cast<const f4*>(reinterpret_cast<const char*>(s_r0) + off),
+                                     *reinterpret_cast<const f4*>(reinterpret_cast<const char*>(s_r1) + off),
+                                     *reinterpret_cast<const f4*>(reinterpret_cast<const char*>(s_r2) + off),
+                                     *reinterpret_cast<const f4*>(reinterpret_cast<const char*>(s_r3) + off), (base + sub + 1u) + bit);
+                }
             }
             GHR_PROF(4);
         }
     }
 
 #undef GHR_GATHER
+    if constexpr (LISTS) st.last >>= 4;  // 16 pos1 -> pos1 (a tile's list holds a Gaussian once: pos1 <= P < 2^28, ghr_capi.hip)
 
     {   // the cell's largest n_contrib: positions at or beyond it are dead for all its pixels (backward.cu:490-492)
         uint32_t lm = inside ? st.last : 0u;
