@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GHR_LIB_PATH") or os.path.join(CSRC, "libghr_hip.so")  # override: kernel experiments
 SOURCES = ["ghr_capi.hip"]
 HEADERS = ["ghr_device.h", "ghr_preprocess.h", "ghr_binning.h", "ghr_render_fwd.h", "ghr_render_bwd.h", "ghr_render_bwd2.h", "ghr_render_bwd3.h",
-           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_products.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_meshdist.h", "ghr_tilelists.h", "ghr_visibility.h", "ghr_strandview.h", "ghr_sds.h", "ghr_nn.h", "ghr_compare.h", "ghr_texstrands.h", "ghr_guides.h", "ghr_haar.h"]
+           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_products.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_meshdist.h", "ghr_tilelists.h", "ghr_visibility.h", "ghr_strandview.h", "ghr_sds.h", "ghr_nn.h", "ghr_compare.h", "ghr_texstrands.h", "ghr_guides.h", "ghr_haar.h", "ghr_capture.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-fPIC",
                "-shared"]
 
@@ -247,7 +247,7 @@ EXPORTS = ["ghr_last_error", "ghr_abi_version", "ghr_forward_sizes", "ghr_binnin
            "ghr_mesh_tris_sizes", "ghr_mesh_tris_build", "ghr_mesh_closest", "ghr_mesh_distance_backward",
            "ghr_vis_sizes", "ghr_vis_view", "ghr_vis_head_mask",
            "ghr_strandview_sizes", "ghr_strandview_face_depth", "ghr_strandview_raster", "ghr_strandview_shade",
-           "ghr_strandview_resolve", "ghr_strandview_opacity", "ghr_strandview_shade_shadowed",
+           "ghr_strandview_resolve", "ghr_strandview_opacity", "ghr_strandview_shade_shadowed", "ghr_strandview_capture",
            "ghr_sds_local", "ghr_sds_local_backward", "ghr_sds_texture", "ghr_sds_texture_backward",
            "ghr_nn_workspace_size", "ghr_nn_search", "ghr_chamfer_point", "ghr_chamfer_point_backward",
            "ghr_cmp_over_white", "ghr_cmp_strip",
@@ -370,6 +370,8 @@ def lib() -> ctypes.CDLL:
                                          ctypes.c_size_t, vp, vp]
     L.ghr_strandview_shade_shadowed.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, i32,
                                                 ctypes.POINTER(StrandViewShading), vp, ctypes.POINTER(StrandViewShadow), vp]
+    L.ghr_strandview_capture.argtypes = [vp, i32, i32, vp, ctypes.POINTER(ctypes.c_float * 12), f32, i32, i32, i32, i32, vp, vp, vp, f32,
+                                         vp, vp, vp, vp]
     L.ghr_sds_local.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, f32, vp, vp]
     L.ghr_sds_local_backward.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, f32, vp, vp, vp]
     L.ghr_sds_texture.argtypes = [vp, i32, i32, i32, i32] + [vp] * 13

@@ -37,6 +37,7 @@
 #include "ghr_meshdist.h"
 #include "ghr_visibility.h"
 #include "ghr_strandview.h"
+#include "ghr_capture.h"
 #include "ghr_sds.h"
 #include "ghr_texstrands.h"
 #include "ghr_guides.h"
@@ -2678,6 +2679,53 @@ int ghr_strandview_shade_shadowed(void* stream, int32_t S, int32_t L, const floa
     sa.t = t;
     memcpy(&sa.sd, shadow, sizeof(sa.sd));
     hipLaunchKernelGGL(ghr::k_sv_shade_shadowed, dim3(sv_blocks(N)), dim3(GHR_SV_BLOCK), 0, s, sa);
+    return finish(s, 0);
+}
+
+// -- synthetic captures: the masks and the orientation map of a view from its supersampled raster
+int ghr_strandview_capture(void* stream, int32_t S, int32_t L, const float* points, const float* M, float near_w, int32_t H,
+                           int32_t W, int32_t supersample, int32_t F, const int32_t* pix_to_segment, const int32_t* pix_to_face_out,
+                           const float* table, float var_floor, uint8_t* mask_hair, uint8_t* mask_body, uint8_t* angle, float* var)
+{
+    static const char* fn = "ghr_strandview_capture: %s";
+    if (S < 0 || H < 0 || W < 0 || F < 0) return lt_bad(fn, "negative size");
+    if (L < 2) return lt_bad(fn, "L < 2: a strand needs two points");
+    if (S > 0 && L > (0x7fffffffll / 3) / S) return lt_bad(fn, "S * L * 3 exceeds 32-bit offsets");
+    if (supersample != 1 && supersample != 2 && supersample != 4) return lt_bad(fn, "supersample is not 1, 2 or 4");
+    if ((uint64_t)H * supersample * (uint64_t)W * supersample > 0x7fffffffull) return lt_bad(fn, "H * W exceeds 32-bit offsets");
+    if (!(ghr::vis_finite(var_floor) && var_floor >= 0.f)) return lt_bad(fn, "var_floor is negative or not finite");
+    if (!(near_w >= 0.f)) return lt_bad(fn, "near is negative or NaN");
+    if (S && !points) return lt_bad(fn, "points is NULL");
+    if (!M) return lt_bad(fn, "M is NULL");
+    if (!table) return lt_bad(fn, "table is NULL");
+    const uint64_t N = (uint64_t)H * (uint64_t)W;
+    if (N && (!pix_to_segment || !pix_to_face_out)) return lt_bad(fn, "pix_to_segment or pix_to_face_out is NULL");
+    if (N && (!mask_hair || !mask_body || !angle || !var)) return lt_bad(fn, "an output plane is NULL");
+    if (!al4(points) || !al4(pix_to_segment) || !al4(pix_to_face_out) || !al4(table) || !al4(var))
+        return lt_bad(fn, "a buffer is not 4-B aligned");
+    if (N == 0) return GHR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    ghr::CapArgs a{};
+    a.S = S; a.L = L; a.H = H; a.W = W; a.F = F;
+    a.near = near_w; a.var_floor = var_floor;
+    for (int k = 0; k < 12; k++) a.Ms[k] = M[k];
+    a.out_dword = al4(mask_hair) && al4(mask_body) && al4(angle);
+    a.out_f4 = al16(var);
+    a.points = points; a.pix_to_segment = pix_to_segment; a.pix_to_face_out = pix_to_face_out; a.table = table;
+    a.mask_hair = mask_hair; a.mask_body = mask_body; a.angle = angle; a.var = var;
+    // a row of a pixel's subsamples is one load when both planes are aligned to it (a plane's rows are 4 s W bytes apart)
+    const uintptr_t both = (uintptr_t)pix_to_segment | (uintptr_t)pix_to_face_out;
+    const bool vec = (both & (uintptr_t)(4 * supersample - 1)) == 0;
+    const dim3 grid(sv_blocks((N + GHR_CAP_QUAD - 1) / GHR_CAP_QUAD)), block(GHR_CAP_BLOCK);
+    if (supersample == 4) {
+        if (vec) hipLaunchKernelGGL((ghr::k_sv_capture<4, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((ghr::k_sv_capture<4, false>), grid, block, 0, s, a);
+    } else if (supersample == 2) {
+        if (vec) hipLaunchKernelGGL((ghr::k_sv_capture<2, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((ghr::k_sv_capture<2, false>), grid, block, 0, s, a);
+    } else {
+        hipLaunchKernelGGL((ghr::k_sv_capture<1, false>), grid, block, 0, s, a);
+    }
     return finish(s, 0);
 }
 

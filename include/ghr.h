@@ -1033,6 +1033,21 @@ int ghr_strandview_shade_shadowed(void* stream, int32_t S, int32_t L, const floa
                                   const int32_t* pix_to_face_out, const float* t, int32_t mode, const ghr_strandview_shading* shading,
                                   const float* base, const ghr_strandview_shadow* shadow, uint8_t* rgb);
 
+/* ---- synthetic captures: a groom's masks and orientation map from the strand raster (csrc/ghr_capture.h)
+ * Added without an ABI_VERSION bump, as the preview's entries were: one new function, nothing existing changed.
+ * ghr_strandview_capture: from the planes pix_to_segment and pix_to_face_out [s H][s W] of ghr_strandview_raster on the s-times
+ * finer grid (s = supersample in {1, 2, 4}; M [12] on the HOST is that grid's matrix: already supersampled) the four planes
+ * [H][W] of one view: mask_hair and mask_body (bytes: the covered share of the pixel's s s subsamples; the body includes the
+ * hair), angle (a byte 0 .. 179: the bin of the mean doubled angle of the covering segments' screen directions; byte k is the
+ * direction (sin k deg, cos k deg), x right, y down) and var (float: var_floor + half of one minus the mean resultant length,
+ * 0.5 where no strand is seen).  table [180][2] = (cos 2 th_k, sin 2 th_k), th_k = k pi / 180, in float64 rounded once, is device
+ * memory.  The definition is the one at the top of csrc/ghr_capture.h.  An entry outside its table counts as nothing.
+ * H * W == 0, S == 0 and F == 0 are valid.  Refused, launching nothing: L < 2, supersample outside {1, 2, 4}, a var_floor that is
+ * negative or not finite, a negative (or NaN) near, a NULL required buffer, an index or float plane that is not 4-B aligned. */
+int ghr_strandview_capture(void* stream, int32_t S, int32_t L, const float* points, const float* M, float near_w, int32_t H,
+                           int32_t W, int32_t supersample, int32_t F, const int32_t* pix_to_segment, const int32_t* pix_to_face_out,
+                           const float* table, float var_floor, uint8_t* mask_hair, uint8_t* mask_body, uint8_t* angle, float* var);
+
 /* ---- the comparison video's frame assembly (src/postprocessing/concat_video.py:26-40; csrc/ghr_compare.h)
  * Added without an ABI_VERSION bump: two new functions, no existing struct or signature changed.
  * ghr_cmp_over_white: rgba [n_pixels][4] -> rgb [n_pixels][3], Pillow's paste of the image over opaque white through its own
