@@ -19,6 +19,7 @@
 #include "ghr_geom_bwd.h"
 #include "ghr_knn.h"
 #include "ghr_nn.h"
+#include "ghr_field.h"
 #include "ghr_loss.h"
 #include "ghr_eval.h"
 #include "ghr_orient.h"
@@ -2991,6 +2992,121 @@ int ghr_guides_blend_backward(void* stream, int32_t S, int32_t N, int32_t n, int
     hipLaunchKernelGGL(ghr::k_haar_dalpha<ghr::HaarRoots>, dim3(sds_blocks(S)), dim3(GHR_SDS_BLOCK), 0, s, a);
     hipLaunchKernelGGL(ghr::k_haar_gather<ghr::HaarRoots>, dim3(sds_blocks(N)), dim3(GHR_SDS_BLOCK), 0, s, a);
     if (d_vg) hipLaunchKernelGGL(ghr::k_haar_bwd_v<ghr::HaarRoots>, dim3(sds_blocks(N)), dim3(GHR_SDS_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+// ---- the hair field, strands traced through it, their resampling (ghr_field.h) ---------------------------------------------------
+static const int64_t FIELD_2_31 = (int64_t)1 << 31;
+
+static const char* field_cloud_bad(int64_t P)
+{
+    if (P < 1) return "P < 1: the field needs a point";
+    if (P >= FIELD_2_31) return "sizes exceed the kernels' 32-bit indexing";
+    return nullptr;
+}
+
+static const char* field_radius_bad(float r2)
+{
+    return (r2 > 0.f && r2 <= FLT_MAX) ? nullptr : "r2 must be positive and finite";
+}
+
+struct FieldWs { ghr::KnnCloud cloud; ghr::FieldPayload pay; };
+static FieldWs field_carve(const void* ws, int64_t P)
+{
+    char* base = align_base(ws);
+    return FieldWs{ghr::knn_cloud(base, (uint64_t)P), ghr::field_payload(base + ghr::knn_layout((uint64_t)P).bytes, (uint64_t)P)};
+}
+
+int ghr_field_workspace_size(int64_t P, size_t* bytes)
+{
+    static const char* fn = "ghr_field_workspace_size: %s";
+    if (const char* why = field_cloud_bad(P)) return lt_bad(fn, why);
+    if (!bytes) return lt_bad(fn, "bytes is NULL");
+    *bytes = ghr::knn_layout((uint64_t)P).bytes + ghr::field_payload_bytes((uint64_t)P) + ALIGN;
+    return GHR_OK;
+}
+
+int ghr_field_build(void* stream, int64_t P, const float* points, const int64_t* order, const float* directions, const float* weights,
+                    const float* colors, void* ws)
+{
+    static const char* fn = "ghr_field_build: %s";
+    if (const char* why = field_cloud_bad(P)) return lt_bad(fn, why);
+    if (!points || !order) return lt_bad(fn, "points or order is NULL");
+    if (!directions || !weights || !colors) return lt_bad(fn, "directions, weights or colors is NULL");
+    if (!ws) return lt_bad(fn, "ws is NULL");
+    const FieldWs w = field_carve(ws, P);
+    hipStream_t s = (hipStream_t)stream;
+    knn_boxes(s, w.cloud, points, order);
+    hipLaunchKernelGGL(ghr::k_field_pack, dim3((unsigned)((P + GHR_FIELD_BLOCK - 1) / GHR_FIELD_BLOCK)), dim3(GHR_FIELD_BLOCK), 0, s,
+                       w.cloud, directions, weights, colors, const_cast<float4*>(w.pay.dm), const_cast<float4*>(w.pay.f));
+    return finish(s, 0);
+}
+
+static unsigned field_wave_blocks(int64_t rows)
+{
+    const int64_t waves = (rows + GHR_KNN_BLOCK - 1) / GHR_KNN_BLOCK;
+    return (unsigned)((waves + GHR_FIELD_WAVES - 1) / GHR_FIELD_WAVES);
+}
+
+int ghr_field_query(void* stream, int64_t P, const void* ws, int64_t Q, const float* x, const float* t, const int64_t* query_order,
+                    float r2, float* rho, float* v, float* c, int32_t* n)
+{
+    static const char* fn = "ghr_field_query: %s";
+    if (const char* why = field_cloud_bad(P)) return lt_bad(fn, why);
+    if (Q < 0) return lt_bad(fn, "Q < 0");
+    if (Q >= FIELD_2_31 / 3) return lt_bad(fn, "sizes exceed the kernels' 32-bit indexing");
+    if (const char* why = field_radius_bad(r2)) return lt_bad(fn, why);
+    if (!ws) return lt_bad(fn, "ws is NULL");
+    if (!x || !t) return lt_bad(fn, "x or t is NULL");
+    if (!rho || !v || !c || !n) return lt_bad(fn, "rho, v, c or n is NULL");
+    if (Q == 0) return GHR_OK;
+    const FieldWs w = field_carve(ws, P);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ghr::k_field_query, dim3(field_wave_blocks(Q)), dim3(64 * GHR_FIELD_WAVES), 0, s, w.cloud, w.pay, (int)Q, x, t,
+                       (const long long*)query_order, r2, rho, v, c, n);
+    return finish(s, 0);
+}
+
+int ghr_field_trace(void* stream, int64_t P, const void* ws, int64_t S, const float* roots, const float* normals,
+                    const int64_t* root_order, int32_t M, float r2, float h, float beta, float rho_min, int32_t max_coast, float* path,
+                    int32_t* steps, float* rgb)
+{
+    static const char* fn = "ghr_field_trace: %s";
+    if (const char* why = field_cloud_bad(P)) return lt_bad(fn, why);
+    if (S < 0) return lt_bad(fn, "S < 0");
+    if (M < 1) return lt_bad(fn, "M < 1");
+    if (S >= FIELD_2_31 || S * ((int64_t)M + 1) * 3 >= FIELD_2_31) return lt_bad(fn, "sizes exceed the kernels' 32-bit indexing");
+    if (const char* why = field_radius_bad(r2)) return lt_bad(fn, why);
+    if (!(h > 0.f) || !(h <= FLT_MAX)) return lt_bad(fn, "h must be positive and finite");
+    if (!(beta >= 0.f && beta <= 1.f)) return lt_bad(fn, "beta must be in [0, 1]");
+    if (!(rho_min > 0.f)) return lt_bad(fn, "rho_min must be positive");
+    if (max_coast < 0) return lt_bad(fn, "max_coast < 0");
+    if (!ws) return lt_bad(fn, "ws is NULL");
+    if (!roots || !normals) return lt_bad(fn, "roots or normals is NULL");
+    if (!path || !steps || !rgb) return lt_bad(fn, "path, steps or rgb is NULL");
+    if (S == 0) return GHR_OK;
+    const FieldWs w = field_carve(ws, P);
+    const ghr::FieldTraceArgs a{r2, h, beta, 1.f - beta, rho_min, M, max_coast};
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ghr::k_field_trace, dim3(field_wave_blocks(S)), dim3(64 * GHR_FIELD_WAVES), 0, s, w.cloud, w.pay, (int)S, roots,
+                       normals, (const long long*)root_order, a, path, steps, rgb);
+    return finish(s, 0);
+}
+
+int ghr_strands_resample(void* stream, int64_t S, int32_t M, int32_t L, const float* path, const int32_t* steps, float* out)
+{
+    static const char* fn = "ghr_strands_resample: %s";
+    if (S < 0) return lt_bad(fn, "S < 0");
+    if (M < 1) return lt_bad(fn, "M < 1");
+    if (L < 2) return lt_bad(fn, "L < 2");
+    if (S >= FIELD_2_31 || S * ((int64_t)M + 1) * 3 >= FIELD_2_31 || S * (int64_t)L * 3 >= FIELD_2_31)
+        return lt_bad(fn, "sizes exceed the kernels' 32-bit indexing");
+    if (!path || !steps) return lt_bad(fn, "path or steps is NULL");
+    if (!out) return lt_bad(fn, "out is NULL");
+    if (S == 0) return GHR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ghr::k_strands_resample, dim3((unsigned)((S * L + GHR_FIELD_BLOCK - 1) / GHR_FIELD_BLOCK)), dim3(GHR_FIELD_BLOCK),
+                       0, s, (int)S, (int)M, (int)L, path, steps, out);
     return finish(s, 0);
 }
 

@@ -146,6 +146,13 @@ struct KnnTop3 {
     GHR_HD float mean() const { return ((b0 + b1) + b2) / 3.0f; }
 };
 
+// A policy may also have stage(blk, n, lane): the lane's share of staging something of its own beside block blk's n points,
+// between the walk's two fences (ghr_field.h's payload tile).  A policy without one costs nothing.
+template <class Policy>
+GHR_HD auto knn_stage(Policy& pol, int blk, int n, int lane, int) -> decltype(pol.stage(blk, n, lane), void()) { pol.stage(blk, n, lane); }
+template <class Policy>
+GHR_HD void knn_stage(Policy&, int, int, int, long) {}
+
 #if defined(__HIPCC__)
 #ifdef GHR_NN_COUNT_BLOCKS
 // measurement build only (tools/build_variant.sh -DGHR_NN_COUNT_BLOCKS): [0] blocks scanned by knn_walk, [1] waves
@@ -234,6 +241,7 @@ __device__ __forceinline__ void knn_walk(const KnnCloud& c, float4* tile, float3
         const int n = min(GHR_KNN_BLOCK, c.P - blk * GHR_KNN_BLOCK);
         knn_wave_lds_fence();  // every lane is done reading the previous tile
         if (lane < n) tile[lane] = c.sorted[(long long)blk * GHR_KNN_BLOCK + lane];
+        knn_stage(pol, blk, n, lane, 0);
         knn_wave_lds_fence();
         pol.scan(tile, n, skip_pos, q);
         GHR_KNN_COUNTING(++scanned;)

@@ -104,6 +104,23 @@ class GaussianModelStrands(GaussianModel):
         self.initialize_gaussians_hair()
         return self
 
+    def create_from_polylines(self, points, rgb=None, spatial_lr_scale: float = 1.0):
+        """A thin front of ``create_from_strands`` for an explicit groom (``strand_growing.grow_strands``): ``points [S, L, 3]``
+        polylines -> origins ``points[:, :1]``, directions ``diff(points)``; ``rgb [S, 3]`` (None: zeros) is the strand's
+        ``features_dc`` repeated over its segments, ``features_rest`` is 0."""
+        if points.dim() != 3 or points.shape[2] != 3 or points.shape[1] < 2:
+            raise ValueError("create_from_polylines: points must be [S, L, 3] with L >= 2, got %s" % (tuple(points.shape),))
+        S, n_seg = int(points.shape[0]), int(points.shape[1]) - 1
+        if rgb is not None and tuple(rgb.shape) != (S, 3):
+            raise ValueError("create_from_polylines: rgb must be [S, 3], got %s" % (tuple(rgb.shape),))
+        K = (self.max_sh_degree + 1) ** 2
+        pts = points.detach().float()
+        features = torch.zeros(S * n_seg, K, 3, device=pts.device)
+        if rgb is not None:
+            features[:, 0, :] = rgb.detach().float().to(pts.device)[:, None, :].expand(S, n_seg, 3).reshape(S * n_seg, 3)
+        self.num_strands, self.strand_length = S, n_seg + 1
+        return self.create_from_strands(pts[:, :1], pts[:, 1:] - pts[:, :-1], features, None, spatial_lr_scale)
+
     def create_from_generator(self, generator, num_strands: int, spatial_lr_scale: float = 1.0):
         """The reference's ``create_from_pcd`` (gaussian_model_strands.py:537-574) without its checkpoint loading: ``num_strands``
         strands out of ``generator.forward_inference`` (``strand_generator.TexturedStrands``) become the explicit parameters of

@@ -1119,6 +1119,33 @@ int ghr_guides_blend_backward(void* stream, int32_t S, int32_t N, int32_t n, int
                               const int32_t* nbr, const float* w, const float* csim, const float* alpha_s, const int32_t* start,
                               const int32_t* list, const float* d_z, float* dalpha_s, float* d_csim, float* d_zg, float* d_vg);
 
+/* ---- growing strands through the orientation field of a hair-point cloud (csrc/ghr_field.h)
+ * Added without an ABI_VERSION bump: five new functions, no existing struct or signature changed.
+ * The definition of the field (rho, v, c, n at a point under a heading: sequential fp32 sums over the points inside the radius in
+ * ascending key-ordered position), of a strand's trace and of the resampling is the one at the top of csrc/ghr_field.h.  A
+ * query's and a strand's bits depend on nothing but the cloud, its order and their own arguments.
+ * Sequence: ghr_knn_keys on the points over their own bounds; the caller sorts the keys (stable) and passes the permutation;
+ * ghr_field_build (block boxes and the payload in sorted order) fills ws, which ghr_field_query / ghr_field_trace then only read.
+ * ghr_field_build: points / directions / colors [P][3], weights [P], order [P] int64; ws: ghr_field_workspace_size(P) bytes.
+ * ghr_field_query: x / t [Q][3]; r2 the squared radius; rho [Q], v [Q][3], c [Q][3], n [Q] int32: every element written.
+ * ghr_field_trace: roots / normals [S][3]; path [S][M + 1][3], steps [S] int32, rgb [S][3]: every element written.
+ * query_order [Q] / root_order [S] (int64) may be NULL; otherwise a permutation: lane i of the launch takes row order[i] and
+ * writes that row, so rows that are near each other share a wave (speed only; the caller sorts them by their ghr_knn_keys in the
+ * cloud's bounds).
+ * ghr_strands_resample: path [S][M + 1][3], steps [S] -> out [S][L][3].
+ * Refused, with GHR_E_INVALID and a ghr_last_error() text before the runtime is touched: P < 1, Q or S < 0, M < 1, L < 2, r2 <= 0
+ * or not finite, h <= 0, rho_min <= 0, beta outside [0, 1], max_coast < 0, a NULL buffer (the two orders excepted), sizes beyond
+ * 32-bit indexing.  Q == 0 / S == 0 do nothing. */
+int ghr_field_workspace_size(int64_t P, size_t* bytes);
+int ghr_field_build(void* stream, int64_t P, const float* points, const int64_t* order, const float* directions, const float* weights,
+                    const float* colors, void* ws);
+int ghr_field_query(void* stream, int64_t P, const void* ws, int64_t Q, const float* x, const float* t, const int64_t* query_order,
+                    float r2, float* rho, float* v, float* c, int32_t* n);
+int ghr_field_trace(void* stream, int64_t P, const void* ws, int64_t S, const float* roots, const float* normals,
+                    const int64_t* root_order, int32_t M, float r2, float h, float beta, float rho_min, int32_t max_coast, float* path,
+                    int32_t* steps, float* rgb);
+int ghr_strands_resample(void* stream, int64_t S, int32_t M, int32_t L, const float* path, const int32_t* steps, float* out);
+
 /* Introspection for tests (device pointers into the workspaces; layout is otherwise private). */
 typedef struct ghr_ws_view {
     const float* rec;          /* [P][16]: x, y, conic a, b, c, opacity, features[10] */

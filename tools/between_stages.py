@@ -17,6 +17,14 @@
         its faces and its UV map, each a .npy, .pkl or .pth file; SEAMS.json: {"groups": [[...], ...]}, scalp vertices kept or cut
         together.
 
+    python tools/between_stages.py grow   --ply STAGE1.ply | --model_path M  --scalp SCALP.obj --out_dir DIR [--scalp_uvs UV]
+                                          [--num_strands 30000] [--strand_length 100] [--radius R] [--step_length H] [--max_steps 400]
+                                          [--mesh HEAD.obj] [--seed 0]
+        the hair Gaussians of a stage-1 model (default M/point_cloud_filtered/iteration_N/point_cloud.ply) -> an initial groom grown
+        from roots sampled on the scalp along its normals (strand_growing.grow_strands): DIR/N_strands.pkl,
+        DIR/N_strands.ply, DIR/N_strands_rgb.npy.  --mesh prunes the strands that run inside the head.  Without --scalp_uvs the
+        scalp's two widest coordinates stand in for its UV map (only the roots' normals are used, not their tangents).
+
 (src/preprocessing/scale_scene_into_sphere.py, filter_flame_intersections.py, export_strands.py,
 extract_non_visible_head_scalp.py.)  Containment and visibility run in HIP on cuda:0; --composed evaluates the PyTorch-composed
 forms instead (any device, slow)."""
@@ -78,9 +86,33 @@ def _scalp(a, fused, dev):
           % (len(views), int(vertex_mask.sum()), len(v), len(kept), len(np.asarray(idx).reshape(-1)), len(faces), len(sf.reshape(-1, 3)), out))
 
 
+def _grow(a, fused, dev):
+    from gaussianhaircut_amd import strand_generator as sgen
+    from gaussianhaircut_amd import strand_growing as sg
+    from gaussianhaircut_amd.mesh import read_obj
+    ply = a.ply or os.path.join(a.model_path, "point_cloud_filtered", "iteration_%d" % a.iter, "point_cloud.ply")
+    field = sg.HairField.from_model(_load(ply, a.sh_degree, dev), a.label_threshold)
+    v, f = read_obj(a.scalp)
+    v, f = torch.as_tensor(np.asarray(v, np.float32)), torch.as_tensor(np.asarray(f, np.int64))
+    if a.scalp_uvs:
+        uv = torch.as_tensor(np.asarray(_load_array(a.scalp_uvs), np.float32)).reshape(-1, 2)
+    else:
+        wide = torch.argsort(v.max(0).values - v.min(0).values, descending=True)[:2].sort().values
+        uv = v[:, wide]
+    roots = sgen.sample_roots(v, f, uv, a.num_strands, generator=torch.Generator().manual_seed(a.seed))
+    normals = roots["local2world"][:, :, 2].contiguous()
+    out = sg.grow_strands(field, roots["origins"].to(dev), normals.to(dev), L=a.strand_length, radius=a.radius, step=a.step_length,
+                          max_steps=a.max_steps, mesh=HeadMesh.from_obj(a.mesh) if a.mesh else None, fused=fused)
+    print("grow: %d hair Gaussians, radius %.5g, step %.5g, rho_min %.5g; kept %d of %d strands (steps: median %d, longest %d)"
+          % (field.P, out["radius"], out["step"], out["rho_min"], int(out["keep"].sum()), a.num_strands,
+             int(out["steps"].float().median()), int(out["steps"].max())))
+    print("export: %s %s" % bs.export_strands(out["points"], a.out_dir, a.iter))
+    np.save(os.path.join(a.out_dir, "%s_strands_rgb.npy" % a.iter), out["rgb"].cpu().numpy())
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("step", choices=["crop", "filter", "export", "split", "scalp"])
+    ap.add_argument("step", choices=["crop", "filter", "export", "split", "scalp", "grow"])
     ap.add_argument("--model_path")
     ap.add_argument("--path_to_data")
     ap.add_argument("--mesh")
@@ -100,12 +132,22 @@ def main(argv=None):
     ap.add_argument("--max_root_dist", type=float, default=0.1)
     ap.add_argument("--prob_thr", type=float, default=0.5)
     ap.add_argument("--n_views_thr", type=float, default=0.1)
+    ap.add_argument("--ply")
+    ap.add_argument("--num_strands", type=int, default=30_000)
+    ap.add_argument("--strand_length", type=int, default=100)
+    ap.add_argument("--radius", type=float, default=None)
+    ap.add_argument("--step_length", type=float, default=None)
+    ap.add_argument("--max_steps", type=int, default=400)
+    ap.add_argument("--label_threshold", type=float, default=0.5)
+    ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args(argv)
     fused = not a.composed
     dev = torch.device(a.device or ("cuda:0" if fused else "cpu"))
     it = "iteration_%d" % a.iter
     if a.step == "scalp":
         _scalp(a, fused, dev)
+    elif a.step == "grow":
+        _grow(a, fused, dev)
     elif a.step == "crop":
         m = _load(os.path.join(a.model_path, "point_cloud", it, "raw_point_cloud.ply"), a.sh_degree, dev)
         tr, s = bs.hair_sphere(m)
