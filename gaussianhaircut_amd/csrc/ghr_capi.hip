@@ -36,6 +36,7 @@
 #include "ghr_shared.h"
 #include "ghr_mesh.h"
 #include "ghr_meshdist.h"
+#include "ghr_grow.h"
 #include "ghr_visibility.h"
 #include "ghr_strandview.h"
 #include "ghr_capture.h"
@@ -3067,29 +3068,69 @@ int ghr_field_query(void* stream, int64_t P, const void* ws, int64_t Q, const fl
     return finish(s, 0);
 }
 
+// what ghr_field_trace and ghr_field_trace_guarded refuse alike, in one order
+static const char* field_trace_bad(int64_t P, const void* ws, int64_t S, const float* roots, const float* normals, int32_t M, float r2,
+                                   float h, float beta, float rho_min, int32_t max_coast, const float* path, const int32_t* steps,
+                                   const float* rgb)
+{
+    if (const char* why = field_cloud_bad(P)) return why;
+    if (S < 0) return "S < 0";
+    if (M < 1) return "M < 1";
+    if (S >= FIELD_2_31 || S * ((int64_t)M + 1) * 3 >= FIELD_2_31) return "sizes exceed the kernels' 32-bit indexing";
+    if (const char* why = field_radius_bad(r2)) return why;
+    if (!(h > 0.f) || !(h <= FLT_MAX)) return "h must be positive and finite";
+    if (!(beta >= 0.f && beta <= 1.f)) return "beta must be in [0, 1]";
+    if (!(rho_min > 0.f)) return "rho_min must be positive";
+    if (max_coast < 0) return "max_coast < 0";
+    if (!ws) return "ws is NULL";
+    if (!roots || !normals) return "roots or normals is NULL";
+    if (!path || !steps || !rgb) return "path, steps or rgb is NULL";
+    return nullptr;
+}
+
 int ghr_field_trace(void* stream, int64_t P, const void* ws, int64_t S, const float* roots, const float* normals,
                     const int64_t* root_order, int32_t M, float r2, float h, float beta, float rho_min, int32_t max_coast, float* path,
                     int32_t* steps, float* rgb)
 {
     static const char* fn = "ghr_field_trace: %s";
-    if (const char* why = field_cloud_bad(P)) return lt_bad(fn, why);
-    if (S < 0) return lt_bad(fn, "S < 0");
-    if (M < 1) return lt_bad(fn, "M < 1");
-    if (S >= FIELD_2_31 || S * ((int64_t)M + 1) * 3 >= FIELD_2_31) return lt_bad(fn, "sizes exceed the kernels' 32-bit indexing");
-    if (const char* why = field_radius_bad(r2)) return lt_bad(fn, why);
-    if (!(h > 0.f) || !(h <= FLT_MAX)) return lt_bad(fn, "h must be positive and finite");
-    if (!(beta >= 0.f && beta <= 1.f)) return lt_bad(fn, "beta must be in [0, 1]");
-    if (!(rho_min > 0.f)) return lt_bad(fn, "rho_min must be positive");
-    if (max_coast < 0) return lt_bad(fn, "max_coast < 0");
-    if (!ws) return lt_bad(fn, "ws is NULL");
-    if (!roots || !normals) return lt_bad(fn, "roots or normals is NULL");
-    if (!path || !steps || !rgb) return lt_bad(fn, "path, steps or rgb is NULL");
+    if (const char* why = field_trace_bad(P, ws, S, roots, normals, M, r2, h, beta, rho_min, max_coast, path, steps, rgb)) return lt_bad(fn, why);
     if (S == 0) return GHR_OK;
     const FieldWs w = field_carve(ws, P);
     const ghr::FieldTraceArgs a{r2, h, beta, 1.f - beta, rho_min, M, max_coast};
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(ghr::k_field_trace, dim3(field_wave_blocks(S)), dim3(64 * GHR_FIELD_WAVES), 0, s, w.cloud, w.pay, (int)S, roots,
                        normals, (const long long*)root_order, a, path, steps, rgb);
+    return finish(s, 0);
+}
+
+// ---- the guarded trace: strands grown around the head mesh (ghr_grow.h) -----------------------------------------------------------
+int ghr_field_trace_guarded(void* stream, int64_t P, const void* ws, const ghr_mesh_tris* tris_header, const void* tris_dev,
+                            const ghr_mesh_grid* grid_header, const void* grid_dev, int64_t S, const float* roots, const float* normals,
+                            const int64_t* root_order, int32_t M, float r2, float h, float beta, float rho_min, int32_t max_coast,
+                            float margin, float* path, int32_t* steps, float* rgb, int32_t* contacts, uint8_t* stop)
+{
+    static const char* fn = "ghr_field_trace_guarded: %s";
+    if (const char* why = field_trace_bad(P, ws, S, roots, normals, M, r2, h, beta, rho_min, max_coast, path, steps, rgb)) return lt_bad(fn, why);
+    if (!(margin > 0.f) || !(margin <= FLT_MAX)) return lt_bad(fn, "margin must be positive and finite");
+    if (!contacts || !stop) return lt_bad(fn, "contacts or stop is NULL");
+    if (!tris_header || !tris_dev) return lt_bad(fn, "tris_header or tris_dev is NULL");
+    if (!grid_header || !grid_dev) return lt_bad(fn, "grid_header or grid_dev is NULL");
+    if (int rc = tris_header_check("ghr_field_trace_guarded: tris_header: %s", tris_header, tris_dev)) return rc;
+    if (int rc = mesh_header_check("ghr_field_trace_guarded: grid_header: %s", grid_header, grid_dev)) return rc;
+    if (S == 0) return GHR_OK;
+    const FieldWs w = field_carve(ws, P);
+    const ghr::MeshTris& th = *reinterpret_cast<const ghr::MeshTris*>(tris_header);
+    ghr::GrowArgs g{};
+    g.c = w.cloud; g.pay = w.pay;
+    g.md = ghr::md_view(th, tris_dev);
+    for (int k = 0; k < 3; k++) g.md_bounds[k] = th.lo[k], g.md_bounds[3 + k] = th.hi[k];
+    g.mesh = ghr::mesh_view(*reinterpret_cast<const ghr::MeshGrid*>(grid_header), grid_dev);
+    g.a = ghr::FieldTraceArgs{r2, h, beta, 1.f - beta, rho_min, M, max_coast};
+    g.margin = margin; g.S = (int)S;
+    g.roots = roots; g.normals = normals; g.order = (const long long*)root_order;
+    g.path = path; g.steps = steps; g.rgb = rgb; g.contacts = contacts; g.stop = stop;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ghr::k_grow_guarded, dim3(field_wave_blocks(S)), dim3(64 * GHR_FIELD_WAVES), 0, s, g);
     return finish(s, 0);
 }
 

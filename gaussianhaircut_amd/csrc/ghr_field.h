@@ -123,6 +123,35 @@ GHR_HD void field_strand_init(FieldStrand& s, const float* o, const float* nrm)
     s.live = true;
 }
 
+// The heading update of one step from the field at (s.x, s.t): field_strand_step below up to its new t (support, blend, coast, C,
+// R, the coast stop), for ghr_grow.h's guarded trace, which asks the mesh before it moves.  Returns FIELD_STOPPED (the strand is
+// not live afterwards), FIELD_COASTED or FIELD_SUPPORTED.  field_strand_step keeps its own copy of these lines: routed through
+// this function k_field_trace compiles to other code; a guarded strand that never touches the mesh must equal the
+// unguarded one bit for bit, which tests/test_grow_guarded_cpu.py holds the two to.
+enum { FIELD_STOPPED = 0, FIELD_COASTED = 1, FIELD_SUPPORTED = 2 };
+GHR_HD int field_strand_heading(FieldStrand& s, const FieldGather& g, const FieldTraceArgs& a)
+{
+    const float lv = field_len(g.vx, g.vy, g.vz);
+    const bool supported = g.rho >= a.rho_min && lv > 0.f;
+    if (supported) {
+        const float b0 = s.t[0] * a.one_minus_beta + (g.vx / lv) * a.beta;
+        const float b1 = s.t[1] * a.one_minus_beta + (g.vy / lv) * a.beta;
+        const float b2 = s.t[2] * a.one_minus_beta + (g.vz / lv) * a.beta;
+        const float lb = fmaxf(field_len(b0, b1, b2), GHR_FIELD_NORM_EPS);
+        s.t[0] = b0 / lb; s.t[1] = b1 / lb; s.t[2] = b2 / lb;
+        s.coast = 0;
+        s.C[0] += g.cx; s.C[1] += g.cy; s.C[2] += g.cz;
+        s.R += g.rho;
+    } else {
+        s.coast += 1;
+        if (s.coast > a.max_coast) {
+            s.live = false;
+            return FIELD_STOPPED;
+        }
+    }
+    return supported ? FIELD_SUPPORTED : FIELD_COASTED;
+}
+
 // One step of the definition's loop from the field at (s.x, s.t).  Returns whether a point was appended (it is s.x then); a
 // strand that stops appends none and is not live afterwards.
 GHR_HD bool field_strand_step(FieldStrand& s, const FieldGather& g, const FieldTraceArgs& a)

@@ -31,7 +31,8 @@
 //   bkeys [nblocks]        the key of every block's first face: the seed block of a wave is found in it by binary search
 // The search (k_meshdist_search): one wave per 64 queries in the key order of the queries, GHR_MD_WAVES waves per workgroup;
 // the wave stages a block's records in its private 3 KB of LDS and every lane reads the same address (broadcasts); the walk
-// is knn_walk's: seed block, then the superblocks in rotation, wave ballots on needs(bound) -- and inside a staged block one more
+// (md_wave_search, shared with ghr_grow.h's guarded trace) is knn_walk's: seed block, then the superblocks in rotation, wave
+// ballots on needs(bound) -- and inside a staged block one more
 // ballot per face on the bound of the face's own box, which skips most faces of a neighbouring block.  k_meshdist_bwd: one thread per
 // point, no atomics.  Per-element functions are GHR_HD and the header is plain C++ outside __HIPCC__
 // (tests/hostsim/ghr_hostsim_meshdist.cpp walks them); GHR_MD_CHECK(cond) is an assert there and nothing in the library.
@@ -295,27 +296,16 @@ struct MdSearchArgs {
     float* point;                       // [Q][3]
 };
 
-// One wave per 64 queries in key order; outputs at the queries' original indices.  An order entry outside [0, Q) (only a
-// caller's bad permutation can hold one) is read as 0, so no access leaves the buffers.
-__global__ void __launch_bounds__(64 * GHR_MD_WAVES) k_meshdist_search(MdSearchArgs a)
+// The wave loop of the search (every lane of the wave makes the call): `tile` is the wave's private 3 * GHR_KNN_BLOCK float4 of
+// LDS, q the lane's query, `valid` whether the lane has a finite one (an invalid lane votes in no ballot), `first` the
+// wave-uniform seed block, near the lane's state.  Seed block, then the superblocks in rotation from the seed's on; wave ballots on
+// needs(bound) skip superblocks and blocks, and inside a staged block one more ballot per face on the bound of the face's own box.
+// The results do not depend on `first` (the total order of the definition).  k_meshdist_search and k_grow_guarded (ghr_grow.h)
+// call it; each wave works on its own, only wave-level fences order the tile's reuse.
+__device__ __forceinline__ void md_wave_search(const MdView& m, float4* tile, MdVec q, bool valid, int first, MdNearest& near)
 {
-    __shared__ float4 tiles[GHR_MD_WAVES][3 * GHR_KNN_BLOCK];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const long long qb = (long long)blockIdx.x * GHR_MD_WAVES + wave;
-    const long long q0 = qb * GHR_KNN_BLOCK;
-    if (q0 >= a.Q) return;
-    const MdView& m = a.m;
-    float4* tile = tiles[wave];
-    const bool has = q0 + lane < a.Q;
-    const int nq = (int)min((long long)GHR_KNN_BLOCK, a.Q - q0);
-    long long o = a.order[has ? q0 + lane : q0];
-    if (o < 0 || o >= a.Q) o = 0;
-    const MdVec q{a.points[3 * o], a.points[3 * o + 1], a.points[3 * o + 2]};
-    const bool finite = md_finite(q.x) && md_finite(q.y) && md_finite(q.z);
-    const bool valid = has && finite;  // a lane without a finite query votes in no ballot
+    const int lane = threadIdx.x & 63;
     const float3 q3 = make_float3(q.x, q.y, q.z);
-    const int first = __builtin_amdgcn_readfirstlane(md_seed_block(m.bkeys, m.n_blocks, a.keys[q0 + nq / 2]));
-    MdNearest near;
     GHR_MD_COUNTING(unsigned scanned = 0; unsigned taken = 0;)
     auto scan_block = [&](int blk) {
         const int n = min(GHR_KNN_BLOCK, m.n_faces - blk * GHR_KNN_BLOCK);
@@ -347,6 +337,28 @@ __global__ void __launch_bounds__(64 * GHR_MD_WAVES) k_meshdist_search(MdSearchA
     }
     GHR_MD_COUNTING(if (lane == 0) { atomicAdd(&g_md_count[0], (unsigned long long)scanned); atomicAdd(&g_md_count[1], 1ull);
                                       atomicAdd(&g_md_count[2], (unsigned long long)taken); })
+}
+
+// One wave per 64 queries in key order; outputs at the queries' original indices.  An order entry outside [0, Q) (only a
+// caller's bad permutation can hold one) is read as 0, so no access leaves the buffers.
+__global__ void __launch_bounds__(64 * GHR_MD_WAVES) k_meshdist_search(MdSearchArgs a)
+{
+    __shared__ float4 tiles[GHR_MD_WAVES][3 * GHR_KNN_BLOCK];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long qb = (long long)blockIdx.x * GHR_MD_WAVES + wave;
+    const long long q0 = qb * GHR_KNN_BLOCK;
+    if (q0 >= a.Q) return;
+    const MdView& m = a.m;
+    const bool has = q0 + lane < a.Q;
+    const int nq = (int)min((long long)GHR_KNN_BLOCK, a.Q - q0);
+    long long o = a.order[has ? q0 + lane : q0];
+    if (o < 0 || o >= a.Q) o = 0;
+    const MdVec q{a.points[3 * o], a.points[3 * o + 1], a.points[3 * o + 2]};
+    const bool finite = md_finite(q.x) && md_finite(q.y) && md_finite(q.z);
+    const bool valid = has && finite;  // a lane without a finite query votes in no ballot
+    const int first = __builtin_amdgcn_readfirstlane(md_seed_block(m.bkeys, m.n_blocks, a.keys[q0 + nq / 2]));
+    MdNearest near;
+    md_wave_search(m, tiles[wave], q, valid, first, near);
     if (has) {
         a.dist2[o] = finite ? near.best : __builtin_inff();
         a.face[o] = finite && (unsigned)near.face < (unsigned)m.n_faces ? near.face : -1;

@@ -9,6 +9,11 @@ normal, blends its heading with ``v / |v|`` by ``beta`` where ``rho >= rho_min``
 unsupported steps and stops after; ``steps`` is the last point reached by a supported step.  ``resample_strands`` brings the kept
 part to ``L`` points with integer spans.
 
+``grow_strands(..., mesh=, avoid=True)`` grows the strands AROUND the head (``csrc/ghr_grow.h``): where the trace
+would set ``x += h t`` it asks the head mesh for the closest point and the containment of ``y = x + h t``; a ``y`` whose signed
+distance is below ``margin`` is projected to ``margin`` above its closest point, and the part of the heading that points into the
+surface is removed (a heading that has nothing else stops the strand head-on).
+
 ``fused=False`` is the PyTorch-composed comparator: brute force over all points in chunks, the same expressions elementwise with
 ``torch.sum`` (another order of summation), for any floating dtype and the only form for CPU tensors.  ``fused=None`` takes the
 HIP kernels for contiguous fp32 ROCm tensors and the comparator otherwise; ``fused=True`` raises where HIP does not apply.  The
@@ -17,10 +22,11 @@ or the launch.
 
 The defaults of ``grow_strands`` are look constants, chosen and not measured: ``radius`` twice the median nearest-neighbour
 spacing of the cloud (``sqrt(distCUDA2)``), ``step = radius / 2.5``, ``rho_min`` 0.05 of the median ``rho`` at the cloud's own
-points, ``beta = 0.5``, ``max_coast = 4``, ``min_steps = 8``.
+points, ``beta = 0.5``, ``max_coast = 4``, ``min_steps = 8``, and with ``avoid`` ``margin = step``.
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional
 
 import numpy as np
@@ -33,6 +39,7 @@ from .utils.general_utils import build_rotation
 
 PAIR_CHUNK = 2 ** 24  # pairs per brute-force chunk of the comparator
 NORM_EPS = 1e-8       # GHR_FIELD_NORM_EPS
+HEADON_EPS = 1e-4     # GHR_GROW_HEADON_EPS
 
 
 def _f32(v) -> float:
@@ -117,6 +124,75 @@ def trace_composed(field_fn, roots, normals, M: int, h: float, beta: float, rho_
     path = torch.where((ar >= rows[:, None])[..., None], x[:, None, :], path)
     rgb = torch.where((R == 0)[:, None], torch.zeros_like(C), C / torch.where(R == 0, torch.ones_like(R), R)[:, None])
     return path, steps.to(torch.int32), rgb
+
+
+def trace_guarded_composed(field_fn, mesh, roots, normals, M: int, h: float, beta: float, rho_min: float, max_coast: int,
+                           margin: float, headings: bool = False):
+    """The guarded trace of ``csrc/ghr_grow.h`` for every root at once: ``trace_composed``'s loop with the head asked at every step
+    through ``mesh.closest_point(fused=False)`` and ``mesh.contains(fused=False)`` (both float32) -- the only form on CPU tensors.
+    -> ``path [S, M + 1, 3]``, ``steps [S]`` int32, ``rgb [S, 3]``, ``contacts [S]`` int32, ``stop [S]`` uint8 (0 ran out of
+    ``M``, 1 coasted out of support, 2 met the head head-on); with ``headings`` also the strands' last headings ``[S, 3]``."""
+    from .mesh import _sqrt32
+    S, dev, dt = roots.shape[0], roots.device, roots.dtype
+    x = roots.clone()
+    t = normals / _len3(normals).clamp_min(NORM_EPS)[:, None]
+    path = roots[:, None, :].repeat(1, M + 1, 1)
+    live = torch.ones(S, dtype=torch.bool, device=dev)
+    coast = torch.zeros(S, dtype=torch.int64, device=dev)
+    rows = torch.ones(S, dtype=torch.int64, device=dev)
+    steps = torch.zeros(S, dtype=torch.int64, device=dev)
+    contacts = torch.zeros(S, dtype=torch.int64, device=dev)
+    stop = torch.zeros(S, dtype=torch.uint8, device=dev)
+    C, R = torch.zeros(S, 3, dtype=dt, device=dev), torch.zeros(S, dtype=dt, device=dev)
+    omb = float(torch.tensor(1.0, dtype=dt) - torch.tensor(beta, dtype=dt))   # 1 - beta formed once in the tensors' dtype
+    one = torch.ones((), dtype=dt, device=dev)
+    for _ in range(M):
+        if not bool(live.any()):
+            break
+        rho, v, c, _n = field_fn(x, t)
+        lv = _len3(v)
+        sup = live & (rho >= rho_min) & (lv > 0)
+        u = v / torch.where(lv > 0, lv, torch.ones_like(lv))[:, None]
+        b = t * omb + u * beta
+        tn = b / _len3(b).clamp_min(NORM_EPS)[:, None]
+        t = torch.where(sup[:, None], tn, t)
+        C = torch.where(sup[:, None], C + c, C)
+        R = torch.where(sup, R + rho, R)
+        coast = torch.where(sup, torch.zeros_like(coast), coast + 1)
+        coasted_out = live & ~(sup | (coast <= max_coast))
+        stop = torch.where(coasted_out, torch.ones_like(stop), stop)
+        live = live & ~coasted_out
+        # the guard: y asked of the mesh (a row that is not live asks too; its answer is not used)
+        y = x + h * t
+        d2, _face, cpt = mesh.closest_point(y, fused=False)
+        inside = mesh.contains(y, fused=False)
+        d = _sqrt32(d2).to(dt)
+        cpt = cpt.to(dt)
+        sd = torch.where(inside, -d, d)
+        contact = live & (sd < margin)
+        corrected = contact & (d2 != 0)
+        un = (y - cpt) / torch.where(corrected, d, one)[:, None]
+        nrm = torch.where(inside[:, None], -un, un)
+        dot = (t[:, 0] * nrm[:, 0] + t[:, 1] * nrm[:, 1]) + t[:, 2] * nrm[:, 2]
+        slide = corrected & (dot < 0)
+        sl = t - dot[:, None] * nrm
+        ln = _len3(sl)
+        head_on = slide & (ln <= HEADON_EPS)
+        t = torch.where((slide & ~head_on)[:, None], sl / torch.where(ln > 0, ln, one)[:, None], t)
+        stop = torch.where(head_on, torch.full_like(stop, 2), stop)
+        live = live & ~head_on
+        xn = torch.where(corrected[:, None], cpt + margin * nrm, y)
+        x = torch.where(live[:, None], xn, x)
+        contacts = contacts + (contact & live).to(torch.int64)
+        rows = rows + live.to(torch.int64)
+        idx = torch.nonzero(live)[:, 0]
+        path[idx, rows[idx] - 1] = x[idx]
+        steps = torch.where(sup & live, rows - 1, steps)
+    ar = torch.arange(M + 1, device=dev)[None, :]
+    path = torch.where((ar >= rows[:, None])[..., None], x[:, None, :], path)
+    rgb = torch.where((R == 0)[:, None], torch.zeros_like(C), C / torch.where(R == 0, torch.ones_like(R), R)[:, None])
+    out = (path, steps.to(torch.int32), rgb, contacts.to(torch.int32), stop)
+    return out + (t,) if headings else out
 
 
 def resample_composed(path: torch.Tensor, steps: torch.Tensor, L: int) -> torch.Tensor:
@@ -257,6 +333,28 @@ class HairField:
                                                       beta, rho_min, max_coast, _ptr(path), _ptr(steps), _ptr(rgb)))
         return path, steps, rgb
 
+    def trace_guarded_hip(self, mesh, roots, normals, M: int, r2: float, h: float, beta: float, rho_min: float, max_coast: int,
+                          margin: float, sort: bool = True):
+        """``ghr_field_trace_guarded``: ``trace_hip`` with ``mesh`` (a ``HeadMesh``) asked at every step.
+        -> ``path, steps, rgb, contacts [S] int32, stop [S] uint8``."""
+        S, dev = roots.shape[0], roots.device
+        with torch.cuda.device(dev):
+            path = torch.empty(S, M + 1, 3, dtype=torch.float32, device=dev)
+            steps = torch.empty(S, dtype=torch.int32, device=dev)
+            rgb = torch.empty(S, 3, dtype=torch.float32, device=dev)
+            contacts = torch.empty(S, dtype=torch.int32, device=dev)
+            stop = torch.empty(S, dtype=torch.uint8, device=dev)
+            if S:
+                ws = self.workspace()
+                order = self._key_order(roots) if sort else None
+                tris, _bounds = mesh._tris_tables(dev)
+                grid = mesh._tables(dev)
+                _lib.check(_lib.lib().ghr_field_trace_guarded(
+                    _stream(), self.P, _ptr(ws), ctypes.byref(mesh._tris_header), _ptr(tris), ctypes.byref(mesh.header), _ptr(grid), S,
+                    _ptr(roots), _ptr(normals), _ptr(order), M, r2, h, beta, rho_min, max_coast, margin, _ptr(path), _ptr(steps),
+                    _ptr(rgb), _ptr(contacts), _ptr(stop)))
+        return path, steps, rgb, contacts, stop
+
     # -- public
     def query(self, points, headings, radius: Optional[float] = None, fused: Optional[bool] = None):
         """``points [Q, 3]``, ``headings [Q, 3]`` -> ``(rho [Q], v [Q, 3], c [Q, 3], n [Q] int32)``, none normalised.
@@ -316,17 +414,26 @@ def resample_strands(path: torch.Tensor, steps: torch.Tensor, L: int, fused: Opt
 @torch.no_grad()
 def grow_strands(field: HairField, roots, normals, L: int = 100, radius: Optional[float] = None, step: Optional[float] = None,
                  max_steps: int = 400, rho_min: Optional[float] = None, beta: float = 0.5, max_coast: int = 4, min_steps: int = 8,
-                 mesh=None, fused: Optional[bool] = None) -> dict:
+                 mesh=None, fused: Optional[bool] = None, avoid: bool = False, margin: Optional[float] = None) -> dict:
     """Grow one strand from every root ``roots [S, 3]`` along ``normals [S, 3]`` through ``field`` and resample it to ``L`` points.
 
     -> ``dict(points [S', L, 3], keep [S] bool, steps [S] int32, rgb [S', 3], path [S, max_steps + 1, 3], radius, step, rho_min)``:
     ``keep`` marks the strands with ``steps >= min_steps`` that, with ``mesh`` (a ``HeadMesh``), also pass
-    ``between_stages.prune_strands``; ``points`` and ``rgb`` hold those, in the roots' order.  The trace itself knows no mesh."""
+    ``between_stages.prune_strands``; ``points`` and ``rgb`` hold those, in the roots' order.
+
+    ``avoid=False``: the trace itself knows no mesh; ``mesh`` only prunes afterwards.  ``avoid=True`` (needs ``mesh``): the guarded
+    trace of ``csrc/ghr_grow.h`` keeps every step at least ``margin`` off the head (``margin=None``: the step ``h``, a look constant,
+    chosen and not measured); the result gains ``contacts [S]`` int32 (contact steps), ``stop [S]`` uint8 (0 ran out of
+    ``max_steps``, 1 coasted out of support, 2 met the head head-on) and ``margin``.  ``mesh`` still prunes afterwards."""
     roots, normals = _rows3(roots, "roots").contiguous(), _rows3(normals, "normals").contiguous()
     if roots.shape != normals.shape:
         raise ValueError("grow_strands: roots and normals must have the same shape")
     if L < 2 or max_steps < 1 or max_coast < 0 or not 0.0 <= beta <= 1.0:
         raise ValueError("grow_strands: needs L >= 2, max_steps >= 1, max_coast >= 0 and beta in [0, 1]")
+    if avoid and mesh is None:
+        raise ValueError("grow_strands: avoid=True needs mesh")
+    if margin is not None and not avoid:
+        raise ValueError("grow_strands: margin is the guarded trace's; give avoid=True")
     hip = field._use_hip(fused, "grow_strands", roots, normals)
     use = bool(hip)
     r = _f32(field.default_radius(use) if radius is None else radius)
@@ -335,19 +442,33 @@ def grow_strands(field: HairField, roots, normals, L: int = 100, radius: Optiona
     if not (r > 0 and h > 0 and rmin > 0):
         raise ValueError("grow_strands: radius, step and rho_min must be positive (got %g, %g, %g)" % (r, h, rmin))
     r2, beta = _f32(np.float32(r) * np.float32(r)), _f32(beta)
-    if hip:
+    extra = {}
+    if avoid:
+        m = _f32(h if margin is None else margin)
+        if not (m > 0 and np.isfinite(m)):
+            raise ValueError("grow_strands: margin must be positive and finite (got %g)" % m)
+    if hip and avoid:
+        path, steps, rgb, contacts, stop = field.trace_guarded_hip(mesh, roots, normals, int(max_steps), r2, h, beta, rmin,
+                                                                   int(max_coast), m)
+    elif hip:
         path, steps, rgb = field.trace_hip(roots, normals, int(max_steps), r2, h, beta, rmin, int(max_coast))
     else:
         dt = field.points.dtype
 
         def fn(x, t):
             return field_composed(field.points, field.directions, field.weights, field.colors, x, t, r2)
-        path, steps, rgb = trace_composed(fn, roots.to(dt), normals.to(dt), int(max_steps), h, beta, rmin, int(max_coast))
+        if avoid:
+            path, steps, rgb, contacts, stop = trace_guarded_composed(fn, mesh, roots.to(dt), normals.to(dt), int(max_steps), h, beta,
+                                                                      rmin, int(max_coast), m)
+        else:
+            path, steps, rgb = trace_composed(fn, roots.to(dt), normals.to(dt), int(max_steps), h, beta, rmin, int(max_coast))
+    if avoid:
+        extra = dict(contacts=contacts, stop=stop, margin=m)
     keep = steps >= min_steps
     points = resample_strands(path[keep].contiguous(), steps[keep].contiguous(), L, fused=use)
     if mesh is not None:
         from .between_stages import prune_strands
-        points, outside = prune_strands(points, mesh)
+        points, outside = prune_strands(points, mesh, fused=use)   # (the comparator where the trace was composed)
         keep = keep.clone()
         keep[keep.clone()] = outside
-    return dict(points=points, keep=keep, steps=steps, rgb=rgb[keep], path=path, radius=r, step=h, rho_min=rmin)
+    return dict(points=points, keep=keep, steps=steps, rgb=rgb[keep], path=path, radius=r, step=h, rho_min=rmin, **extra)

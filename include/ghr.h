@@ -1146,6 +1146,24 @@ int ghr_field_trace(void* stream, int64_t P, const void* ws, int64_t S, const fl
                     int32_t* steps, float* rgb);
 int ghr_strands_resample(void* stream, int64_t S, int32_t M, int32_t L, const float* path, const int32_t* steps, float* out);
 
+/* ---- the guarded trace: strands grown around the head mesh (csrc/ghr_grow.h)
+ * Added without an ABI_VERSION bump: one new function, no existing struct or signature changed.
+ * ghr_field_trace with the head mesh asked at every step: where that trace sets x += h t, y = x + h t is given to
+ * ghr_mesh_closest's closest point and ghr_mesh_contains' containment; a y whose signed distance is below margin is projected to
+ * margin above its closest point and the heading's component into the surface is removed (the definition is at the top of
+ * csrc/ghr_grow.h).  A strand's bits depend on nothing but the cloud, the mesh and the strand's own arguments.
+ * ws: a field workspace after ghr_field_build; tris_header / tris_dev: the triangle blob of ghr_mesh_tris_build (device copy);
+ * grid_header / grid_dev: the grid blob of ghr_mesh_grid_build (device copy); root_order as ghr_field_trace's (may be NULL).
+ * path [S][M + 1][3], steps [S] int32, rgb [S][3], contacts [S] int32 (contact steps), stop [S] bytes (0: ran out of M, 1: coasted
+ * out of support, 2: met the head head-on): every element written.
+ * Refused, with GHR_E_INVALID and a ghr_last_error() text before the runtime is touched: everything ghr_field_trace refuses,
+ * margin <= 0 or not finite, a NULL contacts / stop, a NULL header or blob, a header whose magic or sizes are not its kind's.
+ * S == 0 does nothing. */
+int ghr_field_trace_guarded(void* stream, int64_t P, const void* ws, const ghr_mesh_tris* tris_header, const void* tris_dev,
+                            const ghr_mesh_grid* grid_header, const void* grid_dev, int64_t S, const float* roots, const float* normals,
+                            const int64_t* root_order, int32_t M, float r2, float h, float beta, float rho_min, int32_t max_coast,
+                            float margin, float* path, int32_t* steps, float* rgb, int32_t* contacts, uint8_t* stop);
+
 /* Introspection for tests (device pointers into the workspaces; layout is otherwise private). */
 typedef struct ghr_ws_view {
     const float* rec;          /* [P][16]: x, y, conic a, b, c, opacity, features[10] */

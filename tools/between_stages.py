@@ -19,11 +19,12 @@
 
     python tools/between_stages.py grow   --ply STAGE1.ply | --model_path M  --scalp SCALP.obj --out_dir DIR [--scalp_uvs UV]
                                           [--num_strands 30000] [--strand_length 100] [--radius R] [--step_length H] [--max_steps 400]
-                                          [--mesh HEAD.obj] [--seed 0]
+                                          [--mesh HEAD.obj [--avoid [--margin M]]] [--seed 0]
         the hair Gaussians of a stage-1 model (default M/point_cloud_filtered/iteration_N/point_cloud.ply) -> an initial groom grown
         from roots sampled on the scalp along its normals (strand_growing.grow_strands): DIR/N_strands.pkl,
-        DIR/N_strands.ply, DIR/N_strands_rgb.npy.  --mesh prunes the strands that run inside the head.  Without --scalp_uvs the
-        scalp's two widest coordinates stand in for its UV map (only the roots' normals are used, not their tangents).
+        DIR/N_strands.ply, DIR/N_strands_rgb.npy.  --mesh prunes the strands that run inside the head; with --avoid the trace itself
+        keeps every step at least M off the head (default M: the step length).  Without --scalp_uvs the scalp's two
+        widest coordinates stand in for its UV map (only the roots' normals are used, not their tangents).
 
 (src/preprocessing/scale_scene_into_sphere.py, filter_flame_intersections.py, export_strands.py,
 extract_non_visible_head_scalp.py.)  Containment and visibility run in HIP on cuda:0; --composed evaluates the PyTorch-composed
@@ -102,10 +103,15 @@ def _grow(a, fused, dev):
     roots = sgen.sample_roots(v, f, uv, a.num_strands, generator=torch.Generator().manual_seed(a.seed))
     normals = roots["local2world"][:, :, 2].contiguous()
     out = sg.grow_strands(field, roots["origins"].to(dev), normals.to(dev), L=a.strand_length, radius=a.radius, step=a.step_length,
-                          max_steps=a.max_steps, mesh=HeadMesh.from_obj(a.mesh) if a.mesh else None, fused=fused)
+                          max_steps=a.max_steps, mesh=HeadMesh.from_obj(a.mesh) if a.mesh else None, fused=fused, avoid=a.avoid,
+                          margin=a.margin)
     print("grow: %d hair Gaussians, radius %.5g, step %.5g, rho_min %.5g; kept %d of %d strands (steps: median %d, longest %d)"
           % (field.P, out["radius"], out["step"], out["rho_min"], int(out["keep"].sum()), a.num_strands,
              int(out["steps"].float().median()), int(out["steps"].max())))
+    if a.avoid:
+        stop = torch.bincount(out["stop"].long().cpu(), minlength=3).tolist()
+        print("grow: margin %.5g; contact steps per strand: median %d, most %d; stopped: %d out of steps, %d coasted out, %d head-on"
+              % (out["margin"], int(out["contacts"].float().median()), int(out["contacts"].max()), stop[0], stop[1], stop[2]))
     print("export: %s %s" % bs.export_strands(out["points"], a.out_dir, a.iter))
     np.save(os.path.join(a.out_dir, "%s_strands_rgb.npy" % a.iter), out["rgb"].cpu().numpy())
 
@@ -140,6 +146,8 @@ def main(argv=None):
     ap.add_argument("--max_steps", type=int, default=400)
     ap.add_argument("--label_threshold", type=float, default=0.5)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--avoid", action="store_true")
+    ap.add_argument("--margin", type=float, default=None)
     a = ap.parse_args(argv)
     fused = not a.composed
     dev = torch.device(a.device or ("cuda:0" if fused else "cpu"))
