@@ -37,6 +37,7 @@
 #include "ghr_mesh.h"
 #include "ghr_meshdist.h"
 #include "ghr_grow.h"
+#include "ghr_shape.h"
 #include "ghr_visibility.h"
 #include "ghr_strandview.h"
 #include "ghr_capture.h"
@@ -3148,6 +3149,76 @@ int ghr_strands_resample(void* stream, int64_t S, int32_t M, int32_t L, const fl
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(ghr::k_strands_resample, dim3((unsigned)((S * L + GHR_FIELD_BLOCK - 1) / GHR_FIELD_BLOCK)), dim3(GHR_FIELD_BLOCK),
                        0, s, (int)S, (int)M, (int)L, path, steps, out);
+    return finish(s, 0);
+}
+
+}  // extern "C"
+
+// ---- the strand shape term: neighbours over the roots, forward, backward (ghr_shape.h) --------------------------------------------
+namespace {
+// the sizes the three entries share, before anything touches the runtime
+const char* shape_sizes(int64_t S, int64_t n)
+{
+    if (S < 0) return "S < 0";
+    if (n < 1) return "n < 1";
+    if (GHR_SHAPE_K * S >= ((int64_t)1 << 31) || S * n * 3 >= ((int64_t)1 << 31)) return "sizes exceed the kernels' 32-bit indexing";
+    return nullptr;
+}
+unsigned shape_blocks(int64_t S) { return (unsigned)((S + GHR_SHAPE_BLOCK / GHR_SHAPE_WAVE - 1) / (GHR_SHAPE_BLOCK / GHR_SHAPE_WAVE)); }
+}  // namespace
+
+extern "C" {
+
+int ghr_shape_neighbours(void* stream, int32_t S, const float* roots, float r2, int32_t* nbr)
+{
+    static const char* fn = "ghr_shape_neighbours: %s";
+    if (const char* why = shape_sizes(S, 1)) return lt_bad(fn, why);
+    if (!(r2 > 0.f)) return lt_bad(fn, "r2 must be positive (+inf: no cut)");
+    if (!roots) return lt_bad(fn, "roots is NULL");
+    if (!nbr) return lt_bad(fn, "nbr is NULL");
+    if (S == 0) return GHR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ghr::k_shape_nbr, dim3((unsigned)((S + GHR_SHAPE_WAVE - 1) / GHR_SHAPE_WAVE)), dim3(GHR_SHAPE_WAVE), 0, s, (int)S, roots,
+                       r2, nbr);
+    return finish(s, 0);
+}
+
+int ghr_shape_forward(void* stream, int32_t S, int32_t n, const float* dirs, const float* rest, const int32_t* nbr, int64_t M,
+                      float* partial, float* E)
+{
+    static const char* fn = "ghr_shape_forward: %s";
+    if (const char* why = shape_sizes(S, n)) return lt_bad(fn, why);
+    if (M < 0) return lt_bad(fn, "M < 0");
+    if (M > (int64_t)GHR_SHAPE_K * S) return lt_bad(fn, "M > 4 S: more pairs than choices");
+    if (!dirs || !rest || !nbr) return lt_bad(fn, "dirs, rest or nbr is NULL");
+    if (!partial || !E) return lt_bad(fn, "partial or E is NULL");
+    if (S == 0) return GHR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    ghr::ShapeArgs a{};
+    a.S = S; a.n = n; a.dirs = dirs; a.rest = rest; a.nbr = nbr; a.partial = partial;
+    ghr::shape_divisors(S, n, M, a.div);
+    hipLaunchKernelGGL(ghr::k_shape_fwd, dim3(shape_blocks(S)), dim3(GHR_SHAPE_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(ghr::k_shape_fold, dim3(1), dim3(GHR_SHAPE_FOLD), 0, s, (int)S, (const float*)partial, a.div[0], a.div[1], a.div[2], E);
+    return finish(s, 0);
+}
+
+int ghr_shape_backward(void* stream, int32_t S, int32_t n, const float* dirs, const float* rest, const int32_t* nbr, const int32_t* start,
+                       const int32_t* list, int64_t M, const float* dE, float* d_dirs)
+{
+    static const char* fn = "ghr_shape_backward: %s";
+    if (const char* why = shape_sizes(S, n)) return lt_bad(fn, why);
+    if (M < 0) return lt_bad(fn, "M < 0");
+    if (M > (int64_t)GHR_SHAPE_K * S) return lt_bad(fn, "M > 4 S: more pairs than choices");
+    if (!dirs || !rest || !nbr) return lt_bad(fn, "dirs, rest or nbr is NULL");
+    if (!start || !list) return lt_bad(fn, "start or list is NULL");
+    if (!dE) return lt_bad(fn, "dE is NULL");
+    if (!d_dirs) return lt_bad(fn, "d_dirs is NULL");
+    if (S == 0) return GHR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    ghr::ShapeArgs a{};
+    a.S = S; a.n = n; a.dirs = dirs; a.rest = rest; a.nbr = nbr; a.start = start; a.list = list; a.M = (int)M; a.dE = dE; a.d_dirs = d_dirs;
+    ghr::shape_divisors(S, n, M, a.div);
+    hipLaunchKernelGGL(ghr::k_shape_bwd, dim3(shape_blocks(S)), dim3(GHR_SHAPE_BLOCK), 0, s, a);
     return finish(s, 0);
 }
 

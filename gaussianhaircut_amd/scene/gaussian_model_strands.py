@@ -74,6 +74,15 @@ class GaussianModelStrands(GaussianModel):
         self.Lsds = None
         self.collision = None
         self.Lpen = None
+        self.shape = None
+        self.Lshape = None
+
+    def attach_shape(self, shape):
+        """``shape``: a callable ``dirs [S, n, 3] -> Lshape`` (``strand_shape.StrandShape``).  From now on
+        ``initialize_gaussians_hair()`` sets ``self.Lshape`` from the strand directions; ``None`` detaches.  Off by default."""
+        self.shape = shape
+        self.Lshape = None
+        return self
 
     def attach_collision(self, collision):
         """``collision``: a callable ``pts [S, L, 3] -> Lpen`` (``strand_collision.HeadCollision``).  From now on
@@ -142,17 +151,20 @@ class GaussianModelStrands(GaussianModel):
             origins, dirs = pts[:, :1], pts[:, 1:] - pts[:, :-1]
         return self.create_from_strands(origins, dirs, features, conf, spatial_lr_scale)
 
-    def initialize_gaussians_hair(self, prior: bool = True, collision: bool = True):
+    def initialize_gaussians_hair(self, prior: bool = True, collision: bool = True, shape: bool = True):
         """gaussian_model_strands.py:435-515.  On a ROCm device one HIP kernel each way (``ghr_strand_build``, csrc/ghr_strands.h)
         instead of ~55 PyTorch kernels per iteration; the polyline points ``_pts`` are then made on first use.  With a prior
         attached (``attach_prior``) and ``prior`` true, ``self.Lsds`` is computed from the strand directions (:456-515);
         ``prior=False`` rebuilds the Gaussians only (a step's further views) and leaves ``Lsds`` as it is.  Likewise ``self.Lpen``
-        with a collision term attached (``attach_collision``), unless ``collision`` is false (a step whose weight for it is 0)."""
+        with a collision term attached (``attach_collision``), unless ``collision`` is false (a step whose weight for it is 0), and
+        ``self.Lshape`` with a shape term attached (``attach_shape``), unless ``shape`` is false."""
         if getattr(self, "use_sds", False) and prior:
             self.Lsds = self.prior(self._dirs)
         if getattr(self, "collision", None) is not None and prior and collision:
             self.__dict__.pop("_pts_value", None)  # the points of the CURRENT directions
             self.Lpen = self.collision(self._pts)
+        if getattr(self, "shape", None) is not None and prior and shape:
+            self.Lshape = self.shape(self._dirs)
         self._dir = self._dirs.reshape(-1, 3)
         if FUSED_STRAND_BUILD and _strand_build_applies(self.pts_origins, self._dirs):
             self.__dict__.pop("_pts_value", None)

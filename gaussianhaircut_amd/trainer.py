@@ -541,14 +541,19 @@ def strand_training_step(gaussians, gaussians_hair, cams: List, background, opt,
     strand model the step's first rebuild computes ``Lsds`` and ``Lsds * opt.lambda_dsds`` joins the first view's loss, whole
     (not divided by the number of views); the term has no NaN drop (the reference has none): a NaN reaches ``_dirs.grad`` and
     the step is skipped by the guard below.  A collision term attached to the strand model (``attach_collision``) joins the same
-    way as ``Lpen * opt.lambda_dpen`` -- only when ``opt.lambda_dpen`` is there and not 0: otherwise it is not evaluated."""
+    way as ``Lpen * opt.lambda_dpen`` -- only when ``opt.lambda_dpen`` is there and not 0: otherwise it is not evaluated.  A shape
+    term (``attach_shape``, strand_shape.py) likewise, as ``Lshape * opt.lambda_dshape``."""
     use_sds = bool(getattr(gaussians_hair, "use_sds", False))
     attached = getattr(gaussians_hair, "collision", None) is not None
     use_pen = attached and getattr(opt, "lambda_dpen", 0.0) != 0
+    shaped = getattr(gaussians_hair, "shape", None) is not None
+    use_shape = shaped and getattr(opt, "lambda_dshape", 0.0) != 0
+    first = {}
     if attached:
-        gaussians_hair.initialize_gaussians_hair(collision=use_pen)
-    else:
-        gaussians_hair.initialize_gaussians_hair()
+        first["collision"] = use_pen
+    if shaped:
+        first["shape"] = use_shape
+    gaussians_hair.initialize_gaussians_hair(**first)
     gaussians_hair.update_learning_rate(iteration)
     V = len(cams)
     losses = []
@@ -575,10 +580,12 @@ def strand_training_step(gaussians, gaussians_hair, cams: List, background, opt,
                 loss = loss + gaussians_hair.Lsds.to(loss.dtype) * opt.lambda_dsds
             if use_pen and view == 0:
                 loss = loss + gaussians_hair.Lpen.to(loss.dtype) * opt.lambda_dpen
+            if use_shape and view == 0:
+                loss = loss + gaussians_hair.Lshape.to(loss.dtype) * opt.lambda_dshape
             loss.backward(gradient=_one_like(loss))
             losses.append(loss.detach())
             if cam is not cams[-1]:  # a fresh graph for the next view (the prior's term is in the first view's already)
-                if use_sds or attached:
+                if use_sds or attached or shaped:
                     gaussians_hair.initialize_gaussians_hair(prior=False)
                 else:
                     gaussians_hair.initialize_gaussians_hair()

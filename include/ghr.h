@@ -1164,6 +1164,25 @@ int ghr_field_trace_guarded(void* stream, int64_t P, const void* ws, const ghr_m
                             const int64_t* root_order, int32_t M, float r2, float h, float beta, float rho_min, int32_t max_coast,
                             float margin, float* path, int32_t* steps, float* rgb, int32_t* contacts, uint8_t* stop);
 
+/* ---- the strand shape term: stretch, bend, neighbour coherence of explicit strands (csrc/ghr_shape.h)
+ * Added without an ABI_VERSION bump: three new functions, no existing struct or signature changed.
+ * The definition -- the three means, the dead rule, the order of every sum -- is at the top of csrc/ghr_shape.h; a result's bits
+ * depend on the inputs alone.
+ * ghr_shape_neighbours: roots [S][3] -> nbr [S][4] int32: the 4 nearest OTHER roots by squared distance, ascending, ties to the
+ * lower index; -1 where the squared distance exceeds r2 (+inf: no cut) or fewer than 4 other roots exist.  Every element written.
+ * ghr_shape_forward: dirs [S][n][3], rest [S] (> 0), nbr [S][4] (another strand or -1), M the number of entries of nbr that are
+ * >= 0 -> partial [S][3] (the per-strand sums) and E [3] (the means): every element written.
+ * ghr_shape_backward: start [S + 1] / list [M]: per strand the entries 4 t + k with nbr[t][k] == s, ascending; dE [3] on the
+ * device -> d_dirs [S][n][3], every element assigned.  An entry of nbr or list outside [0, S) is skipped, and a range of start that
+ * does not lie inside the M entries of list is read as empty.
+ * Refused, with GHR_E_INVALID and a ghr_last_error() text before the runtime is touched: S < 0, n < 1, M < 0 or > 4 S, r2 <= 0 or
+ * NaN, a NULL buffer, sizes beyond 32-bit indexing.  S == 0 does nothing. */
+int ghr_shape_neighbours(void* stream, int32_t S, const float* roots, float r2, int32_t* nbr);
+int ghr_shape_forward(void* stream, int32_t S, int32_t n, const float* dirs, const float* rest, const int32_t* nbr, int64_t M,
+                      float* partial, float* E);
+int ghr_shape_backward(void* stream, int32_t S, int32_t n, const float* dirs, const float* rest, const int32_t* nbr, const int32_t* start,
+                       const int32_t* list, int64_t M, const float* dE, float* d_dirs);
+
 /* Introspection for tests (device pointers into the workspaces; layout is otherwise private). */
 typedef struct ghr_ws_view {
     const float* rec;          /* [P][16]: x, y, conic a, b, c, opacity, features[10] */

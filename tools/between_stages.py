@@ -19,12 +19,14 @@
 
     python tools/between_stages.py grow   --ply STAGE1.ply | --model_path M  --scalp SCALP.obj --out_dir DIR [--scalp_uvs UV]
                                           [--num_strands 30000] [--strand_length 100] [--radius R] [--step_length H] [--max_steps 400]
-                                          [--mesh HEAD.obj [--avoid [--margin M]]] [--seed 0]
+                                          [--mesh HEAD.obj [--avoid [--margin M]]] [--seed 0] [--smooth ITER]
         the hair Gaussians of a stage-1 model (default M/point_cloud_filtered/iteration_N/point_cloud.ply) -> an initial groom grown
         from roots sampled on the scalp along its normals (strand_growing.grow_strands): DIR/N_strands.pkl,
         DIR/N_strands.ply, DIR/N_strands_rgb.npy.  --mesh prunes the strands that run inside the head; with --avoid the trace itself
         keeps every step at least M off the head (default M: the step length).  Without --scalp_uvs the scalp's two
-        widest coordinates stand in for its UV map (only the roots' normals are used, not their tangents).
+        widest coordinates stand in for its UV map (only the roots' normals are used, not their tangents).  --smooth ITER runs ITER
+        Adam steps on the strand shape term alone (stretch, bend, neighbour coherence; DESIGN.md 8u) over the groom before export;
+        the term knows no mesh, so with --avoid the points it moved inside the margin are counted and printed.
 
 (src/preprocessing/scale_scene_into_sphere.py, filter_flame_intersections.py, export_strands.py,
 extract_non_visible_head_scalp.py.)  Containment and visibility run in HIP on cuda:0; --composed evaluates the PyTorch-composed
@@ -112,7 +114,21 @@ def _grow(a, fused, dev):
         stop = torch.bincount(out["stop"].long().cpu(), minlength=3).tolist()
         print("grow: margin %.5g; contact steps per strand: median %d, most %d; stopped: %d out of steps, %d coasted out, %d head-on"
               % (out["margin"], int(out["contacts"].float().median()), int(out["contacts"].max()), stop[0], stop[1], stop[2]))
-    print("export: %s %s" % bs.export_strands(out["points"], a.out_dir, a.iter))
+    points = out["points"]
+    if a.smooth > 0 and points.shape[0] > 0:
+        from gaussianhaircut_amd import strand_shape as ss
+        shape = ss.StrandShape(points[:, :1], points[:, 1:] - points[:, :-1], fused=fused)
+        before = shape.terms(points[:, 1:] - points[:, :-1]).tolist()
+        points = ss.smooth_polylines(points, a.smooth, fused=fused, shape=shape)
+        after = shape.terms(points[:, 1:] - points[:, :-1]).tolist()
+        print("smooth: %d Adam steps on the shape term; stretch %.4g -> %.4g, bend %.4g -> %.4g, coherence %.4g -> %.4g"
+              % (a.smooth, before[0], after[0], before[1], after[1], before[2], after[2]))
+        if a.avoid:  # the term knows no mesh: say what it undid of the guarded trace
+            from gaussianhaircut_amd.mesh import signed_distance
+            sd = signed_distance(points[:, 1:].reshape(-1, 3), HeadMesh.from_obj(a.mesh), fused=fused)
+            print("smooth: %d of %d free points are now nearer to the head than the margin %.5g"
+                  % (int((sd < out["margin"]).sum()), sd.numel(), out["margin"]))
+    print("export: %s %s" % bs.export_strands(points, a.out_dir, a.iter))
     np.save(os.path.join(a.out_dir, "%s_strands_rgb.npy" % a.iter), out["rgb"].cpu().numpy())
 
 
@@ -148,6 +164,7 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--avoid", action="store_true")
     ap.add_argument("--margin", type=float, default=None)
+    ap.add_argument("--smooth", type=int, default=0)
     a = ap.parse_args(argv)
     fused = not a.composed
     dev = torch.device(a.device or ("cuda:0" if fused else "cpu"))
