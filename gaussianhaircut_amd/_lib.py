@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GHR_LIB_PATH") or os.path.join(CSRC, "libghr_hip.so")  # override: kernel experiments
 SOURCES = ["ghr_capi.hip"]
 HEADERS = ["ghr_device.h", "ghr_preprocess.h", "ghr_binning.h", "ghr_render_fwd.h", "ghr_render_bwd.h", "ghr_render_bwd2.h", "ghr_render_bwd3.h",
-           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_products.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_meshdist.h", "ghr_tilelists.h", "ghr_visibility.h", "ghr_strandview.h", "ghr_sds.h", "ghr_nn.h", "ghr_compare.h", "ghr_texstrands.h", "ghr_guides.h", "ghr_haar.h", "ghr_capture.h", "ghr_field.h", "ghr_grow.h", "ghr_shape.h"]
+           "ghr_geom_bwd.h", "ghr_project.h", "ghr_loss.h", "ghr_adam.h", "ghr_strands.h", "ghr_knn.h", "ghr_camera.h", "ghr_eval.h", "ghr_products.h", "ghr_orient.h", "ghr_gt.h", "ghr_latent.h", "ghr_shared.h", "ghr_mesh.h", "ghr_meshdist.h", "ghr_tilelists.h", "ghr_visibility.h", "ghr_strandview.h", "ghr_sds.h", "ghr_nn.h", "ghr_compare.h", "ghr_texstrands.h", "ghr_guides.h", "ghr_haar.h", "ghr_capture.h", "ghr_field.h", "ghr_grow.h", "ghr_shape.h", "ghr_upsample.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics", "-fPIC",
                "-shared"]
 
@@ -255,7 +255,8 @@ EXPORTS = ["ghr_last_error", "ghr_abi_version", "ghr_forward_sizes", "ghr_binnin
            "ghr_guides_blend", "ghr_guides_blend_backward",
            "ghr_field_workspace_size", "ghr_field_build", "ghr_field_query", "ghr_field_trace", "ghr_strands_resample",
            "ghr_field_trace_guarded",
-           "ghr_shape_neighbours", "ghr_shape_forward", "ghr_shape_backward"]
+           "ghr_shape_neighbours", "ghr_shape_forward", "ghr_shape_backward",
+           "ghr_upsample_neighbours", "ghr_upsample_blend"]
 
 _lib = None
 
@@ -401,6 +402,8 @@ def lib() -> ctypes.CDLL:
     L.ghr_shape_neighbours.argtypes = [vp, i32, vp, f32, vp]
     L.ghr_shape_forward.argtypes = [vp, i32, i32, vp, vp, vp, ctypes.c_int64, vp, vp]
     L.ghr_shape_backward.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, ctypes.c_int64, vp, vp]
+    L.ghr_upsample_neighbours.argtypes = [vp, i32, vp, i32, vp, f32, vp, vp]
+    L.ghr_upsample_blend.argtypes = [vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, f32, f32, i32, vp, vp, vp, vp]
     L.ghr_ws_inspect.argtypes = [i32, i32, i32, i32, u32, vp, vp, vp, ctypes.POINTER(WsView)]
     for name in EXPORTS:
         fn = getattr(L, name)

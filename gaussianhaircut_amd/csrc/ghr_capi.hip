@@ -38,6 +38,7 @@
 #include "ghr_meshdist.h"
 #include "ghr_grow.h"
 #include "ghr_shape.h"
+#include "ghr_upsample.h"
 #include "ghr_visibility.h"
 #include "ghr_strandview.h"
 #include "ghr_capture.h"
@@ -3219,6 +3220,61 @@ int ghr_shape_backward(void* stream, int32_t S, int32_t n, const float* dirs, co
     a.S = S; a.n = n; a.dirs = dirs; a.rest = rest; a.nbr = nbr; a.start = start; a.list = list; a.M = (int)M; a.dE = dE; a.d_dirs = d_dirs;
     ghr::shape_divisors(S, n, M, a.div);
     hipLaunchKernelGGL(ghr::k_shape_bwd, dim3(shape_blocks(S)), dim3(GHR_SHAPE_BLOCK), 0, s, a);
+    return finish(s, 0);
+}
+
+}  // extern "C"
+
+// ---- groom upsampling: the guides nearest to every child root, the gated blend (ghr_upsample.h) -----------------------------------
+namespace {
+const int64_t UPS_LIMIT = (int64_t)1 << 31;
+}  // namespace
+
+extern "C" {
+
+int ghr_upsample_neighbours(void* stream, int32_t G, const float* guide_roots, int32_t N, const float* child_origins, float r2,
+                            int32_t* nbr, float* nd2)
+{
+    static const char* fn = "ghr_upsample_neighbours: %s";
+    if (G < 1) return lt_bad(fn, "G < 1");
+    if (N < 0) return lt_bad(fn, "N < 0");
+    if (!(r2 > 0.f)) return lt_bad(fn, "r2 must be positive (+inf: no cut)");
+    if (3 * (int64_t)G >= UPS_LIMIT || GHR_UPS_K * (int64_t)N >= UPS_LIMIT) return lt_bad(fn, "sizes exceed the kernels' 32-bit indexing");
+    if (!guide_roots || !child_origins) return lt_bad(fn, "guide_roots or child_origins is NULL");
+    if (!nbr || !nd2) return lt_bad(fn, "nbr or nd2 is NULL");
+    if (N == 0) return GHR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ghr::k_ups_near, dim3((unsigned)(((int64_t)N + GHR_UPS_BLOCK - 1) / GHR_UPS_BLOCK)), dim3(GHR_UPS_BLOCK), 0, s, (int)G,
+                       guide_roots, (int)N, child_origins, r2, nbr, nd2);
+    return finish(s, 0);
+}
+
+int ghr_upsample_blend(void* stream, int32_t G, int32_t L, const float* gp, const float* gM, const float* gf, int32_t F, int32_t N,
+                       const float* co, const float* cM, const int32_t* nbr, const float* nd2, float eps2, float tau, int32_t gate,
+                       float* out, float* w, float* of, uint8_t* valid)
+{
+    static const char* fn = "ghr_upsample_blend: %s";
+    if (G < 1) return lt_bad(fn, "G < 1");
+    if (N < 0) return lt_bad(fn, "N < 0");
+    if (L < 2) return lt_bad(fn, "L < 2");
+    if (F < 0) return lt_bad(fn, "F < 0");
+    if (!(eps2 > 0.f) || !(eps2 < INFINITY)) return lt_bad(fn, "eps2 must be positive and finite");
+    if (gate && !(tau >= -1.f && tau < 1.f)) return lt_bad(fn, "tau must lie in [-1, 1) while the gate is set");
+    const int64_t big = (int64_t)(G > N ? G : N);
+    if (big * L * 3 >= UPS_LIMIT || big * 9 >= UPS_LIMIT || big * F >= UPS_LIMIT || GHR_UPS_K * (int64_t)N >= UPS_LIMIT)
+        return lt_bad(fn, "sizes exceed the kernels' 32-bit indexing");
+    if (!gp || !gM) return lt_bad(fn, "gp or gM is NULL");
+    if (!co || !cM) return lt_bad(fn, "co or cM is NULL");
+    if (!nbr || !nd2) return lt_bad(fn, "nbr or nd2 is NULL");
+    if (F > 0 && (!gf || !of)) return lt_bad(fn, "gf or of is NULL while F > 0");
+    if (!out || !w || !valid) return lt_bad(fn, "out, w or valid is NULL");
+    if (N == 0) return GHR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    ghr::UpsArgs a{};
+    a.G = G; a.L = L; a.F = F; a.N = N; a.gp = gp; a.gM = gM; a.gf = gf; a.co = co; a.cM = cM; a.nbr = nbr; a.nd2 = nd2;
+    a.eps2 = eps2; a.tau = tau; a.gate = gate ? 1 : 0; a.out = out; a.w = w; a.of = of; a.valid = valid;
+    const int per = GHR_UPS_BLOCK / GHR_UPS_WAVE;
+    hipLaunchKernelGGL(ghr::k_ups_blend, dim3((unsigned)(((int64_t)N + per - 1) / per)), dim3(GHR_UPS_BLOCK), 0, s, a);
     return finish(s, 0);
 }
 

@@ -1183,6 +1183,26 @@ int ghr_shape_forward(void* stream, int32_t S, int32_t n, const float* dirs, con
 int ghr_shape_backward(void* stream, int32_t S, int32_t n, const float* dirs, const float* rest, const int32_t* nbr, const int32_t* start,
                        const int32_t* list, int64_t M, const float* dE, float* d_dirs);
 
+/* ---- groom upsampling: child strands blended from guide strands (csrc/ghr_upsample.h)
+ * Added without an ABI_VERSION bump: two new functions, no existing struct or signature changed.  Forward only.
+ * The definition -- the neighbour rule, the similarity gate, the weights, the order of every sum -- is at the top of
+ * csrc/ghr_upsample.h; a result's bits depend on the inputs alone.
+ * ghr_upsample_neighbours: guide_roots [G][3], child_origins [N][3] -> nbr [N][4] int32: the 4 nearest guides of every child by
+ * squared distance, ascending, ties to the lower index, and nd2 [N][4] their squared distances; -1 and +inf where the squared
+ * distance exceeds r2 (+inf: no cut) or fewer than 4 guides exist.  Every element written.
+ * ghr_upsample_blend: gp [G][L][3] the guides' points, gM [G][3][3] their local2world frames (row-major), gf [G][F] features (NULL
+ * when F == 0), co [N][3] / cM [N][3][3] the children's origins and frames, nbr / nd2 as above (the leading entries inside [0, G)
+ * are a child's list; any other value ends it and is never dereferenced), eps2, tau and gate (0: every similarity weight is 1)
+ * -> out [N][L][3], w [N][4], of [N][F] (NULL when F == 0), valid [N] uint8: every element written.
+ * Refused, with GHR_E_INVALID and a ghr_last_error() text before the runtime is touched: G < 1, N < 0, L < 2, F < 0, r2 <= 0 or
+ * NaN, eps2 <= 0 or not finite, tau outside [-1, 1) while gate is set, a NULL buffer (gf and of may be NULL when F == 0), sizes
+ * beyond 32-bit indexing.  N == 0 does nothing. */
+int ghr_upsample_neighbours(void* stream, int32_t G, const float* guide_roots, int32_t N, const float* child_origins, float r2,
+                            int32_t* nbr, float* nd2);
+int ghr_upsample_blend(void* stream, int32_t G, int32_t L, const float* gp, const float* gM, const float* gf, int32_t F, int32_t N,
+                       const float* co, const float* cM, const int32_t* nbr, const float* nd2, float eps2, float tau, int32_t gate,
+                       float* out, float* w, float* of, uint8_t* valid);
+
 /* Introspection for tests (device pointers into the workspaces; layout is otherwise private). */
 typedef struct ghr_ws_view {
     const float* rec;          /* [P][16]: x, y, conic a, b, c, opacity, features[10] */

@@ -28,6 +28,17 @@
         Adam steps on the strand shape term alone (stretch, bend, neighbour coherence; DESIGN.md 8u) over the groom before export;
         the term knows no mesh, so with --avoid the points it moved inside the margin are counted and printed.
 
+    python tools/between_stages.py upsample --points GUIDES.npy|GUIDES.pkl --scalp SCALP.obj --out_dir DIR --count 150000
+                                            [--scalp_uvs UV] [--seed 0] [--radius R] [--tau 0.5 | --no_gate] [--mesh HEAD.obj]
+                                            [--features RGB.npy] [--with_guides]
+        guide strands [G, L, 3] -> a denser groom (strand_upsampling.upsample_strands): --count child roots and
+        their frames drawn on the scalp (strand_generator.sample_roots), every child a blend of its 4 nearest guides in scalp-local
+        frames, gated by shape similarity at --tau; the guides' own frames are those of the scalp faces nearest to their roots
+        (strand_upsampling.frames_at).  The scalp's UVs come from --scalp_uvs, else from the obj's `vt` records (the first one a
+        vertex is used with), else its two widest coordinates stand in.  --radius leaves a child without a guide that near out;
+        --mesh prunes the children that run inside the head.  DIR/N_strands.pkl, DIR/N_strands.ply (--with_guides: the guides
+        first), and DIR/N_strands_rgb.npy when --features [G, F] is given.
+
 (src/preprocessing/scale_scene_into_sphere.py, filter_flame_intersections.py, export_strands.py,
 extract_non_visible_head_scalp.py.)  Containment and visibility run in HIP on cuda:0; --composed evaluates the PyTorch-composed
 forms instead (any device, slow)."""
@@ -132,9 +143,63 @@ def _grow(a, fused, dev):
     np.save(os.path.join(a.out_dir, "%s_strands_rgb.npy" % a.iter), out["rgb"].cpu().numpy())
 
 
+def _obj_uvs(path, num_vertices):
+    """[V, 2] from an obj's `vt` records through its faces' `v/vt` corners (the first one a vertex is used with), or None"""
+    vts, uv = [], {}
+    with open(path, "r") as fh:
+        for line in fh:
+            tok = line.split()
+            if not tok:
+                continue
+            if tok[0] == "vt":
+                vts.append([float(tok[1]), float(tok[2])])
+            elif tok[0] == "f":
+                for t in tok[1:]:
+                    part = t.split("/")
+                    if len(part) > 1 and part[1]:
+                        a, b = int(part[0]), int(part[1])
+                        uv.setdefault(a - 1 if a > 0 else num_vertices + a, b - 1 if b > 0 else len(vts) + b)
+    if not vts or len(uv) < num_vertices:
+        return None
+    return np.asarray([vts[uv[i]] for i in range(num_vertices)], np.float32)
+
+
+def _upsample(a, fused, dev):
+    from gaussianhaircut_amd import strand_generator as sgen
+    from gaussianhaircut_amd import strand_upsampling as su
+    from gaussianhaircut_amd.mesh import read_obj
+    guides = torch.from_numpy(np.ascontiguousarray(_load_array(a.points), np.float32)).to(dev)
+    v_np, f_np = read_obj(a.scalp)
+    v, f = torch.as_tensor(np.asarray(v_np, np.float32)), torch.as_tensor(np.asarray(f_np, np.int64))
+    uv = np.asarray(_load_array(a.scalp_uvs), np.float32).reshape(-1, 2) if a.scalp_uvs else _obj_uvs(a.scalp, len(v_np))
+    if uv is None:
+        wide = torch.argsort(v.max(0).values - v.min(0).values, descending=True)[:2].sort().values
+        uv = v[:, wide]
+    uv = torch.as_tensor(uv)
+    roots = sgen.sample_roots(v, f, uv, a.count, generator=torch.Generator().manual_seed(a.seed))
+    guide_frames = su.frames_at(HeadMesh(v_np, f_np), sgen.scalp_frames(v, f, uv), guides[:, 0], fused=fused)
+    feats = torch.from_numpy(np.ascontiguousarray(_load_array(a.features), np.float32)).to(dev) if a.features else None
+    out = su.upsample_strands(guides, guide_frames, roots["origins"].to(dev), roots["local2world"].to(dev), features=feats,
+                              radius=a.radius, tau=None if a.no_gate else a.tau, mesh=HeadMesh.from_obj(a.mesh) if a.mesh else None,
+                              fused=fused)
+    keep = out["keep"]
+    used = (out["weights"][out["valid"]] > 0).sum(1).float()
+    print("upsample: %d guides of %d points, %d children; eps2 %.5g; %d without a guide in reach, %d pruned by the head; kept %d "
+          "(guides carrying weight per child: mean %.2f)"
+          % (guides.shape[0], guides.shape[1], a.count, out["eps2"], int((~out["valid"]).sum()), int((out["valid"] & ~keep).sum()),
+             int(keep.sum()), float(used.mean()) if used.numel() else 0.0))
+    points = out["points"][keep]
+    if a.with_guides:
+        points = torch.cat([guides, points])
+    print("export: %s %s" % bs.export_strands(points, a.out_dir, a.iter))
+    if feats is not None:
+        rgb = out["features"][keep]
+        np.save(os.path.join(a.out_dir, "%s_strands_rgb.npy" % a.iter), (torch.cat([feats.reshape(guides.shape[0], -1), rgb]) if a.with_guides else rgb).cpu().numpy())
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("step", choices=["crop", "filter", "export", "split", "scalp", "grow"])
+    ap.add_argument("step", choices=["crop", "filter", "export", "split", "scalp", "grow", "upsample"])
     ap.add_argument("--model_path")
     ap.add_argument("--path_to_data")
     ap.add_argument("--mesh")
@@ -165,6 +230,11 @@ def main(argv=None):
     ap.add_argument("--avoid", action="store_true")
     ap.add_argument("--margin", type=float, default=None)
     ap.add_argument("--smooth", type=int, default=0)
+    ap.add_argument("--count", type=int, default=150_000)
+    ap.add_argument("--tau", type=float, default=0.5)
+    ap.add_argument("--no_gate", action="store_true")
+    ap.add_argument("--features")
+    ap.add_argument("--with_guides", action="store_true")
     a = ap.parse_args(argv)
     fused = not a.composed
     dev = torch.device(a.device or ("cuda:0" if fused else "cpu"))
@@ -173,6 +243,8 @@ def main(argv=None):
         _scalp(a, fused, dev)
     elif a.step == "grow":
         _grow(a, fused, dev)
+    elif a.step == "upsample":
+        _upsample(a, fused, dev)
     elif a.step == "crop":
         m = _load(os.path.join(a.model_path, "point_cloud", it, "raw_point_cloud.ply"), a.sh_degree, dev)
         tr, s = bs.hair_sphere(m)
